@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Assemble + MINRES throughput on synthetic binary trees (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -27,8 +27,16 @@ tree sweeps, true residual checked, rtol 1e-12, one refinement step if it misses
 P ranks one launch per rank, ``k_dir_xr``, exchanging the coarse partials and the residual
 with the other ranks' kernels through peer-mapped mailboxes, the two-all-reduce graph path
 as the fallback), with ``--solver minres`` preconditioned
-MINRES to rtol 1e-12. The other solver is timed on the same workload and reported beside
-(one GPU). Rank 0 prints one JSON line.
+MINRES to rtol 1e-12. Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the headline (``value``,
+``ms_per_step``). ``--dump-outputs DIR`` then writes what the last timed step computed (the
+solution, the rhs and the CSR values, ``DIR/<name>.npy``, float64; a fixed seeded sample of an
+array over its share of 64 MB); the workload is deterministic, so two builds can be compared
+array for array. ``--full`` adds every other leg after the headline: the per-kernel roofline,
+the isolated SpMV, the other solver on the same workload (one GPU), the public ``Solver``
+surface, the parity check against the analytic answer, rank 0's one-GPU time (P > 1), the
+configs[4] and general-degree legs and the CPU baseline.
 """
 
 from __future__ import annotations
@@ -149,6 +157,34 @@ def pmc_traffic(kernel_prefix: str):
             if name.startswith(kernel_prefix) and "hbm_bytes_per_launch" in d:
                 return d["hbm_bytes_per_launch"], f"profiles/{path.name}", d.get("avg_ns")
     return None, None, None
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes of array data over all files of one --dump-outputs
+DUMP_SEED = 20240  # the sample of an array that does not fit is the same in every run
+
+
+def dump_outputs(directory, arrays: dict, budget: int = DUMP_BUDGET, suffix: str = "") -> dict:
+    """Write ``arrays`` as ``directory/<name><suffix>.npy`` in float64. When together they
+    exceed ``budget`` bytes every array is cut to the same fraction: a sorted sample of its
+    entries drawn without replacement by a generator seeded with ``DUMP_SEED`` (so two runs
+    with the same arguments keep the same entries). Returns what was written, per name."""
+    import numpy as np
+
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, budget / total) if total else 1.0
+    rng = np.random.default_rng(DUMP_SEED)
+    info = {}
+    for name, a in arrays.items():
+        keep = a.size if frac >= 1.0 else int(a.size * frac)
+        if keep < a.size:
+            a = a[np.sort(rng.choice(a.size, size=keep, replace=False))]
+        np.save(directory / f"{name}{suffix}.npy", a)
+        info[name] = {"file": f"{name}{suffix}.npy", "entries": int(arrays[name].size),
+                      "written": int(a.size)}
+    return info
 
 
 def cpu_model() -> str:
@@ -491,6 +527,12 @@ def parse_args(argv=None):
                     help="tree generations (default: 15 at 1 GPU, 15 + log2(P) at P GPUs)")
     ap.add_argument("--N", type=int, default=None,
                     help="cells per edge (default 15 at every GPU count; 19: C4 at 8 GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg: roofline, isolated "
+                         "SpMV, the other solver, the public Solver surface, parity, strong "
+                         "scaling, configs[4], general degrees, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--rtol", type=float, default=1e-12)
     ap.add_argument("--check-every", type=int, default=4)
     ap.add_argument("--cpu-budget", type=float, default=20.0)
@@ -628,7 +670,7 @@ def run(args, world: int) -> int:
     asm.set_direct(direct)
     elapsed = timed_steps(h, args.steps, args.warmup, True)
     ms_per_step = 1e3 * elapsed / args.steps
-    iters = state["it"]
+    iters, relres, conv = state["it"], state["relres"], bool(state["conv"])
     solver_used = "direct" if h.solver()[1] == 1 else "minres"
     # every rank's path and exchange status after the timed steps (one all-reduce of a row
     # per rank): the driver's scaling run shows which ranks ran the exchange step
@@ -652,6 +694,73 @@ def run(args, world: int) -> int:
               "MINRES (a rank's decomposition cannot run it exactly); --allow-fallback "
               "measures the fallback", file=sys.stderr, flush=True)
         return 3
+
+    # --- what the last timed step computed, before any other leg touches the handle
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs,
+                              {"solution": h.solution(), "rhs": h.rhs(),
+                               "csr_values": h.csr()[2]},
+                              DUMP_BUDGET // world, f"_rank{rank}" if world > 1 else "")
+
+    def emit(roof=None, other=None, api_ms=None, api_host_ms=None, parity=None, strong=None,
+             c4=None, fe=None, cpu=None) -> int:
+        """Rank 0 prints the result line (the legs a plain run skips stay null)."""
+        if rank == 0:
+            out = {
+                "metric": METRIC,
+                "value": dof_total / (ms_per_step / 1e3),
+                "unit": "DoF/s",
+                "n_gpus": world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": ms_per_step,
+                "higher_is_better": True,
+                "scaling": "weak",
+                "vs_baseline": None,
+                "dtype": "f64",
+                "data": "synthetic (make_tree binary tree, p_bc = y, f = 0, R = 1)",
+                "config": {
+                    "workload": f"make_tree({levels},{levels},{levels}) depth-{levels - 1} "
+                                f"binary tree, N={N} cells/edge, assemble + solve "
+                                f"({solver_used}, rtol {args.rtol:g})",
+                    "dofs": dof_total,
+                    "nnz": E * (7 * N + 1) + 6 * B,
+                    "edges": E,
+                    "N": N,
+                    "solver": solver_used,
+                    "iterations": iters,
+                    "relres": relres,
+                    "converged": conv,
+                    "parallelism": f"edge-partition x{world}" if world > 1 else "single GPU",
+                    "rccl_ranks": h.comm_count() if world > 1 else None,
+                    "preconditioner": "tree Schur complement" if pc_on else "none",
+                },
+                "setup_s": setup,
+                "full": args.full,
+                "dumped_outputs": dumped,
+                "rank_status": rank_status,
+                "api_ms_per_step": api_ms,
+                "api_host_ms_per_step": api_host_ms,
+                "strong_scaling": strong,
+                "c4": c4,
+                "general_degrees": fe,
+                "solver": solver_used,
+                "roofline": roof,
+                "other_solver": other,
+                "cpu_baseline": cpu,
+                "parity": parity,
+            }
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        asm.close()
+        return 0
+
+    if not args.full:
+        return emit()
+
     # the committed PMC summaries profile the default workload (C3) on one GPU only
     default_workload = world == 1 and (levels, N) == (15, 15) and not args.no_pc
 
@@ -909,53 +1018,8 @@ def run(args, world: int) -> int:
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(mesh, asm, dof_total, args.cpu_budget)
 
-    if rank == 0:
-        out = {
-            "metric": METRIC,
-            "value": dof_total / (ms_per_step / 1e3),
-            "unit": "DoF/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (make_tree binary tree, p_bc = y, f = 0, R = 1)",
-            "config": {
-                "workload": f"make_tree({levels},{levels},{levels}) depth-{levels - 1} binary "
-                            f"tree, N={N} cells/edge, assemble + solve ({solver_used}, "
-                            f"rtol {args.rtol:g})",
-                "dofs": dof_total,
-                "nnz": E * (7 * N + 1) + 6 * B,
-                "edges": E,
-                "N": N,
-                "solver": solver_used,
-                "iterations": iters,
-                "parallelism": f"edge-partition x{world}" if world > 1 else "single GPU",
-                "rccl_ranks": h.comm_count() if world > 1 else None,
-                "preconditioner": "tree Schur complement" if pc_on else "none",
-            },
-            "setup_s": setup,
-            "rank_status": rank_status,
-            "api_ms_per_step": api_ms,
-            "api_host_ms_per_step": api_host_ms,
-            "strong_scaling": strong,
-            "c4": c4,
-            "general_degrees": fe,
-            "solver": solver_used,
-            "roofline": roof,
-            "other_solver": other,
-            "cpu_baseline": cpu,
-            "parity": parity,
-        }
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    asm.close()
-    return 0
+    return emit(roof=roof, other=other, api_ms=api_ms, api_host_ms=api_host_ms, parity=parity,
+                strong=strong, c4=c4, fe=fe, cpu=cpu)
 
 
 if __name__ == "__main__":

@@ -12,4 +12,4 @@ C4ARG=--no-c4
 [ "${C4:-0}" = 1 ] && C4ARG=
 NXHIP_TRANSPORT=host timeout -k 10 300 python -m torch.distributed.run --nnodes=1 \
   --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 \
-  --steps 20 --warmup 5 --levels "$LEVELS" --N 15 $C4ARG --api-steps 2
+  --full --steps 20 --warmup 5 --levels "$LEVELS" --N 15 $C4ARG --api-steps 2

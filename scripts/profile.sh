@@ -16,7 +16,7 @@ run() {  # name timeout args...
   echo "rc=$rc"; tail -n 5 "$OUT/$name.log"
   if [ $rc -ne 0 ]; then echo "stopping after $name"; exit $rc; fi
 }
-run trace 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace --output-format csv -- python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline "$@"
-run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o pmc --output-format csv -- python3 "$R/bench.py" --steps 1 --warmup 0 --no-cpu-baseline "$@"
-run pmc_write 600 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o pmc --output-format csv -- python3 "$R/bench.py" --steps 1 --warmup 0 --no-cpu-baseline "$@"
+run trace 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace --output-format csv -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline "$@"
+run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o pmc --output-format csv -- python3 "$R/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline "$@"
+run pmc_write 600 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o pmc --output-format csv -- python3 "$R/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline "$@"
 find "$OUT" -name '*.csv' | head -20

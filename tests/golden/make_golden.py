@@ -14,11 +14,16 @@ box; the fixtures it writes are small data files that travel with the repo):
   the CPU oracle (``oracle/nx_oracle.py``), its direct solution and the analytic
   resistor-network solution. No reference output exists for these values (DOLFINx /
   PETSc are not installed); they pin the oracle and the device path against drift.
+* ``citations.json`` -- what ``tests/test_citations.py`` needs to know about the reference
+  files it checks citations against: each file's line count and, per anchor of that test,
+  the numbers of the lines that contain the anchor's text (numbers only). Written alone by
+  ``python tests/golden/make_golden.py citations [reference checkout]``.
 """
 
 from __future__ import annotations
 
 import importlib.util
+import json
 import sys
 import types
 from pathlib import Path
@@ -124,5 +129,26 @@ def main() -> None:
     print("wrote", HERE / "graphs.npz", "and", HERE / "systems.npz")
 
 
+def record_citations(ref_root: Path) -> None:
+    """Line counts of the cited reference files and the lines holding each anchor's text."""
+    spec = importlib.util.spec_from_file_location("test_citations",
+                                                  HERE.parent / "test_citations.py")
+    tc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tc)
+    lines = {rel: (ref_root / rel).read_text().splitlines() for rel in tc.REF_FILES.values()}
+    doc = {"line_counts": {rel: len(ls) for rel, ls in sorted(lines.items())},
+           "anchor_lines": {}}
+    for name, _, _, text in tc.ANCHORS:
+        rel = tc.REF_FILES[name]
+        doc["anchor_lines"][f"{rel}::{text}"] = [i for i, ln in enumerate(lines[rel], 1)
+                                                 if text in ln]
+    (HERE / "citations.json").write_text(json.dumps(doc, indent=1, sort_keys=True) + "\n")
+    print("wrote", HERE / "citations.json")
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == "citations":
+        record_citations(Path(sys.argv[2]) if len(sys.argv) > 2 else REF.parents[2])
+    else:
+        main()
+        record_citations(REF.parents[2])

@@ -51,6 +51,37 @@ def test_default_workloads():
     assert args.gpus == 1 and args.levels is None and args.N is None
 
 
+def test_plain_run_is_the_default():
+    """--full (every leg beside the headline) and --dump-outputs are opt-in."""
+    args = bench.parse_args([])
+    assert args.full is False and args.dump_outputs is None
+    args = bench.parse_args(["--full", "--dump-outputs", "d", "--steps", "7"])
+    assert args.full is True and args.dump_outputs == "d" and args.steps == 7
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """Arrays within the budget are written whole in float64; over it, every array keeps the
+    same fixed seeded sample from run to run and the files stay within the budget."""
+    import numpy as np
+
+    a = np.arange(1000, dtype=np.float64) * 0.5
+    b = np.arange(3000, dtype=np.float32)
+    info = bench.dump_outputs(tmp_path / "w", {"a": a, "b": b})
+    got = np.load(tmp_path / "w" / "a.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, a)
+    assert np.array_equal(np.load(tmp_path / "w" / "b.npy"), b.astype(np.float64))
+    assert info["b"] == {"file": "b.npy", "entries": 3000, "written": 3000}
+    budget = 8 * 1000
+    for d in ("s1", "s2"):
+        info = bench.dump_outputs(tmp_path / d, {"a": a, "b": b}, budget, "_rank1")
+    s1 = [np.load(tmp_path / "s1" / f"{k}_rank1.npy") for k in ("a", "b")]
+    s2 = [np.load(tmp_path / "s2" / f"{k}_rank1.npy") for k in ("a", "b")]
+    assert all(np.array_equal(x, y) for x, y in zip(s1, s2))
+    assert sum(x.nbytes for x in s1) <= budget
+    assert info["a"]["written"] == s1[0].size == 250 and s1[1].size == 750
+    assert np.isin(s1[0], a).all() and np.all(np.diff(s1[0]) > 0)
+
+
 def test_direct_kernel_bytes_c3():
     """The residual SpMV of the direct solve reads the CSR, x and b once (SURVEY 8(d) + b)."""
     n, nnz, E, N, B = 1_032_160, 3_571_600, 32_767, 15, 16_383
