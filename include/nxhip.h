@@ -463,6 +463,13 @@ int nx_get_direct_path(nx_network_t* h, int32_t* path);
  * (*sup = 1: the instantiation k_dir_step / k_dir_xr <W, CPL, true>, NXHIP_DIR_SUP; 0: the
  * plain phase 2). Replaces nothing in the reference (its profiling names). */
 int nx_get_direct_sup(nx_network_t* h, int32_t* sup);
+/* The dense top of the fused step (one rank, superposition, the dense lists of
+ * nx_set_pc_dense; NXHIP_DIR_DENSE=0 switches it off per solve): *ran = 1 when the last
+ * k_dir_step formed its top values as rows of G times the posted inputs instead of solving
+ * the top part in one workgroup; *builds = how many times this handle has built G (once per
+ * decomposition and per contents of R: new boundary values or a new source do not rebuild
+ * it). Either pointer may be NULL. Replaces nothing in the reference. */
+int nx_get_direct_dense(nx_network_t* h, int32_t* ran, int32_t* builds);
 /* (path 2: the (k, 0) condensed route of nx_fe_set_direct; path 4: the continuous-pressure
  * node-condensed route of nx_fe_set_cp; path 3: several ranks, the
  * exchange step k_dir_xr / k_dir_xg, one launch per rank.)

@@ -70,6 +70,7 @@ _SIGS = {
     "nx_get_direct_info": (C.c_int, [_h, _pi32, _pi32]),
     "nx_get_direct_path": (C.c_int, [_h, _pi32]),
     "nx_get_direct_sup": (C.c_int, [_h, _pi32]),
+    "nx_get_direct_dense": (C.c_int, [_h, _pi32, _pi32]),
     "nx_debug_set_wait_polls": (C.c_int, [_h, C.c_uint32]),
     "nx_debug_xr_rehearse": (C.c_int, [_h, _f64, _i32, _pd]),
     "nx_reset_profile": (C.c_int, [_h]),
@@ -457,6 +458,14 @@ class Handle:
         v = C.c_int32(0)
         check(lib().nx_get_direct_sup(self.ptr, C.byref(v)))
         return bool(v.value)
+
+    def direct_dense(self) -> dict:
+        """The dense top of the one-launch step (nx_get_direct_dense; DESIGN.md section 3c,
+        round 7): ``ran`` -- the last step formed its top values from G; ``builds`` -- how
+        many times this handle built G."""
+        r, b = C.c_int32(0), C.c_int32(0)
+        check(lib().nx_get_direct_dense(self.ptr, C.byref(r), C.byref(b)))
+        return {"ran": bool(r.value), "builds": int(b.value)}
 
     def direct_path(self) -> str:
         """What the last direct solve ran (nx_get_direct_path): ``"fused"`` (k_dir_step, one

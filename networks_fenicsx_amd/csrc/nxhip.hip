@@ -1071,6 +1071,10 @@ struct PcArgs {
   const int* chain_uib;
   const int* job_root_u;
   const int* job_root_dc;
+  // the dense fused step (k_dir_step): per entry of job_tslot its input position (slot_uy)
+  // and its multiplier row (slot_lam), so a workgroup loads them without a dependent trip
+  const int* own_uy;
+  const int* own_lam;
   double* u;
   // factored coefficients (single rank, once per solve by k_pc_factor; D is fixed by the
   // assembly): kappa = g / D_child per hanging-chain entry (0 when grounded), 1 / D
@@ -3487,7 +3491,20 @@ struct DirStep {
   // phase 2 by superposition (dir_sup_*; NXHIP_DIR_SUP, default 1): bit 0 on, bit 2 the
   // chain records' and lane masses' LDS copies (when they fit)
   int sup;
+  // the dense top (k_dir_step's SUP instantiation): where the workgroup's index lists start in
+  // the dynamic LDS (doubles from its base; kDn*), and the number of posted inputs (pa.u)
+  int dense_off, n_u;
 };
+
+// The dense fused step's index lists in LDS (ints): the chains' input positions (chain_uit /
+// chain_uib), the top slots the job needs, the ones it owns (top position, input position,
+// multiplier row), then top_uoff (n_top + 1)
+constexpr int kDnOwnCap = 256;  // top slots one job owns (more: the top solver runs)
+constexpr int kDnCut = 0, kDnCub = kDnCut + 256, kDnNeed = kDnCub + 256,
+              kDnOwn = kDnNeed + kMaxNeed, kDnUy = kDnOwn + kDnOwnCap, kDnLam = kDnUy + kDnOwnCap,
+              kDnUoff = kDnLam + kDnOwnCap;
+constexpr int kDnGPre = 4;   // G elements a lane prefetches (its wave's first row, 64 apart)
+constexpr int kDnUBatch = 8;  // posted inputs a lane of the polling wave loads per round trip
 
 constexpr int kDirWaitPolls = 1 << 20;  // s_sleep-paced polls before a waiting workgroup gives up
 // LDS of k_dir_step (doubles): the largest of phase 1, the top part and phase 2, then the
@@ -4366,10 +4383,11 @@ __device__ __forceinline__ bool sup_wslots(const JobStash& S) {
   return S.jwave > 0 && S.js1 - S.js0 <= 64 && S.lv1 > S.lv0;
 }
 
-template <int W, int CPL, bool MULTI = false>
+template <int W, int CPL, bool MULTI = false, bool DENSE = false>
 __device__ __forceinline__ void dir_up_v2(const PcArgs& pa, const DirStep& da, double* lds,
                                           const JobStash& S, ChainRec& rec, DirLane<W, CPL>& L,
-                                          double& sA_, double& sB_, double* park = nullptr) {
+                                          double& sA_, double& sB_, double* park = nullptr,
+                                          const int* dn = nullptr, int rootu = -1) {
   double* sT = lds;
   double* sIt = sT + kCapC;
   double* sIb = sIt + kCapC;
@@ -4430,7 +4448,11 @@ __device__ __forceinline__ void dir_up_v2(const PcArgs& pa, const DirStep& da, d
       sT[c - c0] = ch.T;
       sIb[c - c0] = ibe;
       sIt[c - c0] = it;
-      if ((cu >= ts0 && cu < ts1) || (clo >= ts0 && clo < ts1)) {  // the top part reads it
+      if constexpr (DENSE) {  // (one chain pass) the top inputs, pre-weighted: a_s sums them
+        const int ui = dn[kDnCut + seg], ub = dn[kDnCub + seg];
+        if (ui >= 0) st_wt(pa.u + ui, it);
+        if (ub >= 0) st_wt(pa.u + ub, ibe);
+      } else if ((cu >= ts0 && cu < ts1) || (clo >= ts0 && clo < ts1)) {  // the top part reads it
         st_wt(pa.chain_T + c, ch.T);
         st_wt(pa.chain_It + c, it);
         st_wt(pa.chain_Ib + c, ibe);
@@ -4594,7 +4616,14 @@ __device__ __forceinline__ void dir_up_v2(const PcArgs& pa, const DirStep& da, d
     const double J = sJ[sl], iv = sIv[sl];
     sA_ = J * iv;
     sB_ = pcn >= 0 ? iv / sT[pcn - c0] : 0.0;
-    if (j < root1) {
+    if constexpr (DENSE) {
+      // the job's root hangs from a top slot: its parent chain's I_top and its Norton current
+      // through that chain, g J_root / D_root (what the top solver's phase A1 forms)
+      if (sl == 0 && rootu >= 0 && pcn >= 0) {
+        const double g = 1.0 / sT[pcn - c0];
+        st_wt(pa.u + rootu, sIt[pcn - c0] + g * J / sD[0]);
+      }
+    } else if (j < root1) {
       st_wt(pa.slot_D + j, sD[sl]);
       st_wt(pa.slot_J + j, J);
     } else if (MULTI) {
@@ -5458,8 +5487,14 @@ __device__ __forceinline__ bool dir_publish_xr(const PcArgs& pa, const DirStep& 
 // part then ends with this rank's coarse partials, the ranks exchange and sum them
 // (xr_allsum), the top part's solver finishes the coarse forest and the top values, and
 // the publisher exchanges the residual's partials and the cut rows' shares the same way.
-template <int W, int CPL, bool XR, bool SUP>
+// DENSE (one rank, superposition, pa.dense; launch_dstep_wc decides): no workgroup solves the
+// top part. Every workgroup posts its top inputs pre-weighted into pa.u (the MINRES path's
+// layout, direct mode's content), the arrival counter itself is the hand-off, and every
+// workgroup forms the top values it needs as dot products of rows of G = the inverse of the
+// top part's Schur matrix (ensure_top_inverse) with the summed inputs.
+template <int W, int CPL, bool XR, bool SUP, bool DENSE = false>
 __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& da, int job) {
+  static_assert(!DENSE || (SUP && !XR), "the dense top: one rank, superposition");
   extern __shared__ double dsm[];
   __shared__ int sFlag, sTopJob, sIdx;
   int* stash = reinterpret_cast<int*>(dsm);  // the job's statics (fixed offsets)
@@ -5472,11 +5507,51 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
   NX_DSTAMP(0);
   JobStash S;
   ChainRec rec;
+  // DENSE: the job's index lists (kDn*) and its header's dense words: the needed top slots
+  // [dn_n0, + dn_need), the owned ones [dn_o0, + dn_own), the root's input position
+  int* dn = DENSE ? reinterpret_cast<int*>(dsm + da.dense_off) : nullptr;
+  int dn_need = 0, dn_own = 0, dn_rootu = -1;
   {
     StashRegs R;
     job_stash_load<W>(pa, da, job, stash, S, R);
+    int d_ut = -1, d_ub = -1, d_nd = 0, d_ow = 0, d_uy = 0, d_lam = 0, d_u0 = 0, d_u1 = 0;
+    if constexpr (DENSE) {
+      const int4* hd = reinterpret_cast<const int4*>(da.job_hdr + kJobHdr * (int64_t)job);
+      const int4 h3 = hd[3];
+      dn_rootu = hd[2].z - 1;
+      dn_need = h3.y;
+      dn_own = h3.w;
+      const int t = threadIdx.x, nt_ = pa.top_nt;
+      if (t < min(S.c1 - S.c0, G)) {
+        d_ut = pa.chain_uit[S.c0 + t];
+        d_ub = pa.chain_uib[S.c0 + t];
+      }
+      if (t < dn_need) d_nd = pa.job_need[h3.x + t] - pa.top_ts0;
+      if (t < dn_own) {
+        d_ow = pa.job_tslot[h3.z + t] - pa.top_ts0;
+        d_uy = pa.own_uy[h3.z + t];
+        d_lam = pa.own_lam[h3.z + t];
+      }
+      if (t <= nt_) d_u0 = pa.top_uoff[t];
+      if (t + kPcThreads <= nt_) d_u1 = pa.top_uoff[t + kPcThreads];
+    }
     chain_rec_load(da, S.c0 + (int)threadIdx.x / W, S.c0 + (int)threadIdx.x / W < S.c1, rec);
     job_stash_store(S, R, min(S.c1 - S.c0, G));
+    if constexpr (DENSE) {
+      const int t = threadIdx.x, nt_ = pa.top_nt;
+      if (t < G) {
+        dn[kDnCut + t] = d_ut;
+        dn[kDnCub + t] = d_ub;
+      }
+      if (t < dn_need) dn[kDnNeed + t] = d_nd;
+      if (t < dn_own) {
+        dn[kDnOwn + t] = d_ow;
+        dn[kDnUy + t] = d_uy;
+        dn[kDnLam + t] = d_lam;
+      }
+      if (t <= nt_) dn[kDnUoff + t] = d_u0;
+      if (t + kPcThreads <= nt_) dn[kDnUoff + t + kPcThreads] = d_u1;
+    }
   }
   __syncthreads();
   const int c0 = S.c0, c1 = S.c1;
@@ -5516,7 +5591,8 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
   double sA_ = 0.0, sB_ = 0.0;
   const int nt = pa.top_nt, ts0 = pa.top_ts0;
   if (rec_lds) rec_to_lds<W>(rec_lds, c0 + (int)threadIdx.x / W < c1, rec);
-  dir_up_v2<W, CPL>(pa, da, smem, S, rec, L, sA_, sB_, sup ? park : nullptr);
+  dir_up_v2<W, CPL, false, DENSE>(pa, da, smem, S, rec, L, sA_, sB_, sup ? park : nullptr, dn,
+                                  dn_rootu);
   if (lpark) {
 #pragma unroll
     for (int t = 0; t < CPL; ++t) {
@@ -5533,7 +5609,110 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
   bool helper = false;      // (superposition) a helper storing its top solver chain in the tail
   bool defer_free = false;  // a waiting workgroup's free waves store theirs after phase 2
   const bool lane_on = c0 + (int)threadIdx.x / W < c1;
-  if (nt > 0) {  // hand-off 1: the top part's inputs -> the last workgroup -> its values
+  if constexpr (DENSE) {
+    // hand-off 1, all to all (nt > 0): the inputs went out as 8-byte write-through stores
+    // (dir_up_v2 and the owned multiplier rows' -b_lambda = -0 below), every wave drains, one
+    // lane adds the arrival; the store-free wave polls the ARRIVAL COUNTER for this launch's
+    // total, then loads every input write-through and sums a_s in top_uoff order; one wave
+    // per needed row of G forms the value (lane-strided, then wave_sum: a fixed order).
+    static_assert(!DENSE || G <= kDnCub - kDnCut, "the chains' input positions: one per lane group");
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    const int nup = (da.n_u + 1) & ~1, ntp = (nt + 1) & ~1;
+    double* sU = smem;       // the posted inputs (phase 1's arrays are done)
+    double* sAt = sU + nup;  // a_s by top position
+    double* sG = sAt + ntp;  // the prefetched rows of G, row k at k nt
+    const int gcap = da.lds_main - nup - ntp;
+    // needed row k belongs to wave k % 16; the first 16, as far as whole rows fit, wait in LDS
+    // (their first 64 kDnGPre columns): loaded under the posts' drain, written after the barrier
+    const bool grow = wv < dn_need && (wv + 1) * nt <= gcap;
+    double gp[kDnGPre];
+    {
+      const double* __restrict__ g = pa.G + (int64_t)(grow ? dn[kDnNeed + wv] : 0) * nt;
+#pragma unroll
+      for (int i = 0; i < kDnGPre; ++i) {
+        const int col = ln + 64 * i;
+        gp[i] = grow && col < nt ? g[col] : 0.0;
+      }
+    }
+    if ((int)threadIdx.x < dn_own) st_wt(pa.u + dn[kDnUy + threadIdx.x], -0.0);
+    vm_drain();
+    __syncthreads();
+    NX_DSTAMP(1);
+    if (threadIdx.x == 0)
+      __hip_atomic_fetch_add(da.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int i = 0; i < kDnGPre; ++i) {
+      const int col = ln + 64 * i;
+      if (grow && col < nt) sG[wv * nt + col] = gp[i];
+    }
+    dir_sup_slots<W, CPL>(pa, sup_lds, S);
+    if (sup_wslots(S)) dir_sup_core_wave0<W, CPL>(pa, L, lane_on, park);
+    sup_s = true;
+    NX_DSTAMP(20);
+    // own stores in the wait, but not wave 0's (it polls and loads: nothing queued before them)
+    dir_stores_v2<W, CPL, true>(pa, da, job, true, c0, c1, true, L, gF);
+    defer_free = true;
+    NX_DSTAMP(8);
+    if (threadIdx.x < 64) {
+      int ok = 0;
+      if (ln == 0) {
+        const unsigned want = (da.epoch + 1u) * (unsigned)nj;  // (wraps with the counter)
+        for (unsigned k = 0; k < da.polls; ++k) {
+          const unsigned v = __hip_atomic_load(da.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if ((int)(v - want) >= 0) {
+            ok = 1;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(1);
+        }
+        if (!ok)
+          __hip_atomic_fetch_add(da.sync + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      ok = __shfl(ok, 0);
+      if (ok) {
+        NX_DSTAMP(28);
+        for (int b = 0; b < da.n_u; b += 64 * kDnUBatch) {  // kDnUBatch loads in flight per lane
+          double v[kDnUBatch];
+#pragma unroll
+          for (int i = 0; i < kDnUBatch; ++i) {
+            const int q = b + ln + 64 * i;
+            v[i] = q < da.n_u ? ld_wt(pa.u + q) : 0.0;
+          }
+#pragma unroll
+          for (int i = 0; i < kDnUBatch; ++i) {
+            const int q = b + ln + 64 * i;
+            if (q < da.n_u) sU[q] = v[i];
+          }
+        }
+        wave_lds_sync();
+        NX_DSTAMP(29);
+        for (int s = ln; s < nt; s += 64) {
+          double a = 0.0;
+          for (int i = dn[kDnUoff + s]; i < dn[kDnUoff + s + 1]; ++i) a += sU[i];
+          sAt[s] = a;
+        }
+      }
+      if (ln == 0) sFlag = ok ? 1 : -1;
+    }
+    __syncthreads();
+    if (sFlag < 0) return;  // the arrivals never completed (the host sees no published state)
+    NX_DSTAMP(2);
+    for (int k = wv; k < dn_need; k += kPcThreads / 64) {
+      const int t = dn[kDnNeed + k];
+      const bool inl = k == wv && grow;
+      const double* __restrict__ g = pa.G + (int64_t)t * nt;
+      double acc = 0.0;
+      for (int col = ln; col < nt; col += 64)
+        acc += (inl && col < 64 * kDnGPre ? sG[k * nt + col] : g[col]) * sAt[col];
+      acc = wave_sum(acc);
+      if (ln == 0) sTop[t] = acc;
+    }
+    __syncthreads();
+    NX_DSTAMP(30);
+    // the owned top slots' values into x (the top solver's z = da.x)
+    if ((int)threadIdx.x < dn_own && !NX_LEDGER(da, 4))
+      da.x[dn[kDnLam + threadIdx.x]] = sTop[dn[kDnOwn + threadIdx.x]];
+  } else if (nt > 0) {  // hand-off 1: the top part's inputs -> the last workgroup -> its values
     vm_drain();
     __syncthreads();
     NX_DSTAMP(1);
@@ -5778,10 +5957,18 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
   NX_DSTAMP(40);
 }
 
-// SUP: phase 2 by superposition (DirStep::sup; instantiated for CPL <= 2, sup_launch)
+// SUP: phase 2 by superposition (DirStep::sup; instantiated for CPL <= 2, sup_launch) with
+// the dense top (no top solver: the default where the top part fits, dstep_dense_on)
 template <int W, int CPL, bool SUP = false>
 __global__ __launch_bounds__(kPcThreads) void k_dir_step(PcArgs pa, DirStep da) {
-  dir_step_body<W, CPL, false, SUP>(pa, da, blockIdx.x);
+  dir_step_body<W, CPL, false, SUP, SUP>(pa, da, blockIdx.x);
+}
+
+// superposition with the top part solved by the last workgroup to arrive (no top part, a top
+// part past the dense caps, NXHIP_DIR_DENSE=0); its own name: profiles tell the two apart
+template <int W, int CPL>
+__global__ __launch_bounds__(kPcThreads) void k_dir_step_ts(PcArgs pa, DirStep da) {
+  dir_step_body<W, CPL, false, true, false>(pa, da, blockIdx.x);
 }
 
 // one rank of several, one GPU each (RCCL ranks; the exchange over IPC-mapped peer memory)
@@ -7082,6 +7269,15 @@ struct nx_network {
   size_t dstep_lds = 0;  // dynamic LDS bytes per workgroup
   bool dstep_park = false;  // dstep_lds holds the superposition's park (DirStep::sup)
   bool dstep_rec = false;   // and the chain records' copy (sup & 4)
+  // the dense top of the one-launch step (nx_set_pc_dense; ensure_top_inverse): the posted
+  // inputs' count, whether the job headers carry the dense words and every job's lists fit,
+  // this step's decision and the last step's, and G's validity: R's contents are versioned
+  // apart from coef_version (new boundary values or a new source leave G alone)
+  int dense_nu = 0;
+  bool dense_hdr = false, dense_now = false, last_dense = false;
+  std::vector<double> R_host;  // the last R (E entries)
+  int64_t r_version = 0, g_version = -1;
+  int g_builds = 0;
   bool last_sup = false;    // the last one-launch step ran the superposition instantiation
   unsigned* d_tsync = nullptr;  // k_dir_team_up's arrival counter (several ranks; pc_bufs)
   bool need_r = false;     // the last pass kept no residual: a refinement step forms it first
@@ -9508,11 +9704,20 @@ NX_API int nx_set_coefficients(nx_network_t* h, const double* edge_R, double R_c
   if (h->E > 0 && edge_bc == nullptr) return fail(NX_ERR_ARG, "edge_bc is NULL");
   CHECK(set_device(h));
   if (h->E > 0) {
+    std::vector<double> Rc;
+    if (!edge_R) Rc.assign((size_t)h->E, R_const);
+    const double* Rn = edge_R ? edge_R : Rc.data();
+    // R's contents decide the top part's inverse (ensure_top_inverse), not f or the boundary
+    // values: compared bit for bit on the host (E doubles)
+    if (h->R_host.size() != (size_t)h->E ||
+        std::memcmp(h->R_host.data(), Rn, sizeof(double) * h->E) != 0) {
+      h->R_host.assign(Rn, Rn + h->E);
+      h->r_version += 1;
+    }
     if (edge_R) {
       HIPCALL(hipMemcpyAsync(h->edge_R, edge_R, sizeof(double) * h->E, hipMemcpyHostToDevice,
                              h->stream));
     } else {
-      std::vector<double> Rc((size_t)h->E, R_const);
       HIPCALL(hipMemcpyAsync(h->edge_R, Rc.data(), sizeof(double) * h->E, hipMemcpyHostToDevice,
                              h->stream));
       HIPCALL(hipStreamSynchronize(h->stream));
@@ -9875,29 +10080,43 @@ bool dstep_on(const nx_network* h) {
 }
 
 DirStep dir_args(nx_network* h, double rtol);
+void opt_in_lds(const void* fn, int bytes);
 template <int CPL>
 bool sup_launch(const DirStep& da);
+size_t dense_lds_extra(const nx_network* h);
 template <int W, int CPL>
 void launch_dstep_wc(nx_network* h, double rtol, bool prof) {
-  const DirStep da = dir_args(h, rtol);
-  static thread_local std::vector<const void*> opted;  // (the dynamic LDS above 64 KiB, once)
+  DirStep da = dir_args(h, rtol);
   const bool sup = sup_launch<CPL>(da);
   h->last_sup = sup;
-  const void* fn = sup ? reinterpret_cast<const void*>(&k_dir_step<W, CPL, CPL <= 2>)
-                       : reinterpret_cast<const void*>(&k_dir_step<W, CPL>);
-  if (std::find(opted.begin(), opted.end(), fn) == opted.end()) {
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kDirLdsMax);
-    (void)hipGetLastError();
-    opted.push_back(fn);
+  // the dense top (run_dstep decided and made G valid): its index lists come after the rest
+  // of the dynamic LDS
+  const bool dense = sup && h->dense_now;
+  h->last_dense = dense;
+  size_t lds = h->dstep_lds;
+  if (dense) {
+    da.dense_off = (int)(h->dstep_lds / 8);
+    da.n_u = h->dense_nu;
+    lds += dense_lds_extra(h);
   }
-  if (sup)
-    hipExtLaunchKernelGGL((k_dir_step<W, CPL, CPL <= 2>), dim3(h->pc_jobs), dim3(kPcThreads),
-                          h->dstep_lds, h->stream, prof ? h->dev[0] : nullptr,
-                          prof ? h->dev[1] : nullptr, 0, h->pa, da);
-  else
-    hipExtLaunchKernelGGL((k_dir_step<W, CPL>), dim3(h->pc_jobs), dim3(kPcThreads), h->dstep_lds,
-                          h->stream, prof ? h->dev[0] : nullptr, prof ? h->dev[1] : nullptr, 0,
-                          h->pa, da);
+  const hipEvent_t e0 = prof ? h->dev[0] : nullptr, e1 = prof ? h->dev[1] : nullptr;
+  if constexpr (CPL <= 2) {
+    if (dense) {
+      opt_in_lds(reinterpret_cast<const void*>(&k_dir_step<W, CPL, true>), kDirLdsMax);
+      hipExtLaunchKernelGGL((k_dir_step<W, CPL, true>), dim3(h->pc_jobs), dim3(kPcThreads), lds,
+                            h->stream, e0, e1, 0, h->pa, da);
+      return;
+    }
+    if (sup) {
+      opt_in_lds(reinterpret_cast<const void*>(&k_dir_step_ts<W, CPL>), kDirLdsMax);
+      hipExtLaunchKernelGGL((k_dir_step_ts<W, CPL>), dim3(h->pc_jobs), dim3(kPcThreads), lds,
+                            h->stream, e0, e1, 0, h->pa, da);
+      return;
+    }
+  }
+  opt_in_lds(reinterpret_cast<const void*>(&k_dir_step<W, CPL>), kDirLdsMax);
+  hipExtLaunchKernelGGL((k_dir_step<W, CPL>), dim3(h->pc_jobs), dim3(kPcThreads), lds, h->stream,
+                        e0, e1, 0, h->pa, da);
 }
 
 // Several ranks: k_dir_team_up, the assembly + up sweep + top part of one rank (half 0 of
@@ -9933,8 +10152,48 @@ bool dteam_on(const nx_network* h) {
          h->top_nt <= kTopThreads && h->pa.n_top_lvl <= kMaxTopLvl && !h->fe;
 }
 
+// The dense top of the one-launch step: the index lists' LDS after the step's own, and when
+// it runs: superposition's <8, 2> instantiation (N <= 16; the park fits, one chain pass), a top
+// part with the dense lists uploaded (nx_set_pc_dense: every job's needs <= kMaxNeed, owned
+// slots <= kDnOwnCap), the inputs and a_s inside the phases' LDS area, not switched off
+// (NXHIP_DIR_DENSE=0, read per solve: tests switch it).
+size_t dense_lds_extra(const nx_network* h) {
+  return 8 * (size_t)((kDnUoff + h->top_nt + 2) / 2);
+}
+int dir_sup_mode();
+bool dstep_dense_on(const nx_network* h) {
+  const char* e = std::getenv("NXHIP_DIR_DENSE");
+  if (e != nullptr && std::atoi(e) == 0) return false;
+  const int nt = h->top_nt;
+  const int nup = (h->dense_nu + 1) & ~1, ntp = (nt + 1) & ~1;
+  return h->pa.dense && h->dense_hdr && nt > 0 && h->pa.n_top == nt && h->pa.G != nullptr &&
+         h->dstep_variant == 5 /* <8, 2>: the one measured */ && h->dstep_park && !h->dstep_multi &&
+         (dir_sup_mode() & 1) != 0 && nup + ntp <= h->dstep_main &&
+         h->dstep_lds + dense_lds_extra(h) <= (size_t)kDirLdsMax;
+}
+
+// G = the inverse of the top part's Schur matrix, valid for this decomposition and this R
+// before a dense step reads it: the lumped mass (the assembly kernel's dq-only launch, as
+// ensure_dq), the start application's up and top sweeps (chain_T and every slot's eliminated
+// D: what a MINRES solve's start runs), then G's columns (pc_gbuild_column, the arithmetic
+// of the MINRES start's pc_prep_in_block on the same inputs: the same bits whoever asks).
+// Stream-ordered ahead of the step; rebuilt only when R's contents or the decomposition
+// change (r_version / g_version), not for new boundary values or a new source.
+int ensure_top_inverse(nx_network* h) {
+  if (h->g_version == h->r_version) return NX_OK;
+  CHECK(launch_assembly(h, 0, 0, 1));
+  launch_pc<false>(h, h->rhs, h->rhs, h->st, h->st + 1, 1, 0);
+  hipLaunchKernelGGL(k_pc_gbuild, dim3(h->pa.n_top), dim3(64), 0, h->stream, h->pa);
+  HIPCALL(hipGetLastError());
+  h->g_version = h->r_version;
+  h->g_builds += 1;
+  return NX_OK;
+}
+
 // Launch k_dir_step and wait for its published state (the host's sequence advances).
 int run_dstep(nx_network* h, double rtol, bool prof) {
+  h->dense_now = dstep_dense_on(h);
+  if (h->dense_now) CHECK(ensure_top_inverse(h));
   switch (h->dstep_variant) {
     case 0: launch_dstep_wc<16, 1>(h, rtol, prof); break;
     case 1: launch_dstep_wc<16, 2>(h, rtol, prof); break;
@@ -11794,6 +12053,13 @@ NX_API int nx_get_direct_sup(nx_network_t* h, int32_t* sup) {
   return NX_OK;
 }
 
+NX_API int nx_get_direct_dense(nx_network_t* h, int32_t* ran, int32_t* builds) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (ran) *ran = h->last_dense ? 1 : 0;
+  if (builds) *builds = h->g_builds;
+  return NX_OK;
+}
+
 NX_API int nx_debug_set_wait_polls(nx_network_t* h, uint32_t polls) {
   if (!h) return fail(NX_ERR_ARG, "null handle");
   h->dstep_polls = polls;
@@ -12100,6 +12366,8 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
   h->d_tsync = nullptr;
   h->dstep_epoch = 0;
   h->dstep_off = false;
+  h->dense_hdr = false;  // (nx_set_pc_dense writes the new headers' dense words)
+  h->g_version = -1;
   h->need_r = false;
   if (lds && n_jobs > 0) {  // one rank or several (then only owned rows of lower jobs)
     std::vector<int> job_of_chain(n_chains, -1), job_of_slot(n_slots, -1);
@@ -12486,6 +12754,8 @@ NX_API int nx_set_pc_dense(nx_network_t* h, int32_t enable, int32_t n_jobs,
   HIPCALL(hipStreamSynchronize(h->stream));
   CHECK(drop_handle_graphs(h));
   h->pa.dense = 0;
+  h->dense_hdr = false;
+  h->g_version = -1;  // (ensure_top_inverse: a new decomposition's G)
   if (!enable) return NX_OK;
   if (n_jobs != h->pc_jobs) return fail(NX_ERR_ARG, "n_jobs differs from the preconditioner's");
   std::vector<int> top_off(h->pa.n_top_lvl + 1);
@@ -12563,6 +12833,37 @@ NX_API int nx_set_pc_dense(nx_network_t* h, int32_t enable, int32_t n_jobs,
     return fail(NX_ERR_HIP, "dense top upload failed");
   pa.n_top = nt;
   pa.dense = 1;
+  // the dense one-launch step (k_dir_step): per owned top slot its input position and its
+  // multiplier row, and the jobs' dense words in their headers ([10] root input + 1, [12..15]
+  // the needed / owned ranges), when every job's owned slots fit the step's lists
+  h->dense_nu = n_u;
+  if (h->d_job_hdr && h->nranks == 1) {
+    std::vector<int> lam(nt), own_uy(nt), own_lam(nt);
+    HIPCALL(hipMemcpy(lam.data(), pa.slot_lam + ts0, sizeof(int) * nt, hipMemcpyDeviceToHost));
+    bool own_fits = true;
+    for (int i = 0; i < nt; ++i) {
+      own_uy[i] = slot_uy[job_tslot[i] - ts0];
+      own_lam[i] = lam[job_tslot[i] - ts0];
+    }
+    std::vector<int> words((size_t)6 * n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+      int* w = words.data() + (size_t)6 * j;
+      w[0] = job_root_u[j] + 1;
+      w[1] = 0;
+      w[2] = job_need_off[j];
+      w[3] = job_need_off[j + 1] - job_need_off[j];
+      w[4] = job_tslot_off[j];
+      w[5] = job_tslot_off[j + 1] - job_tslot_off[j];
+      if (w[5] > kDnOwnCap) own_fits = false;
+    }
+    pa.own_uy = up(own_uy.data(), nt);
+    pa.own_lam = up(own_lam.data(), nt);
+    if (own_fits && pa.own_uy && pa.own_lam) {
+      HIPCALL(hipMemcpy2D(h->d_job_hdr + 10, sizeof(int) * kJobHdr, words.data(), sizeof(int) * 6,
+                          sizeof(int) * 6, n_jobs, hipMemcpyHostToDevice));
+      h->dense_hdr = true;
+    }
+  }
   return NX_OK;
 }
 
