@@ -357,6 +357,33 @@ int nx_fe_cp_ranks(nx_network_t* h, int64_t n_own_edges, int64_t n_edges_global,
                    const int32_t* gid, int64_t n_nodes, const int32_t* nrowx);
 
 /*
+ * Continuous pressure on a graph with cycles (called after nx_fe_set_cp, whose parents and
+ * levels then describe a BFS spanning forest while its incidences keep every edge;
+ * layout_fe.build_cp_tables(cycles=True)): the n_chords non-tree edges (chord, ascending
+ * edge ids -- global ones on several ranks) and the n_slots distinct real border slots at
+ * their ends (cslot, 2 per slot: node, 0 pressure / 1 multiplier; sorted; the multiplier
+ * only where the node has one). The forest's elimination then inverts the grounded node
+ * system S_g (S minus every chord's two off-diagonal 2 x 2 border blocks; negative definite
+ * like S), and the solve corrects it: S = S_g + U C U^T, x = S_g^-1 (g - U w) with
+ * w = (I + C U^T Z)^-1 C U^T x_g, Z = S_g^-1 U. The n_slots x n_slots capacitance matrix is
+ * built and inverted on the device once per contents of R (new boundary values or a new
+ * source do not rebuild it); per pass the node sweep runs three times (x_g, the corrected
+ * solve, one refinement of it). Several ranks need no
+ * further communication: every rank forms the same matrix from the summed blocks. A
+ * singular capacitance matrix detaches the correction (the solves run MINRES).
+ * NX_ERR_ARG: n_slots above 4096 (2 kMaxCyc), indices out of range, a chord that is a
+ * forest edge. n_chords = 0 clears it. Replaces MUMPS' LU (solver.py:58-65) of these pairs
+ * on the graphs it factorises and the forest solve did not (the reference's own cyclic
+ * graph, tests/test_edge_info.py:8-35).
+ */
+int nx_fe_cp_set_cycles(nx_network_t* h, int32_t n_chords, const int32_t* chord,
+                        int32_t n_slots, const int32_t* cslot);
+/* The chords' correction (nx_fe_cp_set_cycles): *ran = 1 when the last node-condensed solve
+ * applied it; *builds = how many times this handle has built its capacitance matrix. Either
+ * pointer may be NULL. Replaces nothing in the reference. */
+int nx_get_cp_cycles(nx_network_t* h, int32_t* ran, int32_t* builds);
+
+/*
  * Process-wide solve mode. 1 (default): with the preconditioner a solve is ONE HIP graph
  * launch -- start application, per-solve coefficients and the first iterations (also with
  * several ranks, RCCL or group, when beta^2 travels point-to-point) -- whose last k_mr_a

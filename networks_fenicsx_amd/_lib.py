@@ -106,6 +106,8 @@ _SIGS = {
     "nx_fe_cp_ranks": (C.c_int, [_h, _i64, _i64, _pi32, _i64, _pi32]),
     "nx_fe_set_cp": (C.c_int, [_h, _i32, _i32, _i32, _pd, _pi32, _i64, _pi32, _pi32, _i32,
                                _pi32, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32]),
+    "nx_fe_cp_set_cycles": (C.c_int, [_h, _i32, _pi32, _i32, _pi32]),
+    "nx_get_cp_cycles": (C.c_int, [_h, _pi32, _pi32]),
     "nx_get_solver": (C.c_int, [_h, _pi32, _pi32]),
     "nx_set_lean": (C.c_int, [_i32]),
     "nx_group_create": (C.c_int, [_i32, C.POINTER(_h), C.POINTER(_h)]),
@@ -117,6 +119,7 @@ _SIGS = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 MAX_CYCLES = 2048  # kMaxCyc of csrc/nxhip.hip: cycle-closing chains the direct solve corrects
+MAX_CP_SLOTS = 2 * MAX_CYCLES  # nx_fe_cp_set_cycles: border slots at chord ends
 
 
 class NxError(RuntimeError):
@@ -608,6 +611,27 @@ class Handle:
         check(lib().nx_fe_cp_ranks(self.ptr, int(n_own_edges), int(n_edges_global),
                                    _ptr(gid if gid.size else np.zeros(1, np.int32), C.c_int32),
                                    int(nrowx.size // 2), _ptr(nrowx, C.c_int32)))
+
+    def fe_cp_set_cycles(self, tab) -> None:
+        """``nx_fe_cp_set_cycles`` (after :meth:`fe_set_cp`): the chords of the tables' node
+        forest and the border slots at their ends (``tab.chord`` / ``tab.cslot``,
+        ``layout_fe.build_cp_tables(cycles=True)``); ``None`` or no chords clears it."""
+        chord = np.zeros(0, np.int32) if tab is None else np.ascontiguousarray(
+            tab.chord, dtype=np.int32).ravel()
+        cslot = np.zeros(0, np.int32) if tab is None else np.ascontiguousarray(
+            tab.cslot, dtype=np.int32).ravel()
+        keep = [a if a.size else np.zeros(2, np.int32) for a in (chord, cslot)]
+        self._cp_cyc_keep = keep
+        check(lib().nx_fe_cp_set_cycles(self.ptr, int(chord.size), _ptr(keep[0], C.c_int32),
+                                        int(cslot.size // 2), _ptr(keep[1], C.c_int32)))
+
+    def cp_cycles(self) -> dict:
+        """The chords' correction of the node-condensed solve (nx_get_cp_cycles): ``ran`` --
+        the last solve applied it; ``builds`` -- how many times this handle built its
+        capacitance matrix (once per contents of R)."""
+        r, b = C.c_int32(0), C.c_int32(0)
+        check(lib().nx_get_cp_cycles(self.ptr, C.byref(r), C.byref(b)))
+        return {"ran": bool(r.value), "builds": int(b.value)}
 
     def set_pc_exact(self, enable: bool) -> None:
         """Consistent (exact Schur complement, default) or lumped flux mass in P."""

@@ -266,11 +266,18 @@ class HydraulicNetworkAssembler:
         pressure_degree: 0 for DG0 pressure (default), m >= 1 for continuous P_m (needs
             k > m); other pairs than (1, 0) run without the tree preconditioner, on one or
             several ranks, with their direct solves on forests
+        cycle_direct: continuous pressure (``pressure_degree >= 1``) on a graph with
+            cycles: the node-condensed direct solve with the chords' low-rank correction
+            (``nx_fe_cp_set_cycles``) instead of MINRES. ``None`` (default) reads the
+            environment variable ``NXHIP_CP_CYCLES`` (``"1"`` on; off when unset)
     """
 
     @timed("nxfx:HydraulicNetworkAssembler:__init__")
-    def __init__(self, mesh: NetworkMesh, flux_degree: int = 1, pressure_degree: int = 0):
+    def __init__(self, mesh: NetworkMesh, flux_degree: int = 1, pressure_degree: int = 0, *,
+                 cycle_direct: bool | None = None):
         self._network_mesh = mesh
+        self._cycle_direct = (os.environ.get("NXHIP_CP_CYCLES", "0") == "1"
+                              if cycle_direct is None else bool(cycle_direct))
         comm = mesh.comm
         self._rank, self._nranks = comm.rank, comm.size
         self._degrees = (int(flux_degree), int(pressure_degree))
@@ -377,7 +384,16 @@ class HydraulicNetworkAssembler:
             # continuous pressure on a forest: the direct solve by condensation onto the graph
             # nodes (nx_fe_set_cp; several ranks: every rank's border blocks summed, the node
             # forest solved on every rank, nx_fe_cp_ranks); a graph with cycles runs MINRES
-            tab = build_cp_tables(full if ranks else fe, src, dst)
+            # (cycle_direct / NXHIP_CP_CYCLES=1: its non-tree edges become chords, the solve
+            # corrected by their capacitance matrix, nx_fe_cp_set_cycles)
+            tab = build_cp_tables(full if ranks else fe, src, dst, cycles=self._cycle_direct)
+            n_chords = 0 if tab is None else int(np.asarray(tab.chord).size)
+            if n_chords and np.asarray(tab.cslot).size // 2 > _lib.MAX_CP_SLOTS:
+                # (every rank sees the same global tables: the same decision)
+                logging.warning("continuous pressure: %d chords (%d border slots at their "
+                                "ends, at most %d); the solve runs MINRES", n_chords,
+                                np.asarray(tab.cslot).size // 2, _lib.MAX_CP_SLOTS)
+                tab = None
             if tab is not None and ranks:
                 # the ranks attach it together or not at all: a rank whose tables or
                 # allocation fail would otherwise leave the others in fe_cp_solve's
@@ -387,6 +403,8 @@ class HydraulicNetworkAssembler:
                     tab, gid, nrowx = build_cp_rank_tables(tab, fe)
                     self._handle.fe_cp_ranks(fe.n_own_edges, mesh.num_edges, gid, nrowx)
                     self._handle.fe_set_cp(tab)
+                    if n_chords:
+                        self._handle.fe_cp_set_cycles(tab)
                 except (_lib.NxError, ValueError, AssertionError, IndexError) as err:
                     logging.error("rank %d: the continuous-pressure direct solve could not be "
                                   "attached (%s); every rank runs MINRES", self._rank, err)
@@ -398,6 +416,15 @@ class HydraulicNetworkAssembler:
             elif tab is not None:
                 self._handle.fe_set_cp(tab)
                 self._fe_cp = tab
+                if n_chords:
+                    try:
+                        self._handle.fe_cp_set_cycles(tab)
+                    except _lib.NxError as err:
+                        logging.warning("continuous pressure: the correction of the graph's %d "
+                                        "chords could not be attached (%s); the solve runs "
+                                        "MINRES", n_chords, err)
+                        self._handle.fe_set_cp(None)
+                        self._fe_cp = None
 
     def _init_fe_direct(self, src, dst) -> None:
         """(k, 0): the direct solve through the condensed P1/DG0 system (``nx_fe_set_direct``).
@@ -471,7 +498,7 @@ class HydraulicNetworkAssembler:
     def fe_direct_available(self) -> bool:
         """A general-degree assembler with a direct solve: (k, 0) through the condensed P1/DG0
         system, continuous pressure (k > m >= 1) by condensation onto the graph nodes (forest
-        graphs)."""
+        graphs; graphs with cycles with ``cycle_direct``)."""
         return (getattr(self, "_fe_aux", None) is not None
                 or getattr(self, "_fe_cp", None) is not None)
 

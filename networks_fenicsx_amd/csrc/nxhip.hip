@@ -7385,6 +7385,24 @@ struct nx_network {
   int* cp_rec = nullptr;  // the node records (CpTree::rec)
   double* cp_ctr = nullptr;  // the nodes' Schur terms for their parents (CpTree::ctr)
   std::vector<int> cp_gid_host, cp_nrowx_host;
+  // a graph with cycles (nx_fe_cp_set_cycles): the chords' correction of the forest's solve.
+  // cpc_ns slots (0: none); their tables; U^T Z, then the capacitance matrix's inverse
+  // (cpc_inv, ns^2); the Gauss-Jordan array and its status word (cpc_gj, 2 ns^2 + 1); the
+  // column batch's scratch (cpc_scr, 2 cp_nn cpc_batch); w; the second sweep's node rhs
+  // (cpc_nb2, 2 cp_nn) with its row table and records (one rank: cpc_nrow2 / cpc_rec2, the
+  // 2 n, 2 n + 1 indexing several ranks already have in cp_nrow / cp_rec)
+  int cpc_ns = 0, cpc_batch = 0;
+  int *cpc_slot = nullptr, *cpc_ent_off = nullptr, *cpc_ent = nullptr, *cpc_slot_of = nullptr;
+  int *cpc_nrow2 = nullptr, *cpc_rec2 = nullptr;
+  double *cpc_inv = nullptr, *cpc_gj = nullptr, *cpc_scr = nullptr, *cpc_w = nullptr;
+  double* cpc_nb2 = nullptr;
+  // the grounded sweep's one refinement: the blocks with a zero ge (20 per edge), the node
+  // residual and the sweep's values (2 cp_nn each)
+  double *cpc_se0 = nullptr, *cpc_rho = nullptr, *cpc_xd = nullptr;
+  int64_t cpc_version = -1;  // R's version its capacitance matrix was built for (fe_cp_solve)
+  bool cpc_failed = false;   // a singular capacitance matrix: the solves run MINRES
+  int cpc_builds = 0;
+  bool cpc_last = false;  // the last fe_cp_solve applied the correction
 };
 
 struct nx_group {
@@ -9315,6 +9333,234 @@ __global__ __launch_bounds__(256) void k_cp_nb(const int* __restrict__ nrowx, in
   if (r >= 0) nb[i] = b[r];
 }
 
+// ---- continuous pressure on a graph with cycles (nx_fe_cp_set_cycles). The non-tree edges
+// of the node forest are chords: the forest's elimination (k_cp_nodes*) sums every edge's
+// diagonal blocks into its end nodes and couples a node only to its parent, so on such a
+// graph it inverts the grounded system S_g = S minus the chords' two off-diagonal 2 x 2
+// blocks. With U the unit columns of the ns distinct real border slots at chord ends and
+// C = U^T (S - S_g) U (the dropped blocks), S = S_g + U C U^T and
+//   x = S_g^-1 (g - U w),   w = (I + C U^T Z)^-1 C U^T x_g,   x_g = S_g^-1 g,  Z = S_g^-1 U
+// (this form: C need not be invertible). Per coefficient version (cpc_build): U^T Z by
+// rhs-only sweeps of the stored pivots, many columns at once, I + C U^T Z, its inverse by
+// k_gj_*. Per pass: w from the first sweep's x_g, then the forest's sweep again on g - U w,
+// and one refinement of that grounded solve (its node residual swept and added).
+struct CpCyc {
+  int ns;                // slots
+  const int* slot;       // per slot: 2 node + (0 pressure, 1 multiplier)
+  const int* ent_off;    // ns + 1: per slot's node, its chord ends
+  const int* ent;        // 4 per entry: chord edge, the node's end of it, the other end's
+                         // pressure slot, its multiplier slot (-1: none)
+};
+
+// Z's columns [j0, j0 + gridDim.x): one workgroup per column, the levels in order with a
+// barrier each, the level's nodes over the threads. Up: h_n = g_n - sum_children B_c^T P_c^-1
+// h_c (the children in list order, the expressions of cp_up_child_v's rhs part); down, in
+// place: x_n = P_n^-1 (h_n - B_n x_parent) (cp_node_down's). No atomics; only U^T Z is kept
+// (utz[i ns + j] = Z[slot_i, j]). scr: 2 nn doubles per column of the batch.
+__global__ __launch_bounds__(256) void k_cp_zcols(const double* __restrict__ se, CpTree t,
+                                                  CpCyc c, int j0, double* __restrict__ scr,
+                                                  double* __restrict__ utz) {
+#pragma clang fp contract(off)
+  const int j = j0 + (int)blockIdx.x;
+  if (j >= c.ns) return;
+  double* v = scr + (int64_t)blockIdx.x * 2 * t.nn;
+  for (int i = threadIdx.x; i < 2 * t.nn; i += 256) v[i] = 0.0;
+  __syncthreads();
+  if (threadIdx.x == 0) v[c.slot[j]] = 1.0;
+  __syncthreads();
+  for (int L = t.nlev - 1; L >= 0; --L) {
+    for (int i = t.lev_off[L] + threadIdx.x; i < t.lev_off[L + 1]; i += 256) {
+      const int n = t.order[i];
+      double g0 = v[2 * n], g1 = v[2 * n + 1];
+      for (int q = t.child_off[n]; q < t.child_off[n + 1]; ++q) {
+        const int ch = t.child[q];
+        const double h0 = v[2 * ch], h1 = v[2 * ch + 1];
+        if (h0 == 0.0 && h1 == 0.0) continue;  // (a unit column: zero off its node's path)
+        const int cend = t.parent[3 * ch + 2];
+        double B[4];
+        cp_block(se, t.parent[3 * ch + 1], cend, 1 - cend, B);
+        const double* Pc = t.Pinv + 4 * (int64_t)ch;
+        const double z0 = Pc[0] * h0 + Pc[1] * h1, z1 = Pc[2] * h0 + Pc[3] * h1;
+        g0 -= B[0] * z0 + B[2] * z1;
+        g1 -= B[1] * z0 + B[3] * z1;
+      }
+      v[2 * n] = g0;
+      v[2 * n + 1] = g1;
+    }
+    __syncthreads();
+  }
+  for (int L = 0; L < t.nlev; ++L) {
+    for (int i = t.lev_off[L] + threadIdx.x; i < t.lev_off[L + 1]; i += 256) {
+      const int n = t.order[i];
+      const int p = t.parent[3 * n];
+      double r0 = v[2 * n], r1 = v[2 * n + 1];
+      if (p >= 0) {
+        const int pend = t.parent[3 * n + 2];
+        double B[4];
+        cp_block(se, t.parent[3 * n + 1], pend, 1 - pend, B);
+        const double x0 = v[2 * p], x1 = v[2 * p + 1];
+        r0 -= B[0] * x0 + B[1] * x1;
+        r1 -= B[2] * x0 + B[3] * x1;
+      }
+      const double* Pn = t.Pinv + 4 * (int64_t)n;
+      v[2 * n] = Pn[0] * r0 + Pn[1] * r1;
+      v[2 * n + 1] = Pn[2] * r0 + Pn[3] * r1;
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < c.ns; i += 256) utz[(int64_t)i * c.ns + j] = v[c.slot[i]];
+}
+
+// the coupling of slot i (its node's end `end` of chord e, row s) to the other end's slots
+__device__ __forceinline__ void cp_cyc_coef(const double* se, const int* en, int s, double* cp,
+                                            double* cl) {
+  const double* S = se + 20 * (int64_t)en[0] + 4 * (2 * en[1] + s) + 2 * (1 - en[1]);
+  *cp = S[0];
+  *cl = S[1];
+}
+
+// [I + C U^T Z | I] into the Gauss-Jordan array (ns x 2 ns, row-major), grid-strided: an
+// entry sums its row slot's chord ends in list order (ascending chord, then end).
+__global__ __launch_bounds__(256) void k_cp_cap(const double* __restrict__ se, CpCyc c,
+                                                const double* __restrict__ utz,
+                                                double* __restrict__ aug) {
+#pragma clang fp contract(off)
+  const int ns = c.ns;
+  const int64_t n = (int64_t)ns * 2 * ns;
+  for (int64_t q = blockIdx.x * (int64_t)256 + threadIdx.x; q < n; q += (int64_t)gridDim.x * 256) {
+    const int r = (int)(q / (2 * ns)), col = (int)(q % (2 * ns));
+    double v;
+    if (col < ns) {
+      v = r == col ? 1.0 : 0.0;
+      const int s = c.slot[r] & 1;
+      for (int k = c.ent_off[r]; k < c.ent_off[r + 1]; ++k) {
+        const int* en = c.ent + 4 * k;
+        double cp, cl;
+        cp_cyc_coef(se, en, s, &cp, &cl);
+        v += cp * utz[(int64_t)en[2] * ns + col];
+        if (en[3] >= 0) v += cl * utz[(int64_t)en[3] * ns + col];
+      }
+    } else {
+      v = col - ns == r ? 1.0 : 0.0;
+    }
+    aug[q] = v;
+  }
+}
+
+// w = Cap^-1 (C U^T x_g): every workgroup forms t = C U^T x_g in LDS (ns doubles; xn the
+// first sweep's node values), then 64 rows of w per workgroup, a row's sum in 16 column
+// parts (stride 16) joined in part order. capT[j ns + i] = Cap^-1[i][j] (k_gj_out).
+__global__ __launch_bounds__(1024) void k_cp_cyc_w(const double* __restrict__ se, CpCyc c,
+                                                   const double* __restrict__ xn,
+                                                   const double* __restrict__ capT,
+                                                   double* __restrict__ w) {
+#pragma clang fp contract(off)
+  extern __shared__ double cw_t[];  // ns, then 16 x 64 partial sums
+  const int ns = c.ns;
+  double* part = cw_t + ns;
+  for (int r = threadIdx.x; r < ns; r += 1024) {
+    const int s = c.slot[r] & 1;
+    double v = 0.0;
+    for (int k = c.ent_off[r]; k < c.ent_off[r + 1]; ++k) {
+      const int* en = c.ent + 4 * k;
+      double cp, cl;
+      cp_cyc_coef(se, en, s, &cp, &cl);
+      const int on = c.slot[en[2]] >> 1;  // the other end's node
+      v += cp * xn[2 * on];
+      if (en[3] >= 0) v += cl * xn[2 * on + 1];
+    }
+    cw_t[r] = v;
+  }
+  __syncthreads();
+  const int li = threadIdx.x & 63, pq = threadIdx.x >> 6;
+  const int i = (int)blockIdx.x * 64 + li;
+  double s = 0.0;
+  if (i < ns)
+    for (int j = pq; j < ns; j += 16) s += capT[(int64_t)j * ns + i] * cw_t[j];
+  part[pq * 64 + li] = s;
+  __syncthreads();
+  if (pq == 0 && i < ns) {
+    double o = part[li];
+    for (int q = 1; q < 16; ++q) o += part[q * 64 + li];
+    w[i] = o;
+  }
+}
+
+// The border blocks of every edge with a zero ge (se0: the refinement sweep's rhs is the
+// node residual alone), once per capacitance build.
+__global__ __launch_bounds__(256) void k_cp_cyc_se0(const double* __restrict__ se, int64_t n20,
+                                                    double* __restrict__ se0) {
+  for (int64_t q = blockIdx.x * (int64_t)256 + threadIdx.x; q < n20; q += (int64_t)gridDim.x * 256)
+    se0[q] = q % 20 < 16 ? se[q] : 0.0;
+}
+
+// The grounded system's node residual of the second sweep's x (one node per thread):
+// rho_n = g_n - D_n x_n - B_n x_parent - sum_children B_c^T x_c, with g_n = nb2 (the node rows
+// of b minus U w) plus the node's edges' ge and D_n their diagonal blocks (list order). The
+// forest's 2 x 2 pivots are applied as explicit inverses, which costs the one-sweep residual
+// up to two digits on short stiff edges; one sweep of rho (k_cp_cyc_add) takes them back.
+__global__ __launch_bounds__(256) void k_cp_cyc_res(const double* __restrict__ se, CpTree t,
+                                                    const int* __restrict__ nrow,
+                                                    const double* __restrict__ nb2,
+                                                    const double* __restrict__ xn,
+                                                    double* __restrict__ rho) {
+#pragma clang fp contract(off)
+  const int n = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (n >= t.nn) return;
+  double g0 = nb2[2 * n], g1 = nb2[2 * n + 1];
+  double D[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int j = t.inc_off[n]; j < t.inc_off[n + 1]; ++j) {
+    const int e = t.inc[2 * j], end = t.inc[2 * j + 1];
+    double B[4];
+    cp_block(se, e, end, end, B);
+    for (int q = 0; q < 4; ++q) D[q] += B[q];
+    g0 += se[20 * (int64_t)e + 16 + 2 * end];
+    g1 += se[20 * (int64_t)e + 17 + 2 * end];
+  }
+  const double x0 = xn[2 * n], x1 = xn[2 * n + 1];
+  g0 -= D[0] * x0 + D[1] * x1;
+  g1 -= D[2] * x0 + D[3] * x1;
+  const int p = t.parent[3 * n];
+  if (p >= 0) {
+    const int pend = t.parent[3 * n + 2];
+    double B[4];
+    cp_block(se, t.parent[3 * n + 1], pend, 1 - pend, B);
+    g0 -= B[0] * xn[2 * p] + B[1] * xn[2 * p + 1];
+    g1 -= B[2] * xn[2 * p] + B[3] * xn[2 * p + 1];
+  }
+  for (int q = t.child_off[n]; q < t.child_off[n + 1]; ++q) {
+    const int c = t.child[q], cend = t.parent[3 * c + 2];
+    double B[4];  // child rows x this node's columns
+    cp_block(se, t.parent[3 * c + 1], cend, 1 - cend, B);
+    g0 -= B[0] * xn[2 * c] + B[2] * xn[2 * c + 1];
+    g1 -= B[1] * xn[2 * c] + B[3] * xn[2 * c + 1];
+  }
+  rho[2 * n] = g0;
+  rho[2 * n + 1] = nrow[2 * n + 1] >= 0 ? g1 : 0.0;  // (no multiplier: the dummy stays 0)
+}
+
+// x_n += d_n (the refinement sweep's values)
+__global__ __launch_bounds__(256) void k_cp_cyc_add(double* __restrict__ xn,
+                                                    const double* __restrict__ xd, int n2) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < n2) xn[i] += xd[i];
+}
+
+// The second sweep's node rhs (2 per node: 2 n, 2 n + 1): the node rows of b (src[nrow];
+// one rank: b itself, several: the summed node rhs) minus U w. The edges' ge stay in se.
+__global__ __launch_bounds__(256) void k_cp_cyc_rhs(const int* __restrict__ nrow, int nn,
+                                                    const double* __restrict__ src,
+                                                    const int* __restrict__ slot_of,
+                                                    const double* __restrict__ w,
+                                                    double* __restrict__ nb2) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= 2 * nn) return;
+  const int r = nrow[i], j = slot_of[i];
+  double v = r >= 0 ? src[r] : 0.0;
+  if (j >= 0) v -= w[j];
+  nb2[i] = v;
+}
+
 // The edge templates (FeTpl) of a layout with `per` rows per edge: each shape's entries and
 // rhs terms from its first edge's gather-table terms, every other edge's checked against its
 // shape (row lengths, local / outside columns, terms); false (the gather kernels stay) on any
@@ -9660,6 +9906,9 @@ NX_API int nx_destroy(nx_network_t* h) {
                   h->cp_eb, h->cp_nrow, h->cp_lev_off, h->cp_order, h->cp_inc_off, h->cp_inc,
                   h->cp_parent, h->cp_child_off, h->cp_child, h->cp_nown, h->cp_gid,
                   h->cp_nrowx, h->cp_rec, h->cp_rng, h->fe_tpl_buf,
+                  h->cpc_slot, h->cpc_ent_off, h->cpc_ent, h->cpc_slot_of, h->cpc_nrow2,
+                  h->cpc_rec2, h->cpc_inv, h->cpc_gj, h->cpc_scr, h->cpc_w, h->cpc_nb2,
+                  h->cpc_se0, h->cpc_rho, h->cpc_xd,
                   h->fe_tpl_rbuf, h->fe_tpl_rs, h->fe_tpl_shape, h->fe_tpl_lam};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
@@ -10231,6 +10480,22 @@ int launch_direct(nx_network* h, double rtol, int refine, bool prof = false) {
 // device: Gauss-Jordan with partial pivoting (k_gj_*), 2 m launches on the handle's stream,
 // stored transposed for the correction's kernels; the same on every rank of a team (the same
 // summed inputs, the same operations). One host sync: a zero coupling or pivot fails loudly.
+// The Gauss-Jordan loop on a filled [A | I] (aug, m x 2 m; bad: its status word, cleared by
+// the caller before the fill): the inverse, transposed, into outT; *status the word after
+// (one host sync). The partial pivoting serves nonsymmetric matrices too.
+int gj_invert(hipStream_t stream, double* aug, int m, int* bad, double* outT, int* status) {
+  for (int col = 0; col < m; ++col) {
+    hipLaunchKernelGGL(k_gj_pivot, dim3(1), dim3(1024), 0, stream, aug, m, col, bad);
+    hipLaunchKernelGGL(k_gj_elim, dim3(m), dim3(256), 0, stream, aug, m, col);
+  }
+  hipLaunchKernelGGL(k_gj_out, dim3(std::min(4096, grid_of((int64_t)m * m, 256))), dim3(256), 0,
+                     stream, aug, m, outT);
+  HIPCALL(hipGetLastError());
+  HIPCALL(hipMemcpyAsync(status, bad, sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIPCALL(hipStreamSynchronize(stream));
+  return NX_OK;
+}
+
 int cyc_invert(nx_network* h) {
   const int m = 2 * h->n_cyc;
   if (!h->cyc_gj) HIPCALL(hipMalloc((void**)&h->cyc_gj, sizeof(double) * 2 * (size_t)m * m + 8));
@@ -10238,16 +10503,8 @@ int cyc_invert(nx_network* h) {
   HIPCALL(hipMemsetAsync(bad, 0, sizeof(int), h->stream));
   const int gb = std::min(4096, grid_of(2 * (int64_t)m * m, 256));
   hipLaunchKernelGGL(k_gj_init, dim3(gb), dim3(256), 0, h->stream, h->cyc_cap, m, h->cyc_gj, bad);
-  for (int col = 0; col < m; ++col) {
-    hipLaunchKernelGGL(k_gj_pivot, dim3(1), dim3(1024), 0, h->stream, h->cyc_gj, m, col, bad);
-    hipLaunchKernelGGL(k_gj_elim, dim3(m), dim3(256), 0, h->stream, h->cyc_gj, m, col);
-  }
-  hipLaunchKernelGGL(k_gj_out, dim3(std::min(4096, grid_of((int64_t)m * m, 256))), dim3(256), 0,
-                     h->stream, h->cyc_gj, m, h->cyc_cinv);
-  HIPCALL(hipGetLastError());
   int b = 0;
-  HIPCALL(hipMemcpyAsync(&b, bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCALL(hipStreamSynchronize(h->stream));
+  CHECK(gj_invert(h->stream, h->cyc_gj, m, bad, h->cyc_cinv, &b));
   if (b == 1) return fail(NX_ERR_STATE, "cycle chain: no coupling at its grounded end");
   if (b == 2) return fail(NX_ERR_STATE, "cycle correction is singular");
   return NX_OK;
@@ -11567,8 +11824,42 @@ void cp_nodes_launch(nx_network* h, const CpArgs& a, const CpTree& tr, const dou
   }
 }
 
+// A graph with cycles: the capacitance matrix of the chords' correction, once per version
+// of R (the caller's), after k_cp_edge (Se) and one factoring node sweep (the pivots) of this version:
+// U^T Z in column batches (k_cp_zcols), I + C U^T Z (k_cp_cap), its inverse (gj_invert) into
+// cpc_inv. *ok = 0: singular (the caller detaches the correction). Every rank of a team forms
+// the same matrix from the same summed blocks: no communication.
+int cpc_build(nx_network* h, const CpTree& tr, int64_t version, int* ok) {
+  const int ns = h->cpc_ns;
+  const CpCyc c{ns, h->cpc_slot, h->cpc_ent_off, h->cpc_ent};
+  for (int j0 = 0; j0 < ns; j0 += h->cpc_batch)
+    hipLaunchKernelGGL(k_cp_zcols, dim3(std::min(h->cpc_batch, ns - j0)), dim3(256), 0, h->stream,
+                       h->cp_se, tr, c, j0, h->cpc_scr, h->cpc_inv);
+  const int64_t n20 = 20 * (h->cp_Eg > 0 ? h->cp_Eg : h->E);
+  hipLaunchKernelGGL(k_cp_cyc_se0, dim3(std::max(1, std::min(4096, grid_of(n20, 256)))), dim3(256),
+                     0, h->stream, h->cp_se, n20, h->cpc_se0);
+  int* bad = reinterpret_cast<int*>(h->cpc_gj + 2 * (size_t)ns * ns);
+  HIPCALL(hipMemsetAsync(bad, 0, sizeof(int), h->stream));
+  hipLaunchKernelGGL(k_cp_cap, dim3(std::min(4096, grid_of(2 * (int64_t)ns * ns, 256))), dim3(256),
+                     0, h->stream, h->cp_se, c, h->cpc_inv, h->cpc_gj);
+  int b = 0;
+  CHECK(gj_invert(h->stream, h->cpc_gj, ns, bad, h->cpc_inv, &b));
+  *ok = b == 0 ? 1 : 0;
+  if (b == 0) {
+    h->cpc_version = version;
+    h->cpc_builds += 1;
+  }
+  return NX_OK;
+}
+
 int fe_cp_solve(nx_network* h, double rtol, int32_t* iters, double* relres, int32_t* converged) {
   CHECK(flush_assembly(h));
+  h->cpc_last = false;
+  if (h->cpc_failed) {  // (a singular capacitance matrix before: MINRES)
+    if (iters) *iters = 0;
+    if (converged) *converged = 0;
+    return NX_OK;
+  }
   // several ranks: the edge kernels over this rank's edges (se by global edge), the node
   // kernels over the summed blocks and node rhs (an: nrow indexes nb), the rows it owns
   const bool ranks = h->cp_Eg > 0;
@@ -11609,6 +11900,47 @@ int fe_cp_solve(nx_network* h, double rtol, int32_t* iters, double* relres, int3
       CHECK(team_allreduce(t, -5, (int)nsum));
     }
     cp_nodes_launch(h, ranks ? an : a, tr, ranks ? nb : b);
+    if (h->cpc_ns > 0) {  // a graph with cycles: cp_xn holds x_g; the sweep again on g - U w
+      // (Se depends on R and the geometry alone: one rank follows R's contents, r_version
+      // -- new boundary values or a new source rebuild nothing; several ranks see only their
+      // own edges' R, so they follow the coefficient calls they make together, lhs_version)
+      const int64_t cver = ranks ? h->lhs_version : h->r_version;
+      if (h->cpc_version != cver) {
+        int ok = 0;
+        CHECK(cpc_build(h, tr, cver, &ok));
+        if (!ok) {
+          h->cpc_failed = true;
+          if (iters) *iters = 0;
+          if (converged) *converged = 0;
+          return NX_OK;
+        }
+      }
+      const int ns = h->cpc_ns;
+      const CpCyc c{ns, h->cpc_slot, h->cpc_ent_off, h->cpc_ent};
+      hipLaunchKernelGGL(k_cp_cyc_w, dim3(grid_of(ns, 64)), dim3(1024),
+                         sizeof(double) * ((size_t)ns + 1024), h->stream, h->cp_se, c, h->cp_xn,
+                         h->cpc_inv, h->cpc_w);
+      hipLaunchKernelGGL(k_cp_cyc_rhs, dim3(grid_of(2 * (int64_t)h->cp_nn, 256)), dim3(256), 0,
+                         h->stream, h->cp_nrow, h->cp_nn, ranks ? nb : b, h->cpc_slot_of,
+                         h->cpc_w, h->cpc_nb2);
+      CpArgs a2 = an;
+      CpTree tr2 = tr;
+      if (!ranks) {
+        a2.nrow = h->cpc_nrow2;
+        tr2.rec = h->cp_rec ? h->cpc_rec2 : nullptr;
+      }
+      cp_nodes_launch(h, a2, tr2, h->cpc_nb2);
+      // one refinement of the grounded solve: its node residual, swept (zero ge), added
+      hipLaunchKernelGGL(k_cp_cyc_res, dim3(grid_of(h->cp_nn, 256)), dim3(256), 0, h->stream,
+                         h->cp_se, tr, h->cp_nrow, h->cpc_nb2, h->cp_xn, h->cpc_rho);
+      CpArgs a3 = a2;
+      a3.se = h->cpc_se0;
+      a3.xn = h->cpc_xd;
+      cp_nodes_launch(h, a3, tr2, h->cpc_rho);
+      hipLaunchKernelGGL(k_cp_cyc_add, dim3(grid_of(2 * (int64_t)h->cp_nn, 256)), dim3(256), 0,
+                         h->stream, h->cp_xn, h->cpc_xd, 2 * h->cp_nn);
+      h->cpc_last = true;
+    }
     hipLaunchKernelGGL(k_cp_back, dim3(eb), dim3(64), xs_lds, h->stream, a, b, h->x, h->cp_nown,
                        pass ? 1 : 0, xs_lds > 0 ? 1 : 0);
     if (ranks)
@@ -13001,6 +13333,159 @@ NX_API int nx_fe_cp_ranks(nx_network_t* h, int64_t n_own_edges, int64_t n_edges_
   return NX_OK;
 }
 
+// the chords' correction off the handle (nx_fe_cp_set_cycles with none, nx_fe_set_cp)
+static int cpc_clear(nx_network* h) {
+  for (int** p : {&h->cpc_slot, &h->cpc_ent_off, &h->cpc_ent, &h->cpc_slot_of, &h->cpc_nrow2,
+                  &h->cpc_rec2}) {
+    if (*p) HIPCALL(hipFree(*p));
+    *p = nullptr;
+  }
+  for (double** p : {&h->cpc_inv, &h->cpc_gj, &h->cpc_scr, &h->cpc_w, &h->cpc_nb2, &h->cpc_se0,
+                     &h->cpc_rho, &h->cpc_xd}) {
+    if (*p) HIPCALL(hipFree(*p));
+    *p = nullptr;
+  }
+  h->cpc_ns = h->cpc_batch = 0;
+  h->cpc_version = -1;
+  h->cpc_failed = false;
+  h->cpc_last = false;
+  return NX_OK;
+}
+
+template <class T>
+static int download(std::vector<T>& v, const T* dev, int64_t count) {
+  v.resize((size_t)std::max<int64_t>(0, count));
+  if (count > 0) HIPCALL(hipMemcpy(v.data(), dev, sizeof(T) * (size_t)count, hipMemcpyDeviceToHost));
+  return NX_OK;
+}
+
+static int cpc_attach(nx_network* h, int32_t n_chords, const int32_t* chord, int32_t n_slots,
+                      const int32_t* cslot) {
+  const bool ranks = h->cp_Eg > 0;
+  const int64_t Es = ranks ? h->cp_Eg : h->E;
+  const int nn = h->cp_nn, ns = n_slots;
+  std::vector<int> inc_off, inc, nrow, parent;
+  CHECK(download(inc_off, h->cp_inc_off, (int64_t)nn + 1));
+  CHECK(download(inc, h->cp_inc, 2 * (int64_t)inc_off[nn]));
+  CHECK(download(nrow, h->cp_nrow, 2 * (int64_t)nn));
+  CHECK(download(parent, h->cp_parent, 3 * (int64_t)nn));
+  std::vector<int> ends(2 * (size_t)Es, -1);  // per edge its two end nodes, from the incidence
+  for (int n = 0; n < nn; ++n)
+    for (int j = inc_off[n]; j < inc_off[n + 1]; ++j) ends[2 * (size_t)inc[2 * j] + inc[2 * j + 1]] = n;
+  std::vector<char> tree(Es, 0);
+  for (int n = 0; n < nn; ++n)
+    if (parent[3 * n] >= 0 && parent[3 * n + 1] >= 0) tree[parent[3 * n + 1]] = 1;
+  std::vector<int> slot(ns), slot_of(2 * (size_t)nn, -1);
+  for (int i = 0; i < ns; ++i) {
+    const int n = cslot[2 * i], s = cslot[2 * i + 1];
+    if (n < 0 || n >= nn || s < 0 || s > 1 || (s == 1 && nrow[2 * n + 1] < 0))
+      return fail(NX_ERR_ARG, "continuous pressure, cycles: slot out of range");
+    slot[i] = 2 * n + s;
+    if (i > 0 && slot[i] <= slot[i - 1])
+      return fail(NX_ERR_ARG, "continuous pressure, cycles: slots not sorted or repeated");
+    slot_of[slot[i]] = i;
+  }
+  std::vector<std::vector<int>> at(nn);  // per node: (chord, end) in chord order
+  for (int q = 0; q < n_chords; ++q) {
+    const int e = chord[q];
+    if (e < 0 || e >= Es || (q > 0 && e <= chord[q - 1]))
+      return fail(NX_ERR_ARG, "continuous pressure, cycles: chords out of range or not ascending");
+    const int u = ends[2 * (size_t)e], v = ends[2 * (size_t)e + 1];
+    if (u < 0 || v < 0 || u == v || tree[e])
+      return fail(NX_ERR_ARG, "continuous pressure, cycles: a chord is a forest edge or a loop");
+    for (int n : {u, v})  // every real slot at a chord end is one of U's columns
+      if (slot_of[2 * n] < 0 || (nrow[2 * n + 1] >= 0) != (slot_of[2 * n + 1] >= 0))
+        return fail(NX_ERR_ARG, "continuous pressure, cycles: a chord end's slots are not listed");
+    at[u].push_back(e);
+    at[u].push_back(0);
+    at[v].push_back(e);
+    at[v].push_back(1);
+  }
+  std::vector<int> ent_off(ns + 1, 0), ent;
+  for (int i = 0; i < ns; ++i) {
+    const std::vector<int>& a = at[slot[i] >> 1];
+    if (a.empty()) return fail(NX_ERR_ARG, "continuous pressure, cycles: a slot at no chord end");
+    for (size_t q = 0; q < a.size(); q += 2) {
+      const int o = ends[2 * (size_t)a[q] + 1 - a[q + 1]];
+      ent.insert(ent.end(), {a[q], a[q + 1], slot_of[2 * o], slot_of[2 * o + 1]});
+    }
+    ent_off[i + 1] = (int)(ent.size() / 4);
+  }
+  std::vector<int> nrow2, rec2;
+  if (!ranks) {  // the second sweep's rhs by node (2 n, 2 n + 1): its row table and records
+    nrow2.resize(2 * (size_t)nn);
+    for (int n = 0; n < nn; ++n) {
+      nrow2[2 * n] = 2 * n;
+      nrow2[2 * n + 1] = nrow[2 * n + 1] >= 0 ? 2 * n + 1 : -1;
+    }
+    if (h->cp_rec) {
+      CHECK(download(rec2, h->cp_rec, (int64_t)nn * kCpRecPad));
+      for (int i = 0; i < nn; ++i) {
+        int* r = rec2.data() + (size_t)i * kCpRecPad;
+        if (r[0] < 0 || r[0] >= nn) return fail(NX_ERR_STATE, "continuous pressure: node records");
+        r[1] = nrow2[2 * r[0]];
+        r[2] = nrow2[2 * r[0] + 1];
+      }
+    }
+  }
+  // memory: ns^2 (U^T Z, then the inverse) + 2 ns^2 (the Gauss-Jordan array) + the column
+  // batch (at most 512 columns or 256 MB); a failed allocation leaves the handle without it
+  const int batch = (int)std::max<int64_t>(
+      1, std::min<int64_t>(std::min(ns, 512), ((int64_t)1 << 25) / (2 * (int64_t)nn)));
+  CHECK(upload(&h->cpc_slot, slot.data(), ns, h->stream));
+  CHECK(upload(&h->cpc_slot_of, slot_of.data(), 2 * (int64_t)nn, h->stream));
+  CHECK(upload(&h->cpc_ent_off, ent_off.data(), (int64_t)ns + 1, h->stream));
+  CHECK(upload(&h->cpc_ent, ent.data(), (int64_t)ent.size(), h->stream));
+  if (!ranks) {
+    CHECK(upload(&h->cpc_nrow2, nrow2.data(), 2 * (int64_t)nn, h->stream));
+    if (!rec2.empty()) CHECK(upload(&h->cpc_rec2, rec2.data(), (int64_t)rec2.size(), h->stream));
+  }
+  CHECK(dalloc(&h->cpc_inv, (int64_t)ns * ns));
+  CHECK(dalloc(&h->cpc_gj, 2 * (int64_t)ns * ns + 1));
+  CHECK(dalloc(&h->cpc_scr, 2 * (int64_t)nn * batch));
+  CHECK(dalloc(&h->cpc_w, ns));
+  CHECK(dalloc(&h->cpc_nb2, 2 * (int64_t)nn));
+  CHECK(dalloc(&h->cpc_se0, 20 * Es));
+  CHECK(dalloc(&h->cpc_rho, 2 * (int64_t)nn));
+  CHECK(dalloc(&h->cpc_xd, 2 * (int64_t)nn));
+  HIPCALL(hipStreamSynchronize(h->stream));
+  h->cpc_batch = batch;
+  h->cpc_ns = ns;
+  return NX_OK;
+}
+
+// Continuous pressure on a graph with cycles: the chords of the node forest given to
+// nx_fe_set_cp and the border slots at their ends (see include/nxhip.h); none clears it.
+NX_API int nx_fe_cp_set_cycles(nx_network_t* h, int32_t n_chords, const int32_t* chord,
+                               int32_t n_slots, const int32_t* cslot) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  CHECK(flush_assembly(h));
+  if (!h->fe_cp) return fail(NX_ERR_STATE, "nx_fe_set_cp before nx_fe_cp_set_cycles");
+  CHECK(set_device(h));
+  HIPCALL(hipStreamSynchronize(h->stream));
+  CHECK(cpc_clear(h));
+  if (n_chords == 0) return NX_OK;
+  if (n_chords < 0 || n_slots < 1 || !chord || !cslot)
+    return fail(NX_ERR_ARG, "bad chord tables");
+  if (n_slots > 2 * kMaxCyc)
+    return fail(NX_ERR_ARG, "more border slots at chord ends than 2 kMaxCyc (the solve runs MINRES)");
+  const int rc = cpc_attach(h, n_chords, chord, n_slots, cslot);
+  if (rc != NX_OK) {
+    const std::string msg = g_err;
+    (void)hipStreamSynchronize(h->stream);
+    (void)cpc_clear(h);
+    return fail(rc, msg);
+  }
+  return NX_OK;
+}
+
+NX_API int nx_get_cp_cycles(nx_network_t* h, int32_t* ran, int32_t* builds) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (ran) *ran = h->cpc_last ? 1 : 0;
+  if (builds) *builds = h->cpc_builds;
+  return NX_OK;
+}
+
 // Continuous pressure (k > m >= 1), a forest: attach the node-condensed direct solve (see
 // include/nxhip.h); k = 0 detaches it.
 NX_API int nx_fe_set_cp(nx_network_t* h, int32_t k, int32_t m, int32_t nI, const double* cst,
@@ -13030,6 +13515,7 @@ NX_API int nx_fe_set_cp(nx_network_t* h, int32_t k, int32_t m, int32_t nI, const
   }
   h->cp_runs.clear();
   h->fe_cp = false;
+  CHECK(cpc_clear(h));  // (the chords belong to the tables that leave)
   if (k == 0) {
     h->cp_Eown = h->cp_Eg = 0;
     h->cp_gid_host.clear();

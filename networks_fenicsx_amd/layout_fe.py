@@ -31,7 +31,7 @@ so the device sums them in a fixed order (``k_assemble_fe``).
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -557,11 +557,20 @@ class CpTables:
     child_off: np.ndarray
     child: np.ndarray
     nown: np.ndarray  # the edge that writes each node's rows
+    # graphs with cycles (``build_cp_tables(..., cycles=True)``): the non-tree edges of the BFS
+    # forest, ascending, and the distinct real border slots at their ends, sorted -- (node,
+    # slot) pairs, slot 0 the pressure, 1 the multiplier (where the node has one)
+    chord: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    cslot: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))  # (n_slots, 2)
 
 
-def build_cp_tables(lay: FeLayout, src: np.ndarray, dst: np.ndarray) -> CpTables | None:
+def build_cp_tables(lay: FeLayout, src: np.ndarray, dst: np.ndarray,
+                    cycles: bool = False) -> CpTables | None:
     """Tables of the node-condensed direct solve for continuous pressure (``lay.m >= 1``), or
-    ``None`` when the graph is not a forest (a cycle: MINRES)."""
+    ``None`` when the graph is not a forest (a cycle: MINRES). ``cycles=True``: a non-tree
+    edge of the BFS becomes a chord (``chord``, ``cslot``: the grounded solve's low-rank
+    correction, ``nx_fe_cp_set_cycles``) instead; ``parent`` / ``child`` / the levels describe
+    the spanning forest, ``inc`` keeps every edge. A self-loop still gives ``None``."""
     from collections import deque
 
     from .element import condensed_cell_blocks
@@ -592,6 +601,9 @@ def build_cp_tables(lay: FeLayout, src: np.ndarray, dst: np.ndarray) -> CpTables
     # BFS forest from the lowest node of every component
     parent = np.full((n, 3), -1, dtype=np.int64)
     level = np.full(n, -1, dtype=np.int64)
+    if cycles and bool((u == v).any()):
+        return None  # a self-loop
+    is_chord = np.zeros(E, dtype=bool)
     for r in range(n):
         if level[r] >= 0:
             continue
@@ -605,7 +617,10 @@ def build_cp_tables(lay: FeLayout, src: np.ndarray, dst: np.ndarray) -> CpTables
                 if b == a or (parent[a, 1] == e):
                     continue
                 if level[b] >= 0:
-                    return None  # a cycle
+                    if not cycles:
+                        return None  # a cycle
+                    is_chord[e] = True  # (met from both its ends: recorded once)
+                    continue
                 level[b] = level[a] + 1
                 parent[b] = (a, e, 1 - end)
                 dq.append(b)
@@ -624,9 +639,18 @@ def build_cp_tables(lay: FeLayout, src: np.ndarray, dst: np.ndarray) -> CpTables
     Kh, Ch, Eh, Fh, tI = condensed_cell_blocks(lay.k, lay.m)
     cst = np.concatenate([Kh.ravel(), Ch.ravel(), Eh.ravel(), Fh.ravel()])
     i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()  # noqa: E731
-    return CpTables(lay.k, lay.m, int(tI.size), cst, i32(tI), int(n), i32(nrow), i32(eb),
-                    i32(lev_off), i32(order), i32(inc_off), i32(inc), i32(parent),
-                    i32(child_off), i32(child), i32(nown))
+    tab = CpTables(lay.k, lay.m, int(tI.size), cst, i32(tI), int(n), i32(nrow), i32(eb),
+                   i32(lev_off), i32(order), i32(inc_off), i32(inc), i32(parent),
+                   i32(child_off), i32(child), i32(nown))
+    chord = np.flatnonzero(is_chord)
+    if chord.size:
+        ends = np.unique(np.concatenate([u[chord], v[chord]]))
+        real = ends[nrow[ends, 1] >= 0]
+        cs = np.concatenate([np.stack([ends, np.zeros_like(ends)], axis=1),
+                             np.stack([real, np.ones_like(real)], axis=1)])
+        tab.chord = i32(chord)
+        tab.cslot = i32(cs[np.lexsort((cs[:, 1], cs[:, 0]))])
+    return tab
 
 
 def build_cp_rank_tables(tab: CpTables, part: FeLayout):
@@ -636,7 +660,8 @@ def build_cp_rank_tables(tab: CpTables, part: FeLayout):
     kernels (``eb`` of its own edges; ``gid`` their global ids); the node tables keep global
     nodes and edges, every rank solving the whole node forest over the summed blocks; ``nrow``
     names the summed node rhs (2n, 2n + 1 or -1); ``nrowx`` the local rows of the node rows
-    this rank owns, and ``nown`` the local edge that writes them (-1 elsewhere)."""
+    this rank owns, and ``nown`` the local edge that writes them (-1 elsewhere). ``chord`` /
+    ``cslot`` (a graph with cycles) pass through: the node tables are global on every rank."""
     from dataclasses import replace
 
     own_e = np.asarray(part.edges, dtype=np.int64)[: part.n_own_edges]
@@ -673,9 +698,11 @@ def build_cp_rank_tables(tab: CpTables, part: FeLayout):
 
 
 def cp_model(lay: FeLayout, tab: CpTables, val: np.ndarray, b: np.ndarray, R: np.ndarray,
-             cell_h: np.ndarray) -> np.ndarray:
+             cell_h: np.ndarray, info: dict | None = None) -> np.ndarray:
     """numpy restatement of the device's node-condensed solve (k_cp_edge, k_cp_nodes,
-    k_cp_back) for tests: ``x`` of the (k, m) system with values ``val`` and rhs ``b``."""
+    k_cp_back) for tests: ``x`` of the (k, m) system with values ``val`` and rhs ``b``. With
+    chords (``tab.chord``) the grounded sweep is corrected as ``fe_cp_solve`` does. ``info``
+    (a dict) receives the nodes' pivot inverses ``Pinv`` and the capacitance matrix ``cap``."""
     import scipy.sparse as sp
 
     A = sp.csr_matrix((val, lay.col, lay.rowptr), shape=(lay.n_rows, lay.n_rows))
@@ -767,6 +794,76 @@ def cp_model(lay: FeLayout, tab: CpTables, val: np.ndarray, b: np.ndarray, R: np
             if par[nd, 0] >= 0:
                 r -= blk(par[nd, 1], par[nd, 2], 1 - par[nd, 2]) @ xn[par[nd, 0]]
             xn[nd] = Pinv[nd] @ r
+    if info is not None:
+        info["Pinv"] = Pinv.copy()
+    if np.asarray(tab.chord).size:
+        # a graph with cycles: the sweeps above solved the grounded system S_g (every chord's
+        # off-diagonal blocks dropped); S = S_g + U C U^T, x = S_g^-1 (g - U w) with
+        # w = (I + C U^T Z)^-1 C U^T x_g, Z = S_g^-1 U (rhs-only sweeps with the stored pivots)
+        def sweep(gn):
+            hh, xx = np.zeros_like(gn), np.zeros_like(gn)  # (n, 2, columns)
+            for L in range(lev.size - 2, -1, -1):
+                for i in range(lev[L], lev[L + 1]):
+                    nd = tab.order[i]
+                    g = gn[nd].copy()
+                    for j in range(tab.child_off[nd], tab.child_off[nd + 1]):
+                        c = tab.child[j]
+                        g -= blk(par[c, 1], par[c, 2], 1 - par[c, 2]).T @ Pinv[c] @ hh[c]
+                    hh[nd] = g
+            for L in range(lev.size - 1):
+                for i in range(lev[L], lev[L + 1]):
+                    nd = tab.order[i]
+                    r = hh[nd].copy()
+                    if par[nd, 0] >= 0:
+                        r -= blk(par[nd, 1], par[nd, 2], 1 - par[nd, 2]) @ xx[par[nd, 0]]
+                    xx[nd] = Pinv[nd] @ r
+            return xx
+
+        cs = np.asarray(tab.cslot).reshape(-1, 2)
+        ns = cs.shape[0]
+        pos = {(int(a), int(s)): i for i, (a, s) in enumerate(cs)}
+        Cm = np.zeros((ns, ns))
+        for e in np.asarray(tab.chord):
+            for end in (0, 1):
+                a, o = eb[e, end], eb[e, 1 - end]
+                B = blk(e, end, 1 - end)
+                for s in (0, 1):
+                    for t in (0, 1):
+                        if (a, s) in pos and (o, t) in pos:
+                            Cm[pos[a, s], pos[o, t]] += B[s, t]
+        unit = np.zeros((n, 2, ns))
+        unit[cs[:, 0], cs[:, 1], np.arange(ns)] = 1.0
+        UtZ = sweep(unit)[cs[:, 0], cs[:, 1], :]
+        cap = np.eye(ns) + Cm @ UtZ
+        w = np.linalg.solve(cap, Cm @ xn[cs[:, 0], cs[:, 1]])
+        gn = np.zeros((n, 2))
+        for nd in range(n):
+            gn[nd] = (b[nrow[nd, 0]], b[nrow[nd, 1]] if nrow[nd, 1] >= 0 else 0.0)
+            for j in range(tab.inc_off[nd], tab.inc_off[nd + 1]):
+                e, end = inc[j]
+                gn[nd] += ge[e][2 * end:2 * end + 2]
+        gn[cs[:, 0], cs[:, 1]] -= w
+        xn = sweep(gn[:, :, None])[:, :, 0]
+        # one refinement of the grounded solve (k_cp_cyc_res, the sweep, k_cp_cyc_add): the
+        # 2 x 2 pivots' explicit inverses cost the one-sweep residual up to two digits
+        for _ in range(1):
+            rho = gn.copy()
+            for nd in range(n):
+                D = np.zeros((2, 2))
+                for j in range(tab.inc_off[nd], tab.inc_off[nd + 1]):
+                    e, end = inc[j]
+                    D += blk(e, end, end)
+                if nrow[nd, 1] < 0:
+                    D[1, 1] = 1.0
+                rho[nd] -= D @ xn[nd]
+                if par[nd, 0] >= 0:
+                    rho[nd] -= blk(par[nd, 1], par[nd, 2], 1 - par[nd, 2]) @ xn[par[nd, 0]]
+                for j in range(tab.child_off[nd], tab.child_off[nd + 1]):
+                    c = tab.child[j]
+                    rho[nd] -= blk(par[c, 1], par[c, 2], 1 - par[c, 2]).T @ xn[c]
+            xn = xn + sweep(rho[:, :, None])[:, :, 0]
+        if info is not None:
+            info["cap"] = cap
     for nd in range(n):
         x[nrow[nd, 0]] = xn[nd, 0]
         if nrow[nd, 1] >= 0:
