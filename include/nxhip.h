@@ -142,6 +142,9 @@ int nx_dims(nx_network_t* h, int64_t* n_rows, int64_t* n_cols, int64_t* nnz);
  *   edge_bc  E*2 doubles: rhs contribution at q_0 and q_N of each edge
  *            (-p_bc(source) at an inlet root, +p_bc(target) at an outlet leaf,
  *            0 elsewhere; assembly.py:258-260)
+ * edge_R NULL with R_const NaN keeps the resident R (NX_ERR_STATE if none was ever set): only
+ * f and edge_bc change, R is not uploaded and the matrix's version does not move -- what a
+ * loop over scenarios uses between two right-hand-side assemblies.
  */
 int nx_set_coefficients(nx_network_t* h, const double* edge_R, double R_const, double f,
                         const double* edge_bc);
@@ -415,6 +418,57 @@ int nx_set_coarse(nx_network_t* h, int32_t n_coarse, const int32_t* slot_cidx, i
 /* 1 if the last nx_solve replayed its iterations as HIP graphs (also with RCCL, unless
  * the capture failed or NXHIP_RCCL_GRAPH=0), 0 if it launched them one by one. */
 int nx_get_graph_mode(nx_network_t* h, int32_t* graph);
+
+/*
+ * Many boundary / source scenarios against the handle's current matrix in one batched pass
+ * of the direct solve. The reference answers one scenario per KSP solve (solver.py:107-135)
+ * and would loop compute_forms + assemble + solve (assembly.py:165-262, 329-368); here the
+ * matrix depends on R and the geometry alone, a scenario changes the right-hand side only,
+ * and the sweeps get a column dimension (k_b_*: grid = jobs x columns).
+ *
+ * nx_batch_supported: *ok = 1 when nx_batch_solve would take the batched kernels on this
+ * handle, else 0: an nx_create (P1/DG0) handle, one rank, not in a group,
+ * nx_set_solver(h, 1, .), the exact preconditioner, the LDS sweeps, and tree_exact or a
+ * cycle correction (nx_set_cycles). Anything else makes nx_batch_solve return NX_ERR_STATE.
+ *
+ * nx_batch_solve: n_cols scenarios.
+ *   edge_bc   n_cols x E x 2 (as nx_set_coefficients' edge_bc)
+ *   edge_f    n_cols x E, or NULL
+ *   f_const   n_cols, or NULL (then the handle's source); ignored where edge_f is given
+ *   order     0 device layout, 1 the output map (NX_ERR_STATE if none was set)
+ *   out       n_cols x n_rows; iters / relres / converged: n_cols each (any may be NULL)
+ * A pending deferred assembly is flushed first; the matrix must have been assembled. The
+ * lumped mass and, on a graph with cycles, the correction are made current for the matrix
+ * (nothing current is rebuilt). The handle's coefficients, rhs, x, tmp, published state and
+ * snapshots are left as they were. Columns go in chunks of NXHIP_BATCH_CHUNK (read per call)
+ * or the largest of <= 64 whose workspace fits a quarter of the free device memory; the
+ * workspace is allocated on first use and freed by nx_destroy (a failed allocation halves
+ * the chunk down to 1 before NX_ERR_HIP). Per column: solve, true residual
+ * ||b - A x|| / ||b|| against the CSR, one refinement pass for the columns above rtol (a
+ * list of those columns only), then the single-column nx_solve path (with its MINRES) for a
+ * column still above it. b = 0 gives x = 0, relres = 0, converged = 1. A column's bits do
+ * not depend on the other columns, its position, n_cols or the chunk size.
+ * NX_ERR_ARG: n_cols < 1, NULL edge_bc / out.
+ *
+ * nx_batch_rhs (test hook): only the batched rhs kernel; out = n_cols x n_rows, device
+ * layout, every column bit-equal to nx_assemble's rhs of that scenario.
+ *
+ * nx_get_batch_info: the last nx_batch_solve's kernel launches -- its batched passes (7 per
+ * chunk on a forest, 9 with cycles; 6 / 8 more for a chunk with a refinement pass) and what it had
+ * to make current first (1 for a flushed assembly, 1 for the lumped mass, and the whole build
+ * of the cycle correction: 2 n_cyc unit solves and the inversion), so a call that found
+ * everything current reports the passes alone; the launches inside a column's single-column
+ * fallback are not counted -- then the columns that took the refinement pass, the columns
+ * handed to the single-column path, and the chunk size used.
+ */
+int nx_batch_supported(nx_network_t* h, int32_t* ok);
+int nx_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                   const double* edge_f, const double* f_const, double rtol, int32_t order,
+                   double* out, int32_t* iters, double* relres, int32_t* converged);
+int nx_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc, const double* edge_f,
+                 const double* f_const, double* out);
+int nx_get_batch_info(nx_network_t* h, int32_t* launches, int32_t* refined, int32_t* fallback,
+                      int32_t* chunk);
 
 /* Copy the owned part of the solution / rhs to the host (n_rows doubles). */
 int nx_get_solution(nx_network_t* h, double* x);

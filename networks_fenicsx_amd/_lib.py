@@ -51,6 +51,10 @@ _SIGS = {
     "nx_set_source": (C.c_int, [_h, _pd]),
     "nx_assemble": (C.c_int, [_h, _i32, _i32]),
     "nx_solve": (C.c_int, [_h, _f64, _i32, _i32, _pi32, _pd, _pi32]),
+    "nx_batch_supported": (C.c_int, [_h, _pi32]),
+    "nx_batch_solve": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _pd, _pi32, _pd, _pi32]),
+    "nx_batch_rhs": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd]),
+    "nx_get_batch_info": (C.c_int, [_h, _pi32, _pi32, _pi32, _pi32]),
     "nx_get_solution": (C.c_int, [_h, _pd]),
     "nx_get_rhs": (C.c_int, [_h, _pd]),
     "nx_set_output_map": (C.c_int, [_h, _i64, _pi32]),
@@ -295,6 +299,8 @@ class Handle:
     # ------------------------------------------------------------------ lifecycle
     def close(self) -> None:
         self.__dict__.pop("_addr_v", None)
+        for pool in self.__dict__.pop("_batch_pools", {}).values():
+            pool.close()  # (arrays still viewing its buffers keep them alive)
         if getattr(self, "_h", None):
             lib().nx_destroy(self._h)
             self._h = None
@@ -371,6 +377,76 @@ class Handle:
         x = np.empty(self.n_rows, dtype=np.float64)
         check(lib().nx_get_solution(self.ptr, _ptr(x, C.c_double)))
         return x
+
+    # ------------------------------------------------------------------ batched solve
+    def batch_supported(self) -> bool:
+        """Whether ``nx_batch_solve`` takes the batched kernels on this handle."""
+        ok = C.c_int32(0)
+        check(lib().nx_batch_supported(self.ptr, C.byref(ok)))
+        return bool(ok.value)
+
+    def _batch_inputs(self, edge_bc, edge_f, f_const):
+        bc = np.ascontiguousarray(edge_bc, dtype=np.float64)
+        if bc.ndim != 3 or bc.shape[1:] != (self.n_edges, 2) or bc.shape[0] < 1:
+            raise ValueError("edge_bc must be (B, E, 2) with B >= 1")
+        B = bc.shape[0]
+        ef = None if edge_f is None else np.ascontiguousarray(edge_f, dtype=np.float64)
+        if ef is not None and ef.shape != (B, self.n_edges):
+            raise ValueError("edge_f must be (B, E)")
+        fc = None if f_const is None else np.ascontiguousarray(f_const, dtype=np.float64)
+        if fc is not None and fc.shape != (B,):
+            raise ValueError("f_const must be (B,)")
+        return B, bc, ef, fc
+
+    _BATCH_POOLS = 4  # batch sizes whose page-locked output buffers are kept
+
+    def batch_output(self, B: int) -> np.ndarray:
+        """A page-locked ``(B, n_rows)`` array for the solutions of B scenarios (every copy
+        from the device into it is one DMA; both paths of ``Solver.solve_many`` use it).
+
+        Cost: one pool per batch size, the last ``_BATCH_POOLS`` sizes kept, so alternating
+        between a few sizes allocates nothing new; a size beyond them pays ``hipHostMalloc``
+        again (and the evicted pool's ``hipHostFree``). A buffer is reused by the next call of
+        its size once every array of the earlier result has been dropped; a result still held
+        keeps its ``8 B n_rows`` bytes page-locked, and a call made meanwhile takes another
+        buffer. All of it is released with the handle."""
+        pools = self.__dict__.setdefault("_batch_pools", {})
+        pool = pools.pop(B, None)
+        if pool is None:
+            pool = PinnedPool(B * self.n_rows)
+            while len(pools) >= self._BATCH_POOLS:
+                pools.pop(next(iter(pools))).close()
+        pools[B] = pool  # (most recently used last)
+        return pool.take().reshape(B, self.n_rows)
+
+    def batch_solve(self, edge_bc, edge_f=None, f_const=None, rtol: float = 1e-12,
+                    blocks: bool = True):
+        """``nx_batch_solve``: ``(x (B, n_rows), iterations, relres, converged)``; ``blocks``:
+        every column in the output map's order, else the device layout."""
+        B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
+        out = self.batch_output(B)
+        it = np.zeros(B, dtype=np.int32)
+        rr = np.zeros(B, dtype=np.float64)
+        cv = np.zeros(B, dtype=np.int32)
+        check(lib().nx_batch_solve(self.ptr, B, _ptr(bc, C.c_double), _ptr(ef, C.c_double),
+                                   _ptr(fc, C.c_double), float(rtol), 1 if blocks else 0,
+                                   _ptr(out, C.c_double), _ptr(it, C.c_int32),
+                                   _ptr(rr, C.c_double), _ptr(cv, C.c_int32)))
+        return out, it, rr, cv.astype(bool)
+
+    def batch_rhs(self, edge_bc, edge_f=None, f_const=None) -> np.ndarray:
+        """``nx_batch_rhs`` (test hook): the scenarios' right-hand sides, device layout."""
+        B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
+        out = np.empty((B, self.n_rows), dtype=np.float64)
+        check(lib().nx_batch_rhs(self.ptr, B, _ptr(bc, C.c_double), _ptr(ef, C.c_double),
+                                 _ptr(fc, C.c_double), _ptr(out, C.c_double)))
+        return out
+
+    def batch_info(self) -> dict:
+        """``nx_get_batch_info`` of the last :meth:`batch_solve`."""
+        v = [C.c_int32() for _ in range(4)]
+        check(lib().nx_get_batch_info(self.ptr, *[C.byref(x) for x in v]))
+        return dict(zip(("launches", "refined", "fallback", "chunk"), (int(x.value) for x in v)))
 
     def set_output_map(self, rows: np.ndarray) -> None:
         """Owned rows in output order (``nx_set_output_map``): the solver's function blocks."""

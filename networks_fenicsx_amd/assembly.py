@@ -104,6 +104,46 @@ def edge_boundary_rhs(mesh: NetworkMesh, edge_ids: np.ndarray, pbc: np.ndarray) 
     return edge_bc
 
 
+def batch_coefficients(mesh: NetworkMesh, edge_ids: np.ndarray, p_bc, f=None):
+    """The rhs coefficients of B scenarios, as ``nx_batch_solve`` takes them (no device):
+    ``(edge_bc (B, E, 2), edge_f (B, E) | None, f_const (B,) | None)`` in the local edge order
+    ``edge_ids``.
+
+    ``p_bc``: a sequence of B items, each in any form :func:`evaluate_nodal` accepts, or an
+    array ``(B, num_nodes)`` of nodal values. ``f``: None (both outputs None: the resident
+    source applies), B scalars, or ``(B, num_edges)`` values in ``graph.edges()`` order. Each
+    scenario is normalised exactly as ``compute_forms`` does it
+    (:func:`edge_boundary_rhs`). A 1-D ``f`` always means B scalars, one per scenario: one
+    per-edge vector meant for every scenario is rejected (or, where ``num_edges == B``, read as
+    scalars) -- repeat it into ``(B, num_edges)`` (``np.tile(f, (B, 1))``)."""
+    edge_ids = np.asarray(edge_ids)
+    if isinstance(p_bc, np.ndarray):
+        if p_bc.ndim != 2 or p_bc.shape[1] != mesh.num_nodes:
+            raise ValueError(f"p_bc array must be (B, {mesh.num_nodes}), got {p_bc.shape}")
+        items = list(p_bc)
+    elif isinstance(p_bc, (list, tuple)):
+        items = list(p_bc)
+    else:
+        raise ValueError("p_bc must be a sequence of scenarios or an array (B, num_nodes)")
+    B = len(items)
+    if B < 1:
+        raise ValueError("at least one scenario is needed")
+    edge_bc = np.empty((B, edge_ids.size, 2), dtype=np.float64)
+    for j, item in enumerate(items):
+        pbc = evaluate_nodal(item, mesh.node_coordinates)
+        edge_bc[j] = edge_boundary_rhs(mesh, edge_ids, pbc)
+    if f is None:
+        return edge_bc, None, None
+    fv = np.asarray([c.value if isinstance(c, Constant) else c for c in f]
+                    if isinstance(f, (list, tuple)) else f, dtype=np.float64)
+    if fv.ndim == 1 and fv.size == B:
+        return edge_bc, None, np.ascontiguousarray(fv)
+    if fv.ndim == 2 and fv.shape == (B, mesh.num_edges):
+        return edge_bc, np.ascontiguousarray(fv[:, edge_ids]), None
+    raise ValueError(f"f must be None, {B} scalars or ({B}, {mesh.num_edges}) per-edge values, "
+                     f"got shape {fv.shape}")
+
+
 def _scalar(c, name: str, default: float) -> float:
     if c is None:
         return default
@@ -687,8 +727,11 @@ class HydraulicNetworkAssembler:
         edge_bc = edge_boundary_rhs(mesh, edge_ids, pbc)
         self._handle.set_coefficients(R_edge, R_const, f_val, edge_bc)
         self._handle.set_source(f_edge)
-        self._coefficients = {"R": R_const if R_edge is None else "per-edge",
-                              "f": f_val if f_edge is None else "per-edge", "p_bc": pbc}
+        # what was uploaded (local edge order), kept so that a scenario loop can put it back
+        self._coefficients = {"R": R_const if R_edge is None else R_edge,
+                              "f": f_val if f_edge is None else f_edge, "p_bc": pbc,
+                              "edge_bc": edge_bc}
+        self._forms_version = getattr(self, "_forms_version", 0) + 1
         M = len(self._flux_spaces)
         self._a = _BilinearBlocks(self, M)  # (M + 2)^2 blocks, materialised on access
         self._L = [FormBlock(self, "boundary", c) for c in range(M)]
@@ -709,11 +752,41 @@ class HydraulicNetworkAssembler:
         # enqueued on the handle's stream: the solve (same stream) and every host read of
         # the matrix / rhs order after it, so the host does not wait here
         self._handle.assemble(assemble_lhs, assemble_rhs)
+        if assemble_lhs:  # (solve_many assembles the matrix itself when the forms are newer)
+            self._lhs_forms_version = getattr(self, "_forms_version", 0)
         if A is None and assemble_lhs:
             A = DeviceMatrix(self._handle, kind)
         if b is None and assemble_rhs:
             b = DeviceVector(self._handle)
         return (A, b)
+
+    # ------------------------------------------------------ scenario loops (Solver.solve_many)
+    @property
+    def lhs_current(self) -> bool:
+        """Whether the matrix was assembled (through this assembler) from the last
+        ``compute_forms``."""
+        return getattr(self, "_lhs_forms_version", -1) == getattr(self, "_forms_version", 0)
+
+    def scenario_coefficients(self, p_bc, f=None):
+        """:func:`batch_coefficients` for this assembler's mesh and local edges."""
+        return batch_coefficients(self._network_mesh, self._edge_ids, p_bc, f)
+
+    def set_rhs_coefficients(self, edge_bc: np.ndarray, f_const: float | None,
+                             edge_f: np.ndarray | None) -> None:
+        """Boundary values and source of one scenario (local edge order); R stays resident on
+        the device and is not uploaded again (``nx_set_coefficients`` with a NaN ``R_const``).
+        ``f_const`` and ``edge_f`` both None: the source of the last ``compute_forms``."""
+        co = self._coefficients
+        if edge_f is None and f_const is None:
+            f0 = co["f"]
+            edge_f, f_const = (f0, 0.0) if isinstance(f0, np.ndarray) else (None, float(f0))
+        self._handle.set_coefficients(None, float("nan"), 0.0 if f_const is None else f_const,
+                                      edge_bc)
+        self._handle.set_source(edge_f)
+
+    def restore_rhs_coefficients(self) -> None:
+        """Put back the boundary values and the source of the last ``compute_forms``."""
+        self.set_rhs_coefficients(self._coefficients["edge_bc"], None, None)
 
     # --------------------------------------------------------------- accessors
     @property

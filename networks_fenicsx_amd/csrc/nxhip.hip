@@ -1861,14 +1861,15 @@ __device__ __forceinline__ void direct_residual(const PcArgs& pa, const ChainLan
 constexpr int kCapLvl = 64;  // job levels whose slot offsets are staged in LDS
 constexpr int kWaveKids = 4;  // junction children per slot of the one-wave level sweeps
 
+// The up sweep of one job (workgroup blockIdx.x): the body of k_pc_up_lds, shared with the
+// batched direct solve's k_b_up, whose workgroups run it on their own column's vectors.
 template <bool MULTI, int W, int CPL>
-__global__ __launch_bounds__(kPcThreads) void k_pc_up_lds(PcArgs pa, double* __restrict__ y,
-                                                          const double* __restrict__ r2,
-                                                          MrState* __restrict__ st,
-                                                          MrState* __restrict__ other,
-                                                          const double* __restrict__ partA,
-                                                          int nA, const double* __restrict__ red,
-                                                          int mode) {
+__device__ __forceinline__ void pc_up_lds_body(const PcArgs& pa, double* __restrict__ y,
+                                               const double* __restrict__ r2,
+                                               MrState* __restrict__ st,
+                                               MrState* __restrict__ other,
+                                               const double* __restrict__ partA, int nA,
+                                               const double* __restrict__ red, int mode) {
   __shared__ double sT[kCapC], sIt[kCapC], sIb[kCapC];
   __shared__ double sD0[kCapS], sJ0[kCapS], sD[kCapS], sJ[kCapS];
   __shared__ double sIv[kCapS];  // direct mode: 1 / D of every slot (one division per slot)
@@ -2215,6 +2216,17 @@ __global__ __launch_bounds__(kPcThreads) void k_pc_up_lds(PcArgs pa, double* __r
   NX_PHASE(19);
   NX_PHASE_END(16);
   if (MULTI && dense && pa.fused) pc_cpart_last(pa, sAtop);
+}
+
+template <bool MULTI, int W, int CPL>
+__global__ __launch_bounds__(kPcThreads) void k_pc_up_lds(PcArgs pa, double* __restrict__ y,
+                                                          const double* __restrict__ r2,
+                                                          MrState* __restrict__ st,
+                                                          MrState* __restrict__ other,
+                                                          const double* __restrict__ partA,
+                                                          int nA, const double* __restrict__ red,
+                                                          int mode) {
+  pc_up_lds_body<MULTI, W, CPL>(pa, y, r2, st, other, partA, nA, red, mode);
 }
 
 // LDS of the top part's solve (k_pc_top_lds; with pa.topdown also every direct down sweep)
@@ -3005,12 +3017,14 @@ __device__ void pc_pack_last(const PcArgs& pa, const double* partB, const double
 // part (one rank) or coarse forest (several) a launch of its own solved (pa.topdown /
 // pa.coarsedown off, e.g. C4's 1024 jobs on one GPU): no top-part LDS, 141 -> 20 KB, two
 // workgroups per CU instead of one
+// (the body of k_pc_down_lds, shared with the batched direct solve's k_b_down, whose
+// workgroups run it on their own column's vectors)
 template <bool MULTI, int W, int CPL, bool DIRK, bool TOPL = true>
-__global__ __launch_bounds__(kPcThreads) void k_pc_down_lds(PcArgs pa, double* __restrict__ y,
-                                                            const double* __restrict__ r2,
-                                                            double* __restrict__ z,
-                                                            const MrState* __restrict__ st,
-                                                            double* __restrict__ partB, int mode_in) {
+__device__ __forceinline__ void pc_down_lds_body(const PcArgs& pa, double* __restrict__ y,
+                                                 const double* __restrict__ r2,
+                                                 double* __restrict__ z,
+                                                 const MrState* __restrict__ st,
+                                                 double* __restrict__ partB, int mode_in) {
   const int mode = DIRK ? kModeDirect : mode_in;
   // one rank, direct (pa.topdown): the top part's first indices before anything else (they
   // need no per-job offsets; the scalar loads of the prologue below would hold them back)
@@ -3395,6 +3409,228 @@ __global__ __launch_bounds__(kPcThreads) void k_pc_down_lds(PcArgs pa, double* _
     pc_prep_in_block<kPcThreads>(pa, MULTI ? pa.mdense != 0 : pa.dense != 0, sTa, sGz, sGp, sGt,
                                  sGd, sGc);
   }
+}
+
+template <bool MULTI, int W, int CPL, bool DIRK, bool TOPL = true>
+__global__ __launch_bounds__(kPcThreads) void k_pc_down_lds(PcArgs pa, double* __restrict__ y,
+                                                            const double* __restrict__ r2,
+                                                            double* __restrict__ z,
+                                                            const MrState* __restrict__ st,
+                                                            double* __restrict__ partB, int mode_in) {
+  pc_down_lds_body<MULTI, W, CPL, DIRK, TOPL>(pa, y, r2, z, st, partB, mode_in);
+}
+
+// ======================================================================================
+// Batched direct solve (nx_batch_solve): many right-hand sides against one assembled matrix,
+// one rank, the LDS sweeps in mode kModeDirect. Every vector gets a column dimension: column
+// c of B / X / R / D starts at c * ld, and everything the sweeps write per right-hand side
+// (chain_T / It / Ib, slot_D / J / A / B / z) lives in a workspace with one stripe per
+// column, so the handle's own scratch, x, rhs and tmp are never touched. Grid = (jobs,
+// columns) for the up and down sweeps, (columns) for the top part: a workgroup runs the
+// single solve's body on its column, so a column's bits cannot depend on its neighbours, its
+// position or the chunk. The phases are ordered by the stream alone (a batched grid is
+// larger than what is co-resident). `list` (refinement pass): the columns a launch serves.
+// ======================================================================================
+struct BatchCols {
+  const int* list;  // workspace columns served by this launch, or null: 0 .. gridDim - 1
+  int64_t ld;       // doubles between two columns of a vector
+  int64_t n_chain, n_slot;  // doubles between two columns of the chain / slot arrays
+  double *chain_T, *chain_It, *chain_Ib, *slot_D, *slot_J, *slot_A, *slot_B, *slot_z;
+};
+
+__device__ __forceinline__ int batch_col(const BatchCols& bc, int i) {
+  return bc.list ? bc.list[i] : i;
+}
+
+__device__ __forceinline__ PcArgs batch_col_args(const PcArgs& pa, const BatchCols& bc, int col) {
+  PcArgs p = pa;
+  p.chain_T = bc.chain_T + col * bc.n_chain;
+  p.chain_It = bc.chain_It + col * bc.n_chain;
+  p.chain_Ib = bc.chain_Ib + col * bc.n_chain;
+  p.slot_D = bc.slot_D + col * bc.n_slot;
+  p.slot_J = bc.slot_J + col * bc.n_slot;
+  p.slot_A = bc.slot_A + col * bc.n_slot;
+  p.slot_B = bc.slot_B + col * bc.n_slot;
+  p.slot_z = bc.slot_z + col * bc.n_slot;
+  return p;
+}
+
+template <int W, int CPL>
+__global__ __launch_bounds__(kPcThreads) void k_b_up(PcArgs pa, BatchCols bc,
+                                                     const double* __restrict__ in) {
+  const int col = batch_col(bc, blockIdx.y);
+  const PcArgs p = batch_col_args(pa, bc, col);
+  double* b = const_cast<double*>(in) + col * bc.ld;  // (mode kModeDirect only reads it)
+  pc_up_lds_body<false, W, CPL>(p, b, b, nullptr, nullptr, nullptr, 0, nullptr, kModeDirect);
+}
+
+__global__ __launch_bounds__(kTopThreads) void k_b_top(PcArgs pa, BatchCols bc,
+                                                       const double* __restrict__ in,
+                                                       double* __restrict__ out) {
+  __shared__ double sD0[kCapT], sJ0[kCapT], sD[kCapT], sJ[kCapT], sGp[kCapT], sY[kCapT];
+  __shared__ int sPar[kCapT], sLam[kCapT];
+  __shared__ int sOff[kCapT + 1];
+  __shared__ int sChild[kCapTDC];
+  __shared__ double sG[kCapTDC], sDD[kCapTDC], sDJ[kCapTDC];
+  __shared__ int sLv[kMaxTopLvl + 1];
+  const int col = batch_col(bc, blockIdx.x);
+  const PcArgs p = batch_col_args(pa, bc, col);
+  double* b = const_cast<double*>(in) + col * bc.ld;
+  TopPre pre;
+  top_pre_idx(p, pre);
+  top_pre_val(p, b, pre);
+  top_body<false>(p, b, b, out + col * bc.ld, nullptr, nullptr, 0, nullptr, nullptr, kModeDirect,
+                  TopLds{sD0, sJ0, sD, sJ, sGp, sY, sPar, sLam, sOff, sChild, sG, sDD, sDJ, sLv},
+                  false, pre);
+}
+
+template <int W, int CPL>
+__global__ __launch_bounds__(kPcThreads) void k_b_down(PcArgs pa, BatchCols bc,
+                                                       const double* __restrict__ in,
+                                                       double* __restrict__ out) {
+  const int col = batch_col(bc, blockIdx.y);
+  const PcArgs p = batch_col_args(pa, bc, col);
+  double* b = const_cast<double*>(in) + col * bc.ld;
+  pc_down_lds_body<false, W, CPL, true, false>(p, b, b, out + col * bc.ld, nullptr, nullptr,
+                                               kModeDirect);
+}
+
+// The right-hand sides of a chunk of scenarios, k_assemble's arithmetic (vertex, sqrt, no
+// contraction) so that every column is bit-equal to a single rhs assembly: one thread per
+// flux vertex (edge e, k = 0 .. N) computes the cell length once and writes every column's
+// boundary value, -(f h) and zeros; the threads after them zero the multiplier rows.
+// edge_f: column c's per-edge source at edge_f + c * ef_ld (ef_ld = 0: one source for all),
+// or null: the constant f_const[c].
+__global__ __launch_bounds__(kBlock) void k_b_rhs(EdgeArgs ea, int64_t n_lm, int ncols,
+                                                  const double* __restrict__ edge_bc,
+                                                  const double* __restrict__ edge_f,
+                                                  int64_t ef_ld,
+                                                  const double* __restrict__ f_const,
+                                                  double* __restrict__ out, int64_t ld) {
+#pragma clang fp contract(off)
+  const int N = ea.N;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t nv = ea.E * (int64_t)(N + 1);
+  if (i >= nv) {
+    const int64_t j = i - nv;
+    if (j < n_lm)
+      for (int c = 0; c < ncols; ++c) out[c * ld + ea.E * (int64_t)(2 * N + 1) + j] = 0.0;
+    return;
+  }
+  const int64_t e = i / (N + 1);
+  const int k = (int)(i - e * (N + 1));
+  const int64_t base = e * (2 * N + 1);
+  if (k == N) {
+    for (int c = 0; c < ncols; ++c)
+      out[c * ld + base + 2 * N] = edge_bc[(c * ea.E + e) * 2 + 1];
+    return;
+  }
+  const double invN = 1.0 / (double)N;
+  double x0[3], x1[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    x0[c] = ea.edge_x[6 * e + c];
+    x1[c] = ea.edge_x[6 * e + 3 + c];
+  }
+  double pa[3], pb[3];
+  vertex(x0, x1, k, N, invN, pa);
+  vertex(x0, x1, k + 1, N, invN, pb);
+  const double d0 = pb[0] - pa[0], d1 = pb[1] - pa[1], d2 = pb[2] - pa[2];
+  const double h = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+  for (int c = 0; c < ncols; ++c) {
+    const double fe = edge_f ? edge_f[c * ef_ld + e] : f_const[c];
+    out[c * ld + base + 2 * k + 1] = -(fe * h);  // negated pressure row: -(f h)
+    out[c * ld + base + 2 * k] = (k == 0) ? edge_bc[(c * ea.E + e) * 2] : 0.0;
+  }
+}
+
+// R = B - A X for the listed columns, one row per thread: the row's nonzeros are read once
+// per tile of kBatchTile columns (sum order left to right, no contraction -- a column's r is
+// the same whatever else is in the tile); per column and block the partial ||r||^2 and
+// ||b||^2 (part[(2 col) nblk + block], part[(2 col + 1) nblk + block]; k_b_norms sums them
+// in a fixed order).
+constexpr int kBatchTile = 8;
+__global__ __launch_bounds__(kBlock) void k_b_res(Csr A, const double* __restrict__ X,
+                                                  const double* __restrict__ B,
+                                                  double* __restrict__ R, int64_t ld,
+                                                  const int* __restrict__ list, int ncols,
+                                                  double* __restrict__ part, int nblk) {
+#pragma clang fp contract(off)
+  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool on = row < A.n_rows;
+  const int p0 = on ? A.rowptr[row] : 0, p1 = on ? A.rowptr[row + 1] : 0;
+  for (int c0 = 0; c0 < ncols; c0 += kBatchTile) {
+    const int nt = min(kBatchTile, ncols - c0);
+    int64_t off[kBatchTile];
+    int colv[kBatchTile];
+    double acc[kBatchTile];
+#pragma unroll
+    for (int k = 0; k < kBatchTile; ++k) {
+      colv[k] = k < nt ? (list ? list[c0 + k] : c0 + k) : 0;
+      off[k] = colv[k] * ld;
+      acc[k] = 0.0;
+    }
+    for (int p = p0; p < p1; ++p) {
+      const double a = A.val[p];
+      const int c = A.col[p];
+#pragma unroll
+      for (int k = 0; k < kBatchTile; ++k)
+        if (k < nt) {
+          const double prod = a * X[off[k] + c];
+          acc[k] += prod;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kBatchTile; ++k) {
+      if (k >= nt) break;  // block-uniform
+      double rr = 0.0, bb = 0.0;
+      if (on) {
+        const double bv = B[off[k] + row];
+        const double rv = bv - acc[k];
+        R[off[k] + row] = rv;
+        rr = rv * rv;
+        bb = bv * bv;
+      }
+      double* pc = part + 2 * (int64_t)colv[k] * nblk;
+      block_sum_store(rr, pc + blockIdx.x);
+      __syncthreads();
+      block_sum_store(bb, pc + nblk + blockIdx.x);
+      __syncthreads();
+    }
+  }
+}
+
+// stats[2 col] = ||r||^2, stats[2 col + 1] = ||b||^2 of the listed columns from k_b_res's
+// partials (one workgroup per column, fixed order).
+__global__ __launch_bounds__(kReduceThreads) void k_b_norms(const double* __restrict__ part,
+                                                            int nblk,
+                                                            const int* __restrict__ list,
+                                                            double* __restrict__ stats) {
+  const int col = list ? list[blockIdx.x] : blockIdx.x;
+  const double rr = reduce_partials(part + 2 * (int64_t)col * nblk, nblk);
+  __syncthreads();
+  const double bb = reduce_partials(part + (2 * (int64_t)col + 1) * nblk, nblk);
+  if (threadIdx.x == 0) {
+    stats[2 * col] = rr;
+    stats[2 * col + 1] = bb;
+  }
+}
+
+// X[col] += D[col] on the listed columns (the refinement pass's correction).
+__global__ __launch_bounds__(kBlock) void k_b_add(double* __restrict__ X,
+                                                  const double* __restrict__ D, int64_t ld,
+                                                  const int* __restrict__ list, int64_t n) {
+  const int col = list ? list[blockIdx.y] : blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) X[col * ld + i] += D[col * ld + i];
+}
+
+// Every column in the output order (nx_set_output_map) for the chunk's one copy to the host.
+__global__ __launch_bounds__(kBlock) void k_b_gather(const double* __restrict__ X, int64_t ld,
+                                                     const int* __restrict__ idx, int64_t n,
+                                                     double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) out[blockIdx.y * ld + i] = X[blockIdx.y * ld + idx[i]];
 }
 
 // ======================================================================================
@@ -7399,6 +7635,12 @@ struct nx_network {
   // the grounded sweep's one refinement: the blocks with a zero ge (20 per edge), the node
   // residual and the sweep's values (2 cp_nn each)
   double *cpc_se0 = nullptr, *cpc_rho = nullptr, *cpc_xd = nullptr;
+  // nx_batch_solve: the column workspace (one allocation for bws_cap columns, carved by
+  // batch_carve; allocated on first use, freed in nx_destroy) and the last call's figures
+  void* bws = nullptr;
+  int bws_cap = 0;
+  size_t bws_bytes = 0;
+  int b_launches = 0, b_refined = 0, b_fallback = 0, b_chunk = 0;
   int64_t cpc_version = -1;  // R's version its capacitance matrix was built for (fe_cp_solve)
   bool cpc_failed = false;   // a singular capacitance matrix: the solves run MINRES
   int cpc_builds = 0;
@@ -9914,6 +10156,7 @@ NX_API int nx_destroy(nx_network_t* h) {
     if (p) (void)hipFree(p);
   for (void* p : h->pc_bufs)
     if (p) (void)hipFree(p);
+  if (h->bws) (void)hipFree(h->bws);
   if (h->h_st) (void)hipHostFree(h->h_st);
   if (h->h_last) (void)hipHostFree(h->h_last);
   for (auto& e : h->ev)
@@ -9952,6 +10195,18 @@ NX_API int nx_set_coefficients(nx_network_t* h, const double* edge_R, double R_c
   if (!h) return fail(NX_ERR_ARG, "null handle");
   if (h->E > 0 && edge_bc == nullptr) return fail(NX_ERR_ARG, "edge_bc is NULL");
   CHECK(set_device(h));
+  // edge_R NULL and R_const NaN: the resident R stays (a scenario loop changes f and the
+  // boundary values only: no upload of R, the matrix and everything built for it stay current)
+  const bool keep_R = edge_R == nullptr && R_const != R_const;
+  if (keep_R) {
+    if (!h->have_coeffs) return fail(NX_ERR_STATE, "no resident R to keep (set R once first)");
+    if (h->E > 0)
+      HIPCALL(hipMemcpyAsync(h->edge_bc, edge_bc, sizeof(double) * 2 * h->E, hipMemcpyHostToDevice,
+                             h->stream));
+    h->f = f;
+    HIPCALL(hipStreamSynchronize(h->stream));
+    return chain_rec_refresh(h);
+  }
   if (h->E > 0) {
     std::vector<double> Rc;
     if (!edge_R) Rc.assign((size_t)h->E, R_const);
@@ -10508,6 +10763,18 @@ int cyc_invert(nx_network* h) {
   if (b == 1) return fail(NX_ERR_STATE, "cycle chain: no coupling at its grounded end");
   if (b == 2) return fail(NX_ERR_STATE, "cycle correction is singular");
   return NX_OK;
+}
+
+// The kernel launches one cyc_build issues on one rank (nx_get_batch_info counts them in a
+// batch that had to build the correction): per column of Z the unit right-hand side and the
+// tree solve alone (launch_direct_wc with cyc_raw: the up sweep, the top part unless every
+// down workgroup solves it, the down sweep, the fused check's publish step or the CSR residual
+// and its publish step), then k_cyc_cap and cyc_invert (k_gj_init, a pivot and an elimination
+// per column, k_gj_out).
+int cyc_build_launches(const nx_network* h) {
+  const int m = 2 * h->n_cyc;
+  const int sweeps = (h->pc_jobs > 0 ? 2 : 0) + (top_down_on(h) ? 0 : 1) + (h->fres_ok ? 1 : 2);
+  return m * (1 + sweeps) + 1 + (1 + 2 * m + 1);
 }
 
 // Graphs with cycles: Z = A_g^{-1} U column by column (the tree solve of a unit right-hand
@@ -12153,6 +12420,457 @@ NX_API int nx_solve(nx_network_t* h, double rtol, int32_t maxit, int32_t check_e
   if (h->group) return fail(NX_ERR_STATE, "the handle belongs to a group: use nx_group_solve");
   nx_network* hs[1] = {h};
   return solve_team(Team{hs, 1, nullptr}, rtol, maxit, check_every, iters, relres, converged);
+}
+
+// ---- nx_batch_solve: many boundary / source scenarios against the handle's matrix ----------
+namespace {
+
+// Batched forms of the cycle correction x -= Z Cinv U^T x (k_cyc_w / k_cyc_fix, the same
+// sums in the same order) on the listed columns: w = Cinv U^T x per column (U^T x in dynamic
+// LDS, m doubles), then x -= Z w.
+__global__ __launch_bounds__(256) void k_b_cyc_w(const double* __restrict__ X, int64_t ld,
+                                                 const int* __restrict__ list,
+                                                 const int* __restrict__ rows, int m,
+                                                 const double* __restrict__ cinvT,
+                                                 double* __restrict__ w) {
+  extern __shared__ double g[];
+  const int col = list ? list[blockIdx.y] : blockIdx.y;
+  const double* x = X + col * ld;
+  for (int i = threadIdx.x; i < m; i += 256) g[i] = x[rows[i]];
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  double s = 0.0;
+  for (int j = 0; j < m; ++j) s += cinvT[(int64_t)j * m + i] * g[j];
+  w[(int64_t)col * m + i] = s;
+}
+
+__global__ __launch_bounds__(kBlock) void k_b_cyc_fix(double* __restrict__ X, int64_t ld,
+                                                      const int* __restrict__ list,
+                                                      const double* __restrict__ Z, int64_t ldz,
+                                                      const double* __restrict__ w, int m,
+                                                      int64_t n) {
+  const int col = list ? list[blockIdx.y] : blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const double* wc = w + (int64_t)col * m;
+  double s = 0.0;
+  for (int j = 0; j < m; ++j) s += Z[(int64_t)j * ldz + i] * wc[j];
+  X[col * ld + i] -= s;
+}
+
+constexpr int kBatchChunkMax = 64;     // default chunk: columns per pass
+constexpr int kBatchChunkEnvMax = 4096;  // NXHIP_BATCH_CHUNK is clamped to this (grid.y)
+constexpr double kBatchMemShare = 0.25;  // of the free device memory, for the workspace
+
+// The workspace of `cap` columns, carved from one allocation (doubles first, then ints).
+struct BatchWs {
+  double *B, *X, *R, *D;  // cap x ld each: rhs, solution, residual, correction / output
+  BatchCols cols;         // the sweeps' per-column scratch
+  double *bc, *ef, *fc;   // the chunk's inputs: cap x 2E, cap x E, cap
+  double *part, *stats;   // residual partials (cap x 2 nblk), ||r||^2 | ||b||^2 (cap x 2)
+  double* cw;             // cycle correction: w (cap x m)
+  double* save;           // the handle's x | tmp | rhs while a build of the cycle correction
+                          // or a fallback solve borrows them (3 n_col)
+  int* list;              // cap
+  int nblk;
+};
+
+size_t batch_col_doubles(const nx_network* h) {
+  const int64_t E = h->E, S = std::max<int64_t>(h->pc_slots, 1), m = 2 * (int64_t)h->n_cyc;
+  const int nblk = grid_of(h->n_own, kBlock);
+  return (size_t)(4 * h->n_col + 3 * E + 5 * S + 3 * E + 1 + 2 * nblk + 2 + m);
+}
+size_t batch_bytes(const nx_network* h, int cap) {
+  return 8 * (batch_col_doubles(h) * (size_t)cap + (size_t)(3 * h->n_col)) +
+         sizeof(int) * (size_t)cap + 64;
+}
+BatchWs batch_carve(const nx_network* h, int cap) {
+  const int64_t E = h->E, S = std::max<int64_t>(h->pc_slots, 1), m = 2 * (int64_t)h->n_cyc;
+  const int64_t ld = h->n_col;
+  BatchWs w{};
+  double* p = static_cast<double*>(h->bws);
+  auto take = [&](int64_t n) {
+    double* q = p;
+    p += n;
+    return q;
+  };
+  w.nblk = grid_of(h->n_own, kBlock);
+  w.B = take(cap * ld);
+  w.X = take(cap * ld);
+  w.R = take(cap * ld);
+  w.D = take(cap * ld);
+  w.cols.list = nullptr;
+  w.cols.ld = ld;
+  w.cols.n_chain = E;
+  w.cols.n_slot = S;
+  w.cols.chain_T = take(cap * E);
+  w.cols.chain_It = take(cap * E);
+  w.cols.chain_Ib = take(cap * E);
+  w.cols.slot_D = take(cap * S);
+  w.cols.slot_J = take(cap * S);
+  w.cols.slot_A = take(cap * S);
+  w.cols.slot_B = take(cap * S);
+  w.cols.slot_z = take(cap * S);
+  w.bc = take(cap * 2 * E);
+  w.ef = take(cap * E);
+  w.fc = take(cap);
+  w.part = take((int64_t)cap * 2 * w.nblk);
+  w.stats = take(cap * 2);
+  w.cw = take(cap * m);
+  w.save = take(3 * ld);
+  w.list = reinterpret_cast<int*>(p);
+  return w;
+}
+
+// One rank, P1/DG0, the direct solve's LDS sweeps exact on this handle (a forest, or the
+// cycle correction set): what the batched kernels serve.
+bool batch_ok(const nx_network* h) {
+  return h && !h->fe && !h->fe_cp && !proc_rank(h) && h->group == nullptr && h->nranks == 1 &&
+         h->n_ghost == 0 && direct_local(h) && (h->tree_exact || h->n_cyc > 0);
+}
+
+// Whether the allocation holds `chunk` columns as batch_carve lays them out NOW: a column's
+// size follows the decomposition's slots and the cycle chains, which nx_set_preconditioner
+// and nx_set_cycles change after a workspace was allocated (nx_batch_rhs is legal before
+// either), so the allocated bytes are checked, not the column count alone.
+bool batch_fits(const nx_network* h, int chunk) {
+  return h->bws != nullptr && chunk <= h->bws_cap && batch_bytes(h, h->bws_cap) <= h->bws_bytes;
+}
+
+// The chunk size of this call and a workspace that holds it: NXHIP_BATCH_CHUNK (read per
+// call) or the largest of <= kBatchChunkMax whose workspace fits kBatchMemShare of the free
+// device memory; a failed allocation halves it down to 1.
+int batch_workspace(nx_network* h, int n_cols, int* chunk_out) {
+  int chunk = std::min(n_cols, kBatchChunkMax);
+  const char* e = std::getenv("NXHIP_BATCH_CHUNK");
+  if (e != nullptr && std::atoi(e) > 0) {
+    chunk = std::min(std::min(std::atoi(e), kBatchChunkEnvMax), n_cols);
+  } else if (!batch_fits(h, chunk)) {
+    size_t fr = 0, tot = 0;
+    HIPCALL(hipMemGetInfo(&fr, &tot));
+    const double room = kBatchMemShare * (double)fr;
+    while (chunk > 1 && (double)batch_bytes(h, chunk) > room) --chunk;
+  }
+  if (!batch_fits(h, chunk)) {
+    HIPCALL(hipStreamSynchronize(h->stream));
+    if (h->bws) (void)hipFree(h->bws);
+    h->bws = nullptr;
+    h->bws_cap = 0;
+    h->bws_bytes = 0;
+    for (;;) {
+      if (hipMalloc(&h->bws, batch_bytes(h, chunk)) == hipSuccess) break;
+      (void)hipGetLastError();
+      h->bws = nullptr;
+      if (chunk == 1) return fail(NX_ERR_HIP, "nx_batch_solve: no memory for one column's workspace");
+      chunk = std::max(1, chunk / 2);
+    }
+    h->bws_cap = chunk;
+    h->bws_bytes = batch_bytes(h, chunk);
+  }
+  *chunk_out = chunk;
+  return NX_OK;
+}
+
+// The chunk's inputs to the device and its right-hand sides into ws.B (one launch).
+int batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const double* edge_bc,
+                    const double* edge_f, const double* f_const) {
+  const int64_t E = h->E;
+  HIPCALL(hipMemcpyAsync(ws.bc, edge_bc + (int64_t)c0 * 2 * E, sizeof(double) * 2 * E * nc,
+                         hipMemcpyHostToDevice, h->stream));
+  const double* ef = nullptr;
+  int64_t ef_ld = 0;
+  if (edge_f) {
+    HIPCALL(hipMemcpyAsync(ws.ef, edge_f + (int64_t)c0 * E, sizeof(double) * E * nc,
+                           hipMemcpyHostToDevice, h->stream));
+    ef = ws.ef;
+    ef_ld = E;
+  } else if (f_const) {
+    HIPCALL(hipMemcpyAsync(ws.fc, f_const + c0, sizeof(double) * nc, hipMemcpyHostToDevice,
+                           h->stream));
+  } else if (h->edge_f) {  // the handle's own per-edge source, for every column
+    ef = h->edge_f;
+  } else {
+    std::vector<double> fc((size_t)nc, h->f);
+    HIPCALL(hipMemcpyAsync(ws.fc, fc.data(), sizeof(double) * nc, hipMemcpyHostToDevice,
+                           h->stream));
+    HIPCALL(hipStreamSynchronize(h->stream));  // (fc leaves scope)
+  }
+  const int64_t nthr = E * (int64_t)(h->N + 1) + h->B;
+  hipLaunchKernelGGL(k_b_rhs, dim3(grid_of(nthr, kBlock)), dim3(kBlock), 0, h->stream,
+                     EdgeArgs{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N}, h->B, nc, ws.bc, ef,
+                     ef_ld, ws.fc, ws.B, ws.cols.ld);
+  HIPCALL(hipGetLastError());
+  h->b_launches += 1;
+  return NX_OK;
+}
+
+// out = A^{-1} in on nc columns (list: which, device; null: the first nc): the up, top and
+// down sweeps, then the cycle correction.
+template <int W, int CPL>
+void batch_sweeps_wc(nx_network* h, const BatchWs& ws, const int* list, int nc, const double* in,
+                     double* out) {
+  PcArgs pa = h->pa;
+  pa.accum = 0;
+  pa.fres = 0;
+  pa.topdown = 0;
+  BatchCols bc = ws.cols;
+  bc.list = list;
+  if (h->pc_jobs > 0) {
+    hipLaunchKernelGGL((k_b_up<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, h->stream, pa,
+                       bc, in);
+    h->b_launches += 1;
+  }
+  hipLaunchKernelGGL(k_b_top, dim3(nc), dim3(kTopThreads), 0, h->stream, pa, bc, in, out);
+  h->b_launches += 1;
+  if (h->pc_jobs > 0) {
+    hipLaunchKernelGGL((k_b_down<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, h->stream,
+                       pa, bc, in, out);
+    h->b_launches += 1;
+  }
+  if (h->n_cyc > 0) {
+    const int m = 2 * h->n_cyc;
+    hipLaunchKernelGGL(k_b_cyc_w, dim3(grid_of(m, 256), nc), dim3(256), sizeof(double) * m,
+                       h->stream, out, bc.ld, list, h->d_cyc_rows, m, h->cyc_cinv, ws.cw);
+    hipLaunchKernelGGL(k_b_cyc_fix, dim3(grid_of(h->n_own, kBlock), nc), dim3(kBlock), 0,
+                       h->stream, out, bc.ld, list, h->cyc_z, h->n_col, ws.cw, m, h->n_own);
+    h->b_launches += 2;
+  }
+}
+int batch_sweeps(nx_network* h, const BatchWs& ws, const int* list, int nc, const double* in,
+                 double* out) {
+  switch (h->pc_variant) {
+    case 0: batch_sweeps_wc<16, 1>(h, ws, list, nc, in, out); break;
+    case 1: batch_sweeps_wc<16, 2>(h, ws, list, nc, in, out); break;
+    case 2: batch_sweeps_wc<16, 4>(h, ws, list, nc, in, out); break;
+    case 3: batch_sweeps_wc<64, 2>(h, ws, list, nc, in, out); break;
+    case 5: batch_sweeps_wc<8, 2>(h, ws, list, nc, in, out); break;
+    case 6: batch_sweeps_wc<4, 4>(h, ws, list, nc, in, out); break;
+    case 7: batch_sweeps_wc<8, 4>(h, ws, list, nc, in, out); break;
+    case 8: batch_sweeps_wc<64, 8>(h, ws, list, nc, in, out); break;
+    case 9: batch_sweeps_wc<64, 16>(h, ws, list, nc, in, out); break;
+    default: batch_sweeps_wc<64, 4>(h, ws, list, nc, in, out); break;
+  }
+  HIPCALL(hipGetLastError());
+  return NX_OK;
+}
+
+// R = B - A X and the two norms of nc columns; stats (host, 2 per workspace column) filled
+// for them after one synchronisation.
+int batch_residual(nx_network* h, const BatchWs& ws, const int* list, int nc,
+                   std::vector<double>& stats, int cap) {
+  hipLaunchKernelGGL(k_b_res, dim3(ws.nblk), dim3(kBlock), 0, h->stream, csr_of(h), ws.X, ws.B,
+                     ws.R, ws.cols.ld, list, nc, ws.part, ws.nblk);
+  hipLaunchKernelGGL(k_b_norms, dim3(nc), dim3(kReduceThreads), 0, h->stream, ws.part, ws.nblk,
+                     list, ws.stats);
+  HIPCALL(hipGetLastError());
+  h->b_launches += 2;
+  stats.resize(2 * (size_t)cap);
+  HIPCALL(hipMemcpyAsync(stats.data(), ws.stats, sizeof(double) * 2 * cap, hipMemcpyDeviceToHost,
+                         h->stream));
+  HIPCALL(hipStreamSynchronize(h->stream));
+  return NX_OK;
+}
+
+double batch_relres(double rr, double bb) { return bb > 0.0 ? std::sqrt(rr / bb) : 0.0; }
+
+// What a build of the cycle correction or a fallback solve borrows from the handle.
+struct BatchSaved {
+  MrState last;
+  int last_solver, last_dir_path;
+  bool need_r, last_graph, have_rhs;
+};
+int batch_save(nx_network* h, const BatchWs& ws, BatchSaved* s, bool with_rhs) {
+  const int64_t n = h->n_col;
+  HIPCALL(hipMemcpyAsync(ws.save, h->x, sizeof(double) * n, hipMemcpyDeviceToDevice, h->stream));
+  HIPCALL(hipMemcpyAsync(ws.save + n, h->tmp, sizeof(double) * n, hipMemcpyDeviceToDevice, h->stream));
+  if (with_rhs)
+    HIPCALL(hipMemcpyAsync(ws.save + 2 * n, h->rhs, sizeof(double) * n, hipMemcpyDeviceToDevice,
+                           h->stream));
+  s->last = *h->h_last;
+  s->last_solver = h->last_solver;
+  s->last_dir_path = h->last_dir_path;
+  s->need_r = h->need_r;
+  s->last_graph = h->last_graph;
+  s->have_rhs = h->have_rhs;
+  return NX_OK;
+}
+int batch_restore(nx_network* h, const BatchWs& ws, const BatchSaved& s, bool with_rhs) {
+  const int64_t n = h->n_col;
+  HIPCALL(hipMemcpyAsync(h->x, ws.save, sizeof(double) * n, hipMemcpyDeviceToDevice, h->stream));
+  HIPCALL(hipMemcpyAsync(h->tmp, ws.save + n, sizeof(double) * n, hipMemcpyDeviceToDevice, h->stream));
+  if (with_rhs)
+    HIPCALL(hipMemcpyAsync(h->rhs, ws.save + 2 * n, sizeof(double) * n, hipMemcpyDeviceToDevice,
+                           h->stream));
+  HIPCALL(hipStreamSynchronize(h->stream));
+  *h->h_last = s.last;
+  h->last_solver = s.last_solver;
+  h->last_dir_path = s.last_dir_path;
+  h->need_r = s.need_r;
+  h->last_graph = s.last_graph;
+  h->have_rhs = s.have_rhs;
+  return NX_OK;
+}
+
+// One column through the single-column path (nx_solve's: the direct solve with its
+// refinement, then MINRES): the column's assembled rhs (ws.B) stands in for the handle's,
+// which is put back with its x, tmp and published state (no assembly runs, so the handle's
+// coefficients are not involved). The solution goes to ws.X's column.
+int batch_fallback(nx_network* h, const BatchWs& ws, int wcol, double rtol, int32_t* it,
+                   double* relres, int32_t* conv) {
+  const int64_t n = h->n_col;
+  BatchSaved sv{};
+  CHECK(batch_save(h, ws, &sv, true));
+  HIPCALL(hipMemcpyAsync(h->rhs, ws.B + wcol * n, sizeof(double) * n, hipMemcpyDeviceToDevice,
+                         h->stream));
+  h->have_rhs = true;
+  nx_network* hs[1] = {h};
+  const int rc = solve_team(Team{hs, 1, nullptr}, rtol, 50000, 4, it, relres, conv);
+  if (rc == NX_OK)
+    HIPCALL(hipMemcpyAsync(ws.X + wcol * n, h->x, sizeof(double) * n, hipMemcpyDeviceToDevice,
+                           h->stream));
+  CHECK(batch_restore(h, ws, sv, true));
+  return rc;
+}
+
+int batch_check_args(nx_network* h, int32_t n_cols, const double* edge_bc, const double* out) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (n_cols < 1) return fail(NX_ERR_ARG, "n_cols must be >= 1");
+  if (!edge_bc || !out) return fail(NX_ERR_ARG, "edge_bc / out is NULL");
+  return NX_OK;
+}
+
+}  // namespace
+
+NX_API int nx_batch_supported(nx_network_t* h, int32_t* ok) {
+  if (!h || !ok) return fail(NX_ERR_ARG, "null argument");
+  *ok = batch_ok(h) ? 1 : 0;
+  return NX_OK;
+}
+
+NX_API int nx_get_batch_info(nx_network_t* h, int32_t* launches, int32_t* refined,
+                             int32_t* fallback, int32_t* chunk) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (launches) *launches = h->b_launches;
+  if (refined) *refined = h->b_refined;
+  if (fallback) *fallback = h->b_fallback;
+  if (chunk) *chunk = h->b_chunk;
+  return NX_OK;
+}
+
+NX_API int nx_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                        const double* edge_f, const double* f_const, double* out) {
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  CHECK(batch_check_args(h, n_cols, edge_bc, out));
+  if (h->fe || proc_rank(h) || h->group || h->nranks != 1 || h->n_ghost != 0 || h->E < 1)
+    return fail(NX_ERR_STATE, "nx_batch_rhs: a P1/DG0 handle on one rank");
+  CHECK(set_device(h));
+  int chunk = 0;
+  CHECK(batch_workspace(h, n_cols, &chunk));
+  const BatchWs ws = batch_carve(h, h->bws_cap);
+  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
+    const int nc = std::min(chunk, n_cols - c0);
+    CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
+    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * h->n_own, ws.B, sizeof(double) * h->n_own * nc,
+                           hipMemcpyDeviceToHost, h->stream));
+    HIPCALL(hipStreamSynchronize(h->stream));
+  }
+  return NX_OK;
+}
+
+NX_API int nx_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                          const double* edge_f, const double* f_const, double rtol, int32_t order,
+                          double* out, int32_t* iters, double* relres, int32_t* converged) {
+  // (what the call makes current first is counted in its launches: a pending assembly, the
+  // lumped mass, the cycle correction -- a caller sees that nothing current is rebuilt)
+  const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  CHECK(batch_check_args(h, n_cols, edge_bc, out));
+  if (!batch_ok(h))
+    return fail(NX_ERR_STATE, "nx_batch_solve: the batched direct solve does not apply to this "
+                              "handle (nx_batch_supported)");
+  if (!h->have_lhs) return fail(NX_ERR_STATE, "assemble the matrix before nx_batch_solve");
+  if (order != 0 && !h->out_idx) return fail(NX_ERR_STATE, "nx_set_output_map first");
+  CHECK(set_device(h));
+  h->b_refined = h->b_fallback = 0;
+  h->b_launches = made_current + (h->dq_stale ? 1 : 0);
+  int chunk = 0;
+  CHECK(batch_workspace(h, n_cols, &chunk));
+  h->b_chunk = chunk;
+  const BatchWs ws = batch_carve(h, h->bws_cap);
+  const int cap = h->bws_cap;
+  // what the sweeps read besides the right-hand side, current for the handle's matrix: the
+  // lumped mass, and on a graph with cycles the correction (rebuilt only for a new matrix;
+  // its solves borrow the handle's x, tmp and published state, put back afterwards)
+  CHECK(ensure_dq(h));
+  if (h->n_cyc > 0 && h->cyc_version != h->lhs_version) {
+    BatchSaved sv{};
+    CHECK(batch_save(h, ws, &sv, false));
+    const int rc = cyc_build(h);
+    CHECK(batch_restore(h, ws, sv, false));
+    CHECK(rc);
+    h->b_launches += cyc_build_launches(h);
+  }
+  const int64_t n = h->n_own, ld = ws.cols.ld;
+  std::vector<double> stats;
+  std::vector<int> redo, fall;
+  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
+    const int nc = std::min(chunk, n_cols - c0);
+    CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
+    CHECK(batch_sweeps(h, ws, nullptr, nc, ws.B, ws.X));
+    CHECK(batch_residual(h, ws, nullptr, nc, stats, cap));
+    redo.clear();
+    for (int c = 0; c < nc; ++c) {
+      const double rr = stats[2 * c], bb = stats[2 * c + 1];
+      const double r = batch_relres(rr, bb);
+      if (iters) iters[c0 + c] = 1;
+      if (relres) relres[c0 + c] = r;
+      if (converged) converged[c0 + c] = (bb == 0.0 || r <= rtol) ? 1 : 0;
+      if (bb > 0.0 && !(r <= rtol)) redo.push_back(c);
+    }
+    fall.clear();
+    if (!redo.empty()) {  // one refinement pass over the failing columns only: x += A^{-1} r
+      const int nr = (int)redo.size();
+      HIPCALL(hipMemcpyAsync(ws.list, redo.data(), sizeof(int) * nr, hipMemcpyHostToDevice,
+                             h->stream));
+      CHECK(batch_sweeps(h, ws, ws.list, nr, ws.R, ws.D));
+      hipLaunchKernelGGL(k_b_add, dim3(grid_of(n, kBlock), nr), dim3(kBlock), 0, h->stream, ws.X,
+                         ws.D, ld, ws.list, n);
+      h->b_launches += 1;
+      CHECK(batch_residual(h, ws, ws.list, nr, stats, cap));
+      h->b_refined += nr;
+      for (int c : redo) {
+        const double r = batch_relres(stats[2 * c], stats[2 * c + 1]);
+        if (iters) iters[c0 + c] = 2;
+        if (relres) relres[c0 + c] = r;
+        if (converged) converged[c0 + c] = r <= rtol ? 1 : 0;
+        if (!(r <= rtol)) fall.push_back(c);
+      }
+    }
+    for (int c : fall) {  // still above rtol: the single-column path (with its MINRES)
+      int32_t it = 0, cv = 0;
+      double r = 0.0;
+      CHECK(batch_fallback(h, ws, c, rtol, &it, &r, &cv));
+      h->b_fallback += 1;
+      if (iters) iters[c0 + c] = it;
+      if (relres) relres[c0 + c] = r;
+      if (converged) converged[c0 + c] = cv;
+    }
+    const double* src = ws.X;
+    if (order != 0) {
+      hipLaunchKernelGGL(k_b_gather, dim3(grid_of(n, kBlock), nc), dim3(kBlock), 0, h->stream, ws.X,
+                         ld, h->out_idx, n, ws.D);
+      HIPCALL(hipGetLastError());
+      h->b_launches += 1;
+      src = ws.D;
+    }
+    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * n, src, sizeof(double) * n * nc,
+                           hipMemcpyDeviceToHost, h->stream));
+    HIPCALL(hipStreamSynchronize(h->stream));
+    for (int c = 0; c < nc; ++c)  // b = 0: x = 0 exactly (no division by ||b||)
+      if (stats[2 * c + 1] == 0.0) std::fill_n(out + (int64_t)(c0 + c) * n, n, 0.0);
+  }
+  return NX_OK;
 }
 
 NX_API int nx_get_solution(nx_network_t* h, double* xo) {

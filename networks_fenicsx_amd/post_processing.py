@@ -25,7 +25,7 @@ from .fem import Function, FunctionSpace
 from .mesh import NetworkMesh
 
 __all__ = ["extract_global_flux", "export_functions", "export_submeshes", "integrate_dg1",
-           "write_vtu"]
+           "terminal_conductance", "write_vtu"]
 
 
 def extract_global_flux(graph_mesh: NetworkMesh, functions: list[Function]) -> Function:
@@ -49,6 +49,51 @@ def extract_global_flux(graph_mesh: NetworkMesh, functions: list[Function]) -> F
     nodes = np.arange(N)[:, None] * degree + np.arange(degree + 1)[None, :]  # (N, k+1)
     g.x.array[:] = vals[:, nodes].ravel()
     return g
+
+
+def terminal_conductance(solver) -> tuple[np.ndarray, np.ndarray]:
+    """The terminals' conductance (Dirichlet-to-Neumann) matrix of the network, ``(nodes, C)``.
+
+    ``nodes``: ``boundary_out_nodes`` then ``boundary_in_nodes``. Scenario ``t`` has f = 0 and
+    p_bc = 1 at terminal ``nodes[t]`` alone; all of them go through one
+    :meth:`Solver.solve_many`. ``C[s, t]`` is the signed end flux at terminal ``s`` under
+    scenario ``t``: ``+q_N`` where ``s`` is its edge's target, ``-q_0`` where it is its edge's
+    source -- the flow leaving the network there, so with the reference's sign convention of
+    the weak boundary terms (``assembly.py:258-260``) the diagonal is positive, C is symmetric
+    and its columns sum to zero. ``R`` is the last ``compute_forms``'. The reference has no
+    counterpart (it would run one KSP solve per terminal, ``solver.py:107-135``)."""
+    asm = solver.assembler
+    mesh = asm.network
+    nodes = np.concatenate([np.asarray(mesh.boundary_out_nodes, dtype=np.int64),
+                            np.asarray(mesh.boundary_in_nodes, dtype=np.int64)])
+    T = nodes.size
+    pbc = np.zeros((T, mesh.num_nodes), dtype=np.float64)
+    pbc[np.arange(T), nodes] = 1.0
+    res = solver.solve_many(pbc, f=np.zeros(T))
+    # position of every edge's q_0 in a row of res.x (the flux blocks come first, one per
+    # colour, kN + 1 values per edge, source side first)
+    per = asm.degrees[0] * mesh.N + 1
+    src, dst = mesh.edges
+    q0 = np.full(src.size, -1, dtype=np.int64)
+    off = 0
+    for V in asm.flux_spaces:
+        edges = np.asarray(V.edges, dtype=np.int64)
+        q0[edges] = off + per * np.arange(edges.size)
+        off += per * edges.size
+    pos = np.empty(T, dtype=np.int64)
+    sign = np.empty(T, dtype=np.float64)
+    for i, s in enumerate(nodes):
+        e_t, e_s = np.flatnonzero(dst == s), np.flatnonzero(src == s)
+        if e_t.size + e_s.size != 1:
+            raise ValueError(f"terminal node {int(s)} must have exactly one edge")
+        if e_t.size:
+            pos[i], sign[i] = q0[e_t[0]] + per - 1, 1.0
+        else:
+            pos[i], sign[i] = q0[e_s[0]], -1.0
+    if np.any(pos < 0):
+        raise ValueError("a terminal's edge is not among this rank's flux functions")
+    C = sign[:, None] * res.x[:, pos].T
+    return nodes, C
 
 
 def integrate_dg1(graph_mesh: NetworkMesh, g: Function) -> tuple[float, float]:

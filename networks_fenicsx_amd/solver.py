@@ -40,6 +40,7 @@ solve ran last (``"direct"`` or ``"minres"``).
 
 from __future__ import annotations
 
+import os
 import sys
 import typing
 
@@ -49,7 +50,7 @@ from . import _lib
 from .assembly import DeviceMatrix, DeviceVector, HydraulicNetworkAssembler
 from .timing import timed
 
-__all__ = ["Solver", "KSPInfo"]
+__all__ = ["Solver", "KSPInfo", "BatchResult"]
 
 _DEFAULTS = {
     "ksp_type": "preonly",
@@ -85,6 +86,45 @@ class KSPInfo:
 
     def destroy(self) -> None:
         return None
+
+
+# solve_many: a single scenario on more rows than this takes the sequential path
+BATCH_SINGLE_MAX_ROWS = 1 << 18
+
+
+class BatchResult:
+    """What :meth:`Solver.solve_many` returns.
+
+    ``x``: ``(B, n)``, every row in the reference's block order -- the concatenated functions
+    ``[flux_color_0 .., pressure, global_flux]`` that ``solve()`` returns;
+    ``iterations``, ``residual_norms``, ``converged``: ``(B,)`` each; ``path``: ``"batched"``
+    (``nx_batch_solve``) or ``"sequential"`` (the per-scenario loop); ``info``: the dict of
+    ``nx_get_batch_info`` (launches, refined, fallback, chunk)."""
+
+    def __init__(self, assembler, x, iterations, residual_norms, converged, path, info):
+        self._assembler = assembler
+        self.x = x
+        self.iterations = np.asarray(iterations)
+        self.residual_norms = np.asarray(residual_norms)
+        self.converged = np.asarray(converged, dtype=bool)
+        self.path = path
+        self.info = dict(info)
+
+    def __len__(self) -> int:
+        return self.x.shape[0]
+
+    def functions(self, j: int) -> list:
+        """The function list of scenario ``j`` (new functions, filled by
+        ``scatter_solution``)."""
+        from .fem import Function
+
+        asm = self._assembler
+        names = [f"flux_color_{i}" for i in range(len(asm.flux_spaces))]
+        names += ["pressure", "global_flux"]
+        fns = [Function(V, name=nm) for V, nm in zip(asm.function_spaces, names)]
+        xdev = np.empty(self.x.shape[1], dtype=np.float64)  # block order -> device layout
+        xdev[np.concatenate([asm._block_rows(i) for i in range(len(fns))])] = self.x[j]
+        return asm.scatter_solution(xdev, fns)
 
 
 def _truthy(v) -> bool:
@@ -168,12 +208,7 @@ class Solver:
         if self._closed:
             raise RuntimeError("the solver has been destroyed")
         h = self.assembler.handle
-        if self.assembler.preconditioned != self._pc:
-            self.assembler.set_preconditioner(self._pc)
-        if self.assembler.preconditioned and h.pc_exact() != self._pc_exact:
-            h.set_pc_exact(self._pc_exact)
-        self.assembler.set_direct(self._direct and (self.assembler.preconditioned
-                                                    or self.assembler.fe_direct_available))
+        self._configure()
         ce = self._check_every or (4 if self.assembler.preconditioned else 32)
         it, relres, conv = h.solve(self._rtol, self._maxit, ce)
         self._ksp.iterations, self._ksp.residual_estimate, self._ksp.converged = it, relres, conv
@@ -189,6 +224,82 @@ class Solver:
                 f"MINRES did not converge: {it} iterations, relative residual {relres:.3e} "
                 f"> rtol {self._rtol:.1e}")
         return self.assembler.solution_functions(functions)
+
+    def _configure(self) -> None:
+        """The handle in the state this solver's options ask for (as :meth:`solve` does)."""
+        if self.assembler.preconditioned != self._pc:
+            self.assembler.set_preconditioner(self._pc)
+        h = self.assembler.handle
+        if self.assembler.preconditioned and h.pc_exact() != self._pc_exact:
+            h.set_pc_exact(self._pc_exact)
+        self.assembler.set_direct(self._direct and (self.assembler.preconditioned
+                                                    or self.assembler.fe_direct_available))
+
+    @timed("nxfx:Solver:solve_many")
+    def solve_many(self, p_bc, f=None) -> "BatchResult":
+        """Solve B boundary / source scenarios against the matrix of the last
+        ``compute_forms`` (its ``R``): ``p_bc`` a sequence of B items, each in any form
+        ``compute_forms`` accepts, or an array ``(B, num_nodes)``; ``f`` None (the last
+        ``compute_forms``' source), B scalars or ``(B, num_edges)`` values in ``graph.edges()``
+        order.
+
+        Where the handle supports it (``nx_batch_supported``: P1/DG0, one rank, the direct
+        solve) the scenarios go through ``nx_batch_solve`` in one batched pass
+        (``path == "batched"``). Otherwise -- general degrees, ``ksp_type="minres"``,
+        ``pc_type="none"``, the lumped mass, the global-memory sweeps, or ``NXHIP_BATCH=0`` --
+        the per-scenario loop runs (``"sequential"``): the rhs coefficients alone are set (R
+        is never uploaded again), then rhs assembly, solve, gather; afterwards the coefficients
+        and the rhs of the last ``compute_forms`` are put back. The reference has no
+        counterpart (one KSP solve per call, ``solver.py:107-135``)."""
+        if self._closed:
+            raise RuntimeError("the solver has been destroyed")
+        asm = self.assembler
+        if getattr(asm, "_coefficients", None) is None:
+            raise RuntimeError("compute_forms() must be called before solve_many()")
+        if getattr(asm, "_nranks", 1) > 1:
+            raise NotImplementedError("solve_many runs on one rank; with several ranks loop "
+                                      "over compute_forms / assemble / solve")
+        edge_bc, edge_f, f_const = asm.scenario_coefficients(p_bc, f)
+        B = edge_bc.shape[0]
+        h = asm.handle
+        self._configure()
+        if not asm.lhs_current:  # the matrix of the last compute_forms (its R), values only
+            asm.assemble(assemble_lhs=True, assemble_rhs=False)
+        # the documented rule (DESIGN.md, "Batched scenarios"): one scenario on a large system
+        # has nothing to batch and measured no gain over the single solve (1.03 M rows:
+        # 0.98x; 16 k rows: 1.44x), so it takes the loop; NXHIP_BATCH=1 overrides the rule,
+        # NXHIP_BATCH=0 forces the loop
+        want = os.environ.get("NXHIP_BATCH", "")
+        worth = want == "1" or not (B == 1 and h.n_rows > BATCH_SINGLE_MAX_ROWS)
+        batched = want != "0" and worth and h.batch_supported()
+        if batched:
+            x, it, rr, conv = h.batch_solve(edge_bc, edge_f, f_const, self._rtol, blocks=True)
+            info = h.batch_info()
+        else:
+            x = h.batch_output(B)  # page-locked and reused, as the batched path's
+            it = np.zeros(B, dtype=np.int32)
+            rr = np.zeros(B, dtype=np.float64)
+            conv = np.zeros(B, dtype=bool)
+            ce = self._check_every or (4 if asm.preconditioned else 32)
+            try:
+                for j in range(B):
+                    asm.set_rhs_coefficients(edge_bc[j],
+                                             None if f_const is None else float(f_const[j]),
+                                             None if edge_f is None else edge_f[j])
+                    h.assemble(False, True)
+                    it[j], rr[j], conv[j] = h.solve(self._rtol, self._maxit, ce)
+                    h.solution_blocks(x[j])
+            finally:
+                asm.restore_rhs_coefficients()
+                h.assemble(False, True)
+            info = {"launches": 0, "refined": 0, "fallback": 0, "chunk": 1}
+        res = BatchResult(asm, x, it, rr, conv, "batched" if batched else "sequential", info)
+        if self._raise and not conv.all():
+            bad = np.flatnonzero(~conv)
+            raise _lib.NxNotConverged(
+                f"solve_many: columns {bad.tolist()} did not converge (relative residuals "
+                f"{rr[bad].tolist()} > rtol {self._rtol:.1e})")
+        return res
 
     def solution_vector(self) -> np.ndarray:
         """Device-layout solution (owned DoFs of this rank)."""
