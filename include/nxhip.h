@@ -470,6 +470,54 @@ int nx_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc, const d
 int nx_get_batch_info(nx_network_t* h, int32_t* launches, int32_t* refined, int32_t* fallback,
                       int32_t* chunk);
 
+/*
+ * Adjoint gradients of an observed-row objective with respect to every edge's R, every
+ * boundary value and every edge's source, for n_cols scenarios, in two batched direct solves;
+ * no solution leaves the device (the reference has no counterpart). Per scenario j over the
+ * observed device rows r_i (distinct) with weights w_i:
+ *   kind 1 (least squares)  J_j = 1/2 sum_i w_i (x_j[r_i] - d_ji)^2
+ *   kind 0 (linear)         J_j = sum_i w_i x_j[r_i]
+ * The device system is symmetric (its pressure rows are the reference's, negated), so the
+ * adjoint system is the same matrix with the right-hand side c_j = dJ_j/dx -- w_i
+ * (x_j[r_i] - d_ji), or w_i -- and goes through the same batched sweeps, cycle correction,
+ * residual check, refinement pass and single-column fallback as nx_batch_solve's columns;
+ * c = 0 gives a zero adjoint, converged. Kind 0 has one adjoint column for all scenarios: it
+ * is solved once per call. With mu = A^{-1} c and x the forward solution (both stay resident
+ * in the workspace, which grows by two vectors and 4 E + 1 outputs per column):
+ *   grad_R[j, e]     = -sum_k h_k/6 (2 mu_k x_k + mu_k x_{k+1} + mu_{k+1} x_k + 2 mu_{k+1} x_{k+1})
+ *                      over the edge's cells (its flux vertex values: the R = 1 P1 mass)
+ *   grad_bc[j, e, .] = mu at the edge's q_0 / q_N row: the derivative w.r.t. edge_bc[j, e, .]
+ *   grad_f[j, e]     = -sum_k h_k mu[p_k]: the derivative w.r.t. the edge's source
+ * (the derivatives w.r.t. what the caller passes: edge slots, edge_bc with the sign
+ * nx_set_coefficients documents).
+ *   edge_bc / edge_f / f_const / rtol   as nx_batch_solve
+ *   obs_rows, obs_w   n_obs each; obs_d  n_cols x n_obs (NULL for kind 0)
+ *   value   n_cols;  grad_R  n_cols x E;  grad_bc  n_cols x E x 2 or NULL;  grad_f  n_cols x E
+ *   or NULL;  iters / relres / converged  2 x n_cols each or NULL: the forward columns, then
+ *   the adjoint columns (kind 0: its one column's figures for every scenario)
+ * Supported exactly where nx_batch_supported says 1, else NX_ERR_STATE. It makes current what
+ * nx_batch_solve makes current and leaves the handle's coefficients, rhs, x, tmp, published
+ * state and snapshots as they were; chunks as nx_batch_solve (NXHIP_BATCH_CHUNK, <= 64, a
+ * quarter of the free memory with the larger columns). A column's bits do not depend on the
+ * other columns, its position, n_cols or the chunk size. Per chunk one device-to-host copy per
+ * output array, straight into the caller's memory (page-locked memory makes each one DMA):
+ * (4 E + 1) doubles per column in all.
+ * NX_ERR_ARG: n_cols < 1, n_obs < 1, a row outside [0, n_rows), duplicate rows, an unknown
+ * kind, kind 1 without obs_d, NULL edge_bc / value / grad_R / obs_rows / obs_w.
+ *
+ * nx_get_batch_info then reports this call (refined: forward plus adjoint columns). Steady
+ * launches when nothing is refined, with S = 5 on a forest (up, top, down, residual, norms)
+ * and S = 7 with cycles (the correction's two kernels):
+ *   kind 1   per chunk  1 (rhs) + S + 1 (k_b_obs) + S + 1 (k_b_edge_form): 13 / 17
+ *   kind 0   per call   1 (k_b_obs) + S: 6 / 8;  per chunk  1 + S + 1 + 1: 8 / 10
+ * and 6 / 8 more for each refinement pass, as nx_batch_solve.
+ */
+int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                      const double* edge_f, const double* f_const, double rtol, int32_t kind,
+                      int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
+                      const double* obs_d, double* value, double* grad_R, double* grad_bc,
+                      double* grad_f, int32_t* iters, double* relres, int32_t* converged);
+
 /* Copy the owned part of the solution / rhs to the host (n_rows doubles). */
 int nx_get_solution(nx_network_t* h, double* x);
 int nx_get_rhs(nx_network_t* h, double* b);

@@ -55,6 +55,8 @@ _SIGS = {
     "nx_batch_solve": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _pd, _pi32, _pd, _pi32]),
     "nx_batch_rhs": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd]),
     "nx_get_batch_info": (C.c_int, [_h, _pi32, _pi32, _pi32, _pi32]),
+    "nx_batch_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd, _pd,
+                                    _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
     "nx_get_solution": (C.c_int, [_h, _pd]),
     "nx_get_rhs": (C.c_int, [_h, _pd]),
     "nx_set_output_map": (C.c_int, [_h, _i64, _pi32]),
@@ -442,8 +444,46 @@ class Handle:
                                  _ptr(fc, C.c_double), _ptr(out, C.c_double)))
         return out
 
+    def batch_gradient(self, edge_bc, edge_f=None, f_const=None, rtol: float = 1e-12, *,
+                       rows, weights, data=None):
+        """``nx_batch_gradient``: ``(value (B,), grad_R (B, E), grad_bc (B, E, 2), grad_f
+        (B, E), iterations, relres, converged -- (B, 2) each: forward, adjoint)``. ``rows``:
+        distinct device rows; ``data`` None: the linear objective, else ``(B, n_obs)``."""
+        B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != rows.size:
+            raise ValueError("one weight per observed row")
+        d = None if data is None else np.ascontiguousarray(data, dtype=np.float64)
+        if d is not None and d.shape != (B, rows.size):
+            raise ValueError("data must be (B, n_obs)")
+        E = self.n_edges
+        # one page-locked buffer for the four outputs (every copy from the device is one DMA;
+        # pooled per batch size beside batch_output's, reused once the views are dropped)
+        pools = self.__dict__.setdefault("_batch_pools", {})
+        pool = pools.pop(("gradient", B), None)
+        if pool is None:
+            pool = PinnedPool(B * (4 * E + 1))
+            while len(pools) >= self._BATCH_POOLS:
+                pools.pop(next(iter(pools))).close()
+        pools[("gradient", B)] = pool
+        buf = pool.take()
+        value, gR = buf[:B], buf[B:B + B * E].reshape(B, E)
+        gf = buf[B + B * E:B + 2 * B * E].reshape(B, E)
+        gbc = buf[B + 2 * B * E:].reshape(B, E, 2)
+        it = np.zeros((2, B), dtype=np.int32)
+        rr = np.zeros((2, B), dtype=np.float64)
+        cv = np.zeros((2, B), dtype=np.int32)
+        check(lib().nx_batch_gradient(
+            self.ptr, B, _ptr(bc, C.c_double), _ptr(ef, C.c_double), _ptr(fc, C.c_double),
+            float(rtol), 0 if d is None else 1, int(rows.size), _ptr(rows, C.c_int32),
+            _ptr(w, C.c_double), _ptr(d, C.c_double), _ptr(value, C.c_double),
+            _ptr(gR, C.c_double), _ptr(gbc, C.c_double), _ptr(gf, C.c_double),
+            _ptr(it, C.c_int32), _ptr(rr, C.c_double), _ptr(cv, C.c_int32)))
+        return value, gR, gbc, gf, it.T.copy(), rr.T.copy(), cv.T.astype(bool)
+
     def batch_info(self) -> dict:
-        """``nx_get_batch_info`` of the last :meth:`batch_solve`."""
+        """``nx_get_batch_info`` of the last :meth:`batch_solve` or :meth:`batch_gradient`."""
         v = [C.c_int32() for _ in range(4)]
         check(lib().nx_get_batch_info(self.ptr, *[C.byref(x) for x in v]))
         return dict(zip(("launches", "refined", "fallback", "chunk"), (int(x.value) for x in v)))

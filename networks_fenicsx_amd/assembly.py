@@ -104,6 +104,26 @@ def edge_boundary_rhs(mesh: NetworkMesh, edge_ids: np.ndarray, pbc: np.ndarray) 
     return edge_bc
 
 
+def edge_boundary_rhs_adjoint(mesh: NetworkMesh, edge_ids: np.ndarray):
+    """The transpose of :func:`edge_boundary_rhs` as a gather: ``(index, sign)``, one entry
+    per node, such that derivatives ``g_bc`` ``(B, E, 2)`` with respect to the flux end rows'
+    rhs (local edge order) give the derivatives with respect to the nodal boundary pressure as
+    ``np.take(g_bc.reshape(B, 2 E), index, axis=1) * sign`` -- ``-`` at a root's ``q_0``, ``+``
+    at a leaf's ``q_N``, sign 0 off the boundary nodes (a boundary node has one edge)."""
+    src, dst = mesh.edges
+    s, d = src[edge_ids], dst[edge_ids]
+    leaf = np.zeros(mesh.num_nodes, dtype=bool)
+    leaf[mesh.boundary_in_nodes] = True
+    root = np.zeros(mesh.num_nodes, dtype=bool)
+    root[mesh.boundary_out_nodes] = True
+    index = np.zeros(mesh.num_nodes, dtype=np.int64)
+    sign = np.zeros(mesh.num_nodes, dtype=np.float64)
+    er, el = np.flatnonzero(root[s]), np.flatnonzero(leaf[d])
+    index[s[er]], sign[s[er]] = 2 * er, -1.0
+    index[d[el]], sign[d[el]] = 2 * el + 1, 1.0
+    return index, sign
+
+
 def batch_coefficients(mesh: NetworkMesh, edge_ids: np.ndarray, p_bc, f=None):
     """The rhs coefficients of B scenarios, as ``nx_batch_solve`` takes them (no device):
     ``(edge_bc (B, E, 2), edge_f (B, E) | None, f_const (B,) | None)`` in the local edge order
@@ -870,6 +890,27 @@ class HydraulicNetworkAssembler:
         """Owned device rows of function block ``i`` in the block's DoF order."""
         blocks = [*self._flux_idx, self._p_idx, self._lm_idx]
         return np.asarray(blocks[i], dtype=np.int64)
+
+    def block_order_rows(self) -> np.ndarray:
+        """Device row of every entry of the reference block order (the concatenated function
+        blocks, the columns of ``BatchResult.x``); computed once."""
+        rows = getattr(self, "_block_order", None)
+        if rows is None:
+            n = len(self.function_spaces)
+            rows = self._block_order = np.concatenate([self._block_rows(i) for i in range(n)])
+        return rows
+
+    def gradient_maps(self):
+        """Host gathers of :meth:`Solver.gradient`, computed once: the local slot of every
+        graph edge, and :func:`edge_boundary_rhs_adjoint`'s ``(index, sign)``."""
+        maps = getattr(self, "_gradient_maps", None)
+        if maps is None:
+            edge_ids = np.asarray(self._edge_ids)
+            slot = np.empty(edge_ids.size, dtype=np.int64)
+            slot[edge_ids] = np.arange(edge_ids.size)
+            maps = self._gradient_maps = (
+                slot, *edge_boundary_rhs_adjoint(self._network_mesh, edge_ids))
+        return maps
 
     def scatter_solution(self, x: np.ndarray, functions: list) -> list:
         """Split a host device-layout vector into ``[flux..., pressure, multiplier]``."""

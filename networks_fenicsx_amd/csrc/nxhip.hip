@@ -3633,6 +3633,207 @@ __global__ __launch_bounds__(kBlock) void k_b_gather(const double* __restrict__ 
   if (i < n) out[blockIdx.y * ld + i] = X[blockIdx.y * ld + idx[i]];
 }
 
+// --------------------------------------------------------------------------------------
+// Adjoint gradient of an observed-row objective (nx_batch_gradient). The device system is
+// symmetric (A_dev = S A_ref, S = -1 on the pressure rows), so A_ref^T lambda = c is
+// A_dev mu = c with mu = S lambda: the observation vector goes in as it is and the batched
+// sweeps solve it. In the device's own convention nothing else carries a sign either: the
+// rhs the scenarios set is edge_bc at q_0 / q_N and -(f h) on the pressure rows, so
+// dJ/d edge_bc = mu there, dJ/df_e = sum_k -(h_k mu[p_k]), and dA/dR_e touches flux rows only.
+//
+// k_b_obs, grid = (row slices, forward columns). With C: the column's adjoint right-hand
+// side -- every workgroup zeroes its slice of `span` rows, then writes w_i (x[r_i] - d_i)
+// (kind 1) or w_i (kind 0) at the distinct observed rows r_i that fall into it (one workgroup
+// per column would leave the 8 n bytes of zeros to one CU). With J: slice 0's workgroup forms
+// the objective (kind 1: 1/2 sum_i w_i (x[r_i] - d_i)^2; kind 0: sum_i w_i x[r_i]) into
+// J[col], summed in a fixed order (thread-strided, wave butterfly, waves in order).
+// d: the chunk's data, n_obs per column. Kind 0 builds its one adjoint column with X = null.
+constexpr int kObsThreads = 1024;
+constexpr int kObsSpan = 8 * kObsThreads;  // rows per slice
+__global__ __launch_bounds__(kObsThreads) void k_b_obs(const double* __restrict__ X, int64_t ld,
+                                                       int64_t n, int kind, int n_obs,
+                                                       const int* __restrict__ rows,
+                                                       const double* __restrict__ w,
+                                                       const double* __restrict__ d,
+                                                       double* __restrict__ C,
+                                                       double* __restrict__ J) {
+#pragma clang fp contract(off)
+  __shared__ double s_w[kObsThreads / 64];
+  const int col = blockIdx.y;
+  const double* x = X ? X + col * ld : nullptr;
+  const double* dc = d ? d + (int64_t)col * n_obs : nullptr;
+  if (C) {
+    double* c = C + col * ld;
+    const int64_t r0 = (int64_t)blockIdx.x * kObsSpan, r1 = min<int64_t>(n, r0 + kObsSpan);
+    for (int64_t i = r0 + threadIdx.x; i < r1; i += kObsThreads) c[i] = 0.0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_obs; i += kObsThreads) {
+      const int r = rows[i];
+      if (r >= r0 && r < r1) c[r] = kind ? w[i] * (x[r] - dc[i]) : w[i];
+    }
+  }
+  if (!J || blockIdx.x != 0) return;  // block-uniform
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n_obs; i += kObsThreads) {
+    const double xv = x[rows[i]];
+    if (kind) {
+      const double r = xv - dc[i];
+      const double wr = w[i] * r;
+      acc += wr * r;
+    } else {
+      acc += w[i] * xv;
+    }
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = s_w[0];
+    for (int i = 1; i < kObsThreads / 64; ++i) t += s_w[i];
+    J[col] = kind ? 0.5 * t : t;
+  }
+}
+
+// k_b_edge_form: per (column, edge) the contraction of the adjoint solution L with the
+// forward solution X over the edge's interleaved rows, grid = (edge blocks, columns), in the
+// assembly's lane shapes. Outputs (column col at col E, col E, col 2 E):
+//   gR[e]  = -sum_k h_k/6 (2 l_k x_k + l_k x_{k+1} + l_{k+1} x_k + 2 l_{k+1} x_{k+1})
+//            (x_k, l_k the edge's flux vertex values: -l^T (dA/dR_e) x, the R = 1 P1 mass),
+//   gf[e]  = sum_k -(h_k l[p_k]),   gbc[e] = l[q_0], l[q_N].
+// h_k as k_b_rhs regenerates it (vertex, sqrt, no contraction). A lane is a cell; it loads
+// its q_k, p_k and takes q_{k+1} from the next lane. Column col of X pairs with column col
+// of L (l_ld = ld) or with the one adjoint column of the linear objective (l_ld = 0).
+struct FormArgs {
+  EdgeArgs ea;
+  const double* X;
+  const double* L;
+  int64_t ld, l_ld;
+  double *gR, *gf, *gbc;
+};
+
+__device__ __forceinline__ double form_cell_len(const double* x0, const double* x1, int k, int N,
+                                                double invN) {
+#pragma clang fp contract(off)
+  double pa[3], pb[3];
+  vertex(x0, x1, k, N, invN, pa);
+  vertex(x0, x1, k + 1, N, invN, pb);
+  const double d0 = pb[0] - pa[0], d1 = pb[1] - pa[1], d2 = pb[2] - pa[2];
+  return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+}
+
+__device__ __forceinline__ double form_cell_R(double h, double xk, double xk1, double lk,
+                                              double lk1) {
+#pragma clang fp contract(off)
+  const double a = 2.0 * (lk * xk), b = lk * xk1, c = lk1 * xk, d = 2.0 * (lk1 * xk1);
+  return (h / 6.0) * (((a + b) + c) + d);
+}
+
+// Small N (N < S <= 32): 64 / S edges per wave, one S-lane segment per edge (lane = cell,
+// lane N the closing vertex), as k_assemble_seg; one butterfly inside the segment per output.
+template <int S>
+__global__ __launch_bounds__(kBlock) void k_b_edge_form_seg(FormArgs a) {
+#pragma clang fp contract(off)
+  constexpr int EPW = 64 / S;
+  const int lane = threadIdx.x & 63;
+  const int sub = lane / S, cl = lane % S;
+  const int64_t E = a.ea.E;
+  const int64_t e0 = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * EPW;
+  if (e0 >= E) return;  // wave-uniform
+  const int ne = (int)min<int64_t>(EPW, E - e0);
+  const int64_t e = e0 + min(sub, ne - 1);  // idle segments shadow the last edge
+  const bool mine = sub < ne;
+  const int N = a.ea.N;
+  const int col = blockIdx.y;
+  const int64_t base = e * (2 * N + 1);
+  const double* x = a.X + col * a.ld + base;
+  const double* l = a.L + col * a.l_ld + base;
+  double xq = 0.0, lq = 0.0, lp = 0.0, h = 0.0;
+  if (mine && cl <= N) {
+    xq = x[2 * cl];
+    lq = l[2 * cl];
+  }
+  if (mine && cl < N) {
+    lp = l[2 * cl + 1];
+    double x0[3], x1[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      x0[c] = a.ea.edge_x[6 * e + c];
+      x1[c] = a.ea.edge_x[6 * e + 3 + c];
+    }
+    h = form_cell_len(x0, x1, cl, N, 1.0 / (double)N);
+  }
+  const double xq1 = __shfl(xq, min(lane + 1, 63), 64), lq1 = __shfl(lq, min(lane + 1, 63), 64);
+  double tR = 0.0, tf = 0.0;
+  if (mine && cl < N) {
+    tR = form_cell_R(h, xq, xq1, lq, lq1);
+    tf = -(h * lp);
+  }
+#pragma unroll
+  for (int o = S / 2; o > 0; o >>= 1) {
+    tR += __shfl_xor(tR, o, 64);
+    tf += __shfl_xor(tf, o, 64);
+  }
+  if (mine && cl == 0) {
+    a.gR[col * E + e] = -tR;
+    a.gf[col * E + e] = tf;
+    a.gbc[(col * E + e) * 2] = lq;
+  }
+  if (mine && cl == N) a.gbc[(col * E + e) * 2 + 1] = lq;
+}
+
+// N >= 32: one wave per edge, the cells in chunks of 64 taken in order (as k_assemble); a
+// chunk's closing vertex is one uniform load.
+__global__ __launch_bounds__(kBlock) void k_b_edge_form(FormArgs a) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int64_t E = a.ea.E;
+  const int64_t e = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (e >= E) return;  // wave-uniform
+  const int N = a.ea.N;
+  const double invN = 1.0 / (double)N;
+  const int col = blockIdx.y;
+  const int64_t base = e * (2 * N + 1);
+  const double* x = a.X + col * a.ld + base;
+  const double* l = a.L + col * a.l_ld + base;
+  double x0[3], x1[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    x0[c] = a.ea.edge_x[6 * e + c];
+    x1[c] = a.ea.edge_x[6 * e + 3 + c];
+  }
+  double accR = 0.0, accf = 0.0;
+  for (int c0 = 0; c0 < N; c0 += 64) {
+    const int nc = min(64, N - c0);
+    const int k = c0 + lane;
+    double xq = 0.0, lq = 0.0, lp = 0.0, h = 0.0;
+    if (lane < nc) {
+      xq = x[2 * k];
+      lq = l[2 * k];
+      lp = l[2 * k + 1];
+      h = form_cell_len(x0, x1, k, N, invN);
+    }
+    const double xe = x[2 * (c0 + nc)], le = l[2 * (c0 + nc)];
+    double xq1 = __shfl(xq, min(lane + 1, 63), 64), lq1 = __shfl(lq, min(lane + 1, 63), 64);
+    if (lane == nc - 1) {
+      xq1 = xe;
+      lq1 = le;
+    }
+    double tR = 0.0, tf = 0.0;
+    if (lane < nc) {
+      tR = form_cell_R(h, xq, xq1, lq, lq1);
+      tf = -(h * lp);
+    }
+    accR += wave_sum(tR);
+    accf += wave_sum(tf);
+  }
+  if (lane == 0) {
+    a.gR[col * E + e] = -accR;
+    a.gf[col * E + e] = accf;
+    a.gbc[(col * E + e) * 2] = l[0];
+    a.gbc[(col * E + e) * 2 + 1] = l[2 * N];
+  }
+}
+
 // ======================================================================================
 // k_dir_step: the whole direct step of ONE rank in ONE launch (default; DESIGN.md section
 // 3c). It replaces the four launches k_assemble_seg -> k_pc_up_lds (mode 3) ->
@@ -7641,6 +7842,11 @@ struct nx_network {
   int bws_cap = 0;
   size_t bws_bytes = 0;
   int b_launches = 0, b_refined = 0, b_fallback = 0, b_chunk = 0;
+  // nx_batch_gradient: whether the workspace carries the adjoint columns (kept once a
+  // gradient call asked for them), and the observation list's device copy (rows | w | data)
+  bool bws_grad = false;
+  void* gobs = nullptr;
+  size_t gobs_bytes = 0;
   int64_t cpc_version = -1;  // R's version its capacitance matrix was built for (fe_cp_solve)
   bool cpc_failed = false;   // a singular capacitance matrix: the solves run MINRES
   int cpc_builds = 0;
@@ -10157,6 +10363,7 @@ NX_API int nx_destroy(nx_network_t* h) {
   for (void* p : h->pc_bufs)
     if (p) (void)hipFree(p);
   if (h->bws) (void)hipFree(h->bws);
+  if (h->gobs) (void)hipFree(h->gobs);
   if (h->h_st) (void)hipHostFree(h->h_st);
   if (h->h_last) (void)hipHostFree(h->h_last);
   for (auto& e : h->ev)
@@ -12472,17 +12679,20 @@ struct BatchWs {
   double* cw;             // cycle correction: w (cap x m)
   double* save;           // the handle's x | tmp | rhs while a build of the cycle correction
                           // or a fallback solve borrows them (3 n_col)
+  double *C, *L;          // nx_batch_gradient (bws_grad): adjoint rhs and solution, cap x ld
+  double *gJ, *gR, *gf, *gbc;  // and its outputs: cap, cap x E, cap x E, cap x 2 E
   int* list;              // cap
   int nblk;
 };
 
-size_t batch_col_doubles(const nx_network* h) {
+size_t batch_col_doubles(const nx_network* h, bool grad) {
   const int64_t E = h->E, S = std::max<int64_t>(h->pc_slots, 1), m = 2 * (int64_t)h->n_cyc;
   const int nblk = grid_of(h->n_own, kBlock);
-  return (size_t)(4 * h->n_col + 3 * E + 5 * S + 3 * E + 1 + 2 * nblk + 2 + m);
+  const int64_t g = grad ? 2 * h->n_col + 4 * E + 1 : 0;  // X stays resident beside C and L
+  return (size_t)(4 * h->n_col + 3 * E + 5 * S + 3 * E + 1 + 2 * nblk + 2 + m + g);
 }
-size_t batch_bytes(const nx_network* h, int cap) {
-  return 8 * (batch_col_doubles(h) * (size_t)cap + (size_t)(3 * h->n_col)) +
+size_t batch_bytes(const nx_network* h, int cap, bool grad) {
+  return 8 * (batch_col_doubles(h, grad) * (size_t)cap + (size_t)(3 * h->n_col)) +
          sizeof(int) * (size_t)cap + 64;
 }
 BatchWs batch_carve(const nx_network* h, int cap) {
@@ -12519,6 +12729,14 @@ BatchWs batch_carve(const nx_network* h, int cap) {
   w.stats = take(cap * 2);
   w.cw = take(cap * m);
   w.save = take(3 * ld);
+  if (h->bws_grad) {
+    w.C = take(cap * ld);
+    w.L = take(cap * ld);
+    w.gJ = take(cap);
+    w.gR = take(cap * E);
+    w.gf = take(cap * E);
+    w.gbc = take(cap * 2 * E);
+  }
   w.list = reinterpret_cast<int*>(p);
   return w;
 }
@@ -12534,39 +12752,42 @@ bool batch_ok(const nx_network* h) {
 // size follows the decomposition's slots and the cycle chains, which nx_set_preconditioner
 // and nx_set_cycles change after a workspace was allocated (nx_batch_rhs is legal before
 // either), so the allocated bytes are checked, not the column count alone.
-bool batch_fits(const nx_network* h, int chunk) {
-  return h->bws != nullptr && chunk <= h->bws_cap && batch_bytes(h, h->bws_cap) <= h->bws_bytes;
+bool batch_fits(const nx_network* h, int chunk, bool grad) {
+  return h->bws != nullptr && chunk <= h->bws_cap && (!grad || h->bws_grad) &&
+         batch_bytes(h, h->bws_cap, h->bws_grad) <= h->bws_bytes;
 }
 
 // The chunk size of this call and a workspace that holds it: NXHIP_BATCH_CHUNK (read per
 // call) or the largest of <= kBatchChunkMax whose workspace fits kBatchMemShare of the free
 // device memory; a failed allocation halves it down to 1.
-int batch_workspace(nx_network* h, int n_cols, int* chunk_out) {
+int batch_workspace(nx_network* h, int n_cols, int* chunk_out, bool grad = false) {
+  grad = grad || h->bws_grad;
   int chunk = std::min(n_cols, kBatchChunkMax);
   const char* e = std::getenv("NXHIP_BATCH_CHUNK");
   if (e != nullptr && std::atoi(e) > 0) {
     chunk = std::min(std::min(std::atoi(e), kBatchChunkEnvMax), n_cols);
-  } else if (!batch_fits(h, chunk)) {
+  } else if (!batch_fits(h, chunk, grad)) {
     size_t fr = 0, tot = 0;
     HIPCALL(hipMemGetInfo(&fr, &tot));
     const double room = kBatchMemShare * (double)fr;
-    while (chunk > 1 && (double)batch_bytes(h, chunk) > room) --chunk;
+    while (chunk > 1 && (double)batch_bytes(h, chunk, grad) > room) --chunk;
   }
-  if (!batch_fits(h, chunk)) {
+  if (!batch_fits(h, chunk, grad)) {
     HIPCALL(hipStreamSynchronize(h->stream));
     if (h->bws) (void)hipFree(h->bws);
     h->bws = nullptr;
     h->bws_cap = 0;
     h->bws_bytes = 0;
     for (;;) {
-      if (hipMalloc(&h->bws, batch_bytes(h, chunk)) == hipSuccess) break;
+      if (hipMalloc(&h->bws, batch_bytes(h, chunk, grad)) == hipSuccess) break;
       (void)hipGetLastError();
       h->bws = nullptr;
       if (chunk == 1) return fail(NX_ERR_HIP, "nx_batch_solve: no memory for one column's workspace");
       chunk = std::max(1, chunk / 2);
     }
     h->bws_cap = chunk;
-    h->bws_bytes = batch_bytes(h, chunk);
+    h->bws_grad = grad;
+    h->bws_bytes = batch_bytes(h, chunk, grad);
   }
   *chunk_out = chunk;
   return NX_OK;
@@ -12655,11 +12876,11 @@ int batch_sweeps(nx_network* h, const BatchWs& ws, const int* list, int nc, cons
   return NX_OK;
 }
 
-// R = B - A X and the two norms of nc columns; stats (host, 2 per workspace column) filled
+// R = Bv - A Xv and the two norms of nc columns; stats (host, 2 per workspace column) filled
 // for them after one synchronisation.
-int batch_residual(nx_network* h, const BatchWs& ws, const int* list, int nc,
-                   std::vector<double>& stats, int cap) {
-  hipLaunchKernelGGL(k_b_res, dim3(ws.nblk), dim3(kBlock), 0, h->stream, csr_of(h), ws.X, ws.B,
+int batch_residual(nx_network* h, const BatchWs& ws, const double* Xv, const double* Bv,
+                   const int* list, int nc, std::vector<double>& stats, int cap) {
+  hipLaunchKernelGGL(k_b_res, dim3(ws.nblk), dim3(kBlock), 0, h->stream, csr_of(h), Xv, Bv,
                      ws.R, ws.cols.ld, list, nc, ws.part, ws.nblk);
   hipLaunchKernelGGL(k_b_norms, dim3(nc), dim3(kReduceThreads), 0, h->stream, ws.part, ws.nblk,
                      list, ws.stats);
@@ -12715,22 +12936,118 @@ int batch_restore(nx_network* h, const BatchWs& ws, const BatchSaved& s, bool wi
 // One column through the single-column path (nx_solve's: the direct solve with its
 // refinement, then MINRES): the column's assembled rhs (ws.B) stands in for the handle's,
 // which is put back with its x, tmp and published state (no assembly runs, so the handle's
-// coefficients are not involved). The solution goes to ws.X's column.
-int batch_fallback(nx_network* h, const BatchWs& ws, int wcol, double rtol, int32_t* it,
-                   double* relres, int32_t* conv) {
+// coefficients are not involved). The solution goes to Xv's column (Bv / Xv: ws.B / ws.X, or
+// the adjoint's ws.C / ws.L).
+int batch_fallback(nx_network* h, const BatchWs& ws, const double* Bv, double* Xv, int wcol,
+                   double rtol, int32_t* it, double* relres, int32_t* conv) {
   const int64_t n = h->n_col;
   BatchSaved sv{};
   CHECK(batch_save(h, ws, &sv, true));
-  HIPCALL(hipMemcpyAsync(h->rhs, ws.B + wcol * n, sizeof(double) * n, hipMemcpyDeviceToDevice,
+  HIPCALL(hipMemcpyAsync(h->rhs, Bv + wcol * n, sizeof(double) * n, hipMemcpyDeviceToDevice,
                          h->stream));
   h->have_rhs = true;
   nx_network* hs[1] = {h};
   const int rc = solve_team(Team{hs, 1, nullptr}, rtol, 50000, 4, it, relres, conv);
   if (rc == NX_OK)
-    HIPCALL(hipMemcpyAsync(ws.X + wcol * n, h->x, sizeof(double) * n, hipMemcpyDeviceToDevice,
+    HIPCALL(hipMemcpyAsync(Xv + wcol * n, h->x, sizeof(double) * n, hipMemcpyDeviceToDevice,
                            h->stream));
   CHECK(batch_restore(h, ws, sv, true));
   return rc;
+}
+
+// The per-column policy on the first nc workspace columns, Xv = A^{-1} Bv: the sweeps, the
+// true residual, one refinement pass over the list of columns above rtol, the single-column
+// path for a column still above it. iters / relres / converged: this chunk's entries (any
+// may be null). stats (host) keeps ||r||^2 | ||b||^2 per column: a column with ||b|| = 0 is
+// reported converged and its caller writes the exact zero.
+int batch_solve_cols(nx_network* h, const BatchWs& ws, int nc, const double* Bv, double* Xv,
+                     double rtol, int32_t* iters, double* relres, int32_t* converged,
+                     std::vector<double>& stats) {
+  const int cap = h->bws_cap;
+  const int64_t n = h->n_own, ld = ws.cols.ld;
+  std::vector<int> redo, fall;
+  CHECK(batch_sweeps(h, ws, nullptr, nc, Bv, Xv));
+  CHECK(batch_residual(h, ws, Xv, Bv, nullptr, nc, stats, cap));
+  for (int c = 0; c < nc; ++c) {
+    const double rr = stats[2 * c], bb = stats[2 * c + 1];
+    const double r = batch_relres(rr, bb);
+    if (iters) iters[c] = 1;
+    if (relres) relres[c] = r;
+    if (converged) converged[c] = (bb == 0.0 || r <= rtol) ? 1 : 0;
+    if (bb > 0.0 && !(r <= rtol)) redo.push_back(c);
+  }
+  if (!redo.empty()) {  // one refinement pass over the failing columns only: x += A^{-1} r
+    const int nr = (int)redo.size();
+    HIPCALL(hipMemcpyAsync(ws.list, redo.data(), sizeof(int) * nr, hipMemcpyHostToDevice,
+                           h->stream));
+    CHECK(batch_sweeps(h, ws, ws.list, nr, ws.R, ws.D));
+    hipLaunchKernelGGL(k_b_add, dim3(grid_of(n, kBlock), nr), dim3(kBlock), 0, h->stream, Xv,
+                       ws.D, ld, ws.list, n);
+    h->b_launches += 1;
+    CHECK(batch_residual(h, ws, Xv, Bv, ws.list, nr, stats, cap));
+    h->b_refined += nr;
+    for (int c : redo) {
+      const double r = batch_relres(stats[2 * c], stats[2 * c + 1]);
+      if (iters) iters[c] = 2;
+      if (relres) relres[c] = r;
+      if (converged) converged[c] = r <= rtol ? 1 : 0;
+      if (!(r <= rtol)) fall.push_back(c);
+    }
+  }
+  for (int c : fall) {  // still above rtol: the single-column path (with its MINRES)
+    int32_t it = 0, cv = 0;
+    double r = 0.0;
+    CHECK(batch_fallback(h, ws, Bv, Xv, c, rtol, &it, &r, &cv));
+    h->b_fallback += 1;
+    if (iters) iters[c] = it;
+    if (relres) relres[c] = r;
+    if (converged) converged[c] = cv;
+  }
+  return NX_OK;
+}
+
+// What the sweeps read besides the right-hand side, current for the handle's matrix: the
+// lumped mass, and on a graph with cycles the correction (rebuilt only for a new matrix;
+// its solves borrow the handle's x, tmp and published state, put back afterwards).
+int batch_make_current(nx_network* h, const BatchWs& ws) {
+  CHECK(ensure_dq(h));
+  if (h->n_cyc > 0 && h->cyc_version != h->lhs_version) {
+    BatchSaved sv{};
+    CHECK(batch_save(h, ws, &sv, false));
+    const int rc = cyc_build(h);
+    CHECK(batch_restore(h, ws, sv, false));
+    CHECK(rc);
+    h->b_launches += cyc_build_launches(h);
+  }
+  return NX_OK;
+}
+
+// nx_batch_gradient: exact zeros in the columns whose right-hand side was zero (stats of
+// batch_solve_cols), so that nothing downstream sees what the sweeps left there.
+int batch_zero_cols(nx_network* h, double* Xv, int64_t ld, int nc,
+                    const std::vector<double>& stats) {
+  for (int c = 0; c < nc; ++c)
+    if (stats[2 * c + 1] == 0.0)
+      HIPCALL(hipMemsetAsync(Xv + c * ld, 0, sizeof(double) * h->n_own, h->stream));
+  return NX_OK;
+}
+
+int batch_edge_form(nx_network* h, const BatchWs& ws, int nc, int64_t l_ld) {
+  const int64_t E = h->E;
+  const FormArgs fa{EdgeArgs{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N}, ws.X, ws.L,
+                    ws.cols.ld, l_ld, ws.gR, ws.gf, ws.gbc};
+  constexpr int wpb = kBlock / 64;
+  if (h->N < 16)
+    hipLaunchKernelGGL(k_b_edge_form_seg<16>, dim3(grid_of(E, wpb * 4), nc), dim3(kBlock), 0,
+                       h->stream, fa);
+  else if (h->N < 32)
+    hipLaunchKernelGGL(k_b_edge_form_seg<32>, dim3(grid_of(E, wpb * 2), nc), dim3(kBlock), 0,
+                       h->stream, fa);
+  else
+    hipLaunchKernelGGL(k_b_edge_form, dim3(grid_of(E, wpb), nc), dim3(kBlock), 0, h->stream, fa);
+  HIPCALL(hipGetLastError());
+  h->b_launches += 1;
+  return NX_OK;
 }
 
 int batch_check_args(nx_network* h, int32_t n_cols, const double* edge_bc, const double* out) {
@@ -12798,64 +13115,15 @@ NX_API int nx_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc
   CHECK(batch_workspace(h, n_cols, &chunk));
   h->b_chunk = chunk;
   const BatchWs ws = batch_carve(h, h->bws_cap);
-  const int cap = h->bws_cap;
-  // what the sweeps read besides the right-hand side, current for the handle's matrix: the
-  // lumped mass, and on a graph with cycles the correction (rebuilt only for a new matrix;
-  // its solves borrow the handle's x, tmp and published state, put back afterwards)
-  CHECK(ensure_dq(h));
-  if (h->n_cyc > 0 && h->cyc_version != h->lhs_version) {
-    BatchSaved sv{};
-    CHECK(batch_save(h, ws, &sv, false));
-    const int rc = cyc_build(h);
-    CHECK(batch_restore(h, ws, sv, false));
-    CHECK(rc);
-    h->b_launches += cyc_build_launches(h);
-  }
+  CHECK(batch_make_current(h, ws));
   const int64_t n = h->n_own, ld = ws.cols.ld;
   std::vector<double> stats;
-  std::vector<int> redo, fall;
   for (int c0 = 0; c0 < n_cols; c0 += chunk) {
     const int nc = std::min(chunk, n_cols - c0);
     CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
-    CHECK(batch_sweeps(h, ws, nullptr, nc, ws.B, ws.X));
-    CHECK(batch_residual(h, ws, nullptr, nc, stats, cap));
-    redo.clear();
-    for (int c = 0; c < nc; ++c) {
-      const double rr = stats[2 * c], bb = stats[2 * c + 1];
-      const double r = batch_relres(rr, bb);
-      if (iters) iters[c0 + c] = 1;
-      if (relres) relres[c0 + c] = r;
-      if (converged) converged[c0 + c] = (bb == 0.0 || r <= rtol) ? 1 : 0;
-      if (bb > 0.0 && !(r <= rtol)) redo.push_back(c);
-    }
-    fall.clear();
-    if (!redo.empty()) {  // one refinement pass over the failing columns only: x += A^{-1} r
-      const int nr = (int)redo.size();
-      HIPCALL(hipMemcpyAsync(ws.list, redo.data(), sizeof(int) * nr, hipMemcpyHostToDevice,
-                             h->stream));
-      CHECK(batch_sweeps(h, ws, ws.list, nr, ws.R, ws.D));
-      hipLaunchKernelGGL(k_b_add, dim3(grid_of(n, kBlock), nr), dim3(kBlock), 0, h->stream, ws.X,
-                         ws.D, ld, ws.list, n);
-      h->b_launches += 1;
-      CHECK(batch_residual(h, ws, ws.list, nr, stats, cap));
-      h->b_refined += nr;
-      for (int c : redo) {
-        const double r = batch_relres(stats[2 * c], stats[2 * c + 1]);
-        if (iters) iters[c0 + c] = 2;
-        if (relres) relres[c0 + c] = r;
-        if (converged) converged[c0 + c] = r <= rtol ? 1 : 0;
-        if (!(r <= rtol)) fall.push_back(c);
-      }
-    }
-    for (int c : fall) {  // still above rtol: the single-column path (with its MINRES)
-      int32_t it = 0, cv = 0;
-      double r = 0.0;
-      CHECK(batch_fallback(h, ws, c, rtol, &it, &r, &cv));
-      h->b_fallback += 1;
-      if (iters) iters[c0 + c] = it;
-      if (relres) relres[c0 + c] = r;
-      if (converged) converged[c0 + c] = cv;
-    }
+    CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.X, rtol, iters ? iters + c0 : nullptr,
+                           relres ? relres + c0 : nullptr, converged ? converged + c0 : nullptr,
+                           stats));
     const double* src = ws.X;
     if (order != 0) {
       hipLaunchKernelGGL(k_b_gather, dim3(grid_of(n, kBlock), nc), dim3(kBlock), 0, h->stream, ws.X,
@@ -12869,6 +13137,118 @@ NX_API int nx_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc
     HIPCALL(hipStreamSynchronize(h->stream));
     for (int c = 0; c < nc; ++c)  // b = 0: x = 0 exactly (no division by ||b||)
       if (stats[2 * c + 1] == 0.0) std::fill_n(out + (int64_t)(c0 + c) * n, n, 0.0);
+  }
+  return NX_OK;
+}
+
+NX_API int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                             const double* edge_f, const double* f_const, double rtol,
+                             int32_t kind, int32_t n_obs, const int32_t* obs_rows,
+                             const double* obs_w, const double* obs_d, double* value,
+                             double* grad_R, double* grad_bc, double* grad_f, int32_t* iters,
+                             double* relres, int32_t* converged) {
+  const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (n_cols < 1) return fail(NX_ERR_ARG, "n_cols must be >= 1");
+  if (!edge_bc || !value || !grad_R) return fail(NX_ERR_ARG, "edge_bc / value / grad_R is NULL");
+  if (n_obs < 1 || !obs_rows || !obs_w) return fail(NX_ERR_ARG, "at least one observed row");
+  if (kind != 0 && kind != 1) return fail(NX_ERR_ARG, "kind: 0 linear, 1 least squares");
+  if (kind == 1 && !obs_d) return fail(NX_ERR_ARG, "the least-squares objective needs obs_d");
+  if (!batch_ok(h))
+    return fail(NX_ERR_STATE, "nx_batch_gradient: the batched direct solve does not apply to "
+                              "this handle (nx_batch_supported)");
+  if (!h->have_lhs) return fail(NX_ERR_STATE, "assemble the matrix before nx_batch_gradient");
+  const int64_t n = h->n_own, E = h->E;
+  {
+    std::vector<char> seen((size_t)n, 0);
+    for (int i = 0; i < n_obs; ++i) {
+      const int64_t r = obs_rows[i];
+      if (r < 0 || r >= n) return fail(NX_ERR_ARG, "an observed row is out of range");
+      if (seen[(size_t)r]) return fail(NX_ERR_ARG, "the observed rows must be distinct");
+      seen[(size_t)r] = 1;
+    }
+  }
+  CHECK(set_device(h));
+  h->b_refined = h->b_fallback = 0;
+  h->b_launches = made_current + (h->dq_stale ? 1 : 0);
+  int chunk = 0;
+  CHECK(batch_workspace(h, n_cols, &chunk, true));
+  h->b_chunk = chunk;
+  const BatchWs ws = batch_carve(h, h->bws_cap);
+  CHECK(batch_make_current(h, ws));
+  // the observation list on the device: rows (ints, padded to doubles) | w | the chunk's data
+  const size_t row_d = ((size_t)n_obs + 1) / 2;
+  const size_t need = 8 * (row_d + (size_t)n_obs + (size_t)n_obs * (size_t)chunk);
+  if (need > h->gobs_bytes) {
+    HIPCALL(hipStreamSynchronize(h->stream));
+    if (h->gobs) (void)hipFree(h->gobs);
+    h->gobs = nullptr;
+    h->gobs_bytes = 0;
+    HIPCALL(hipMalloc(&h->gobs, need));
+    h->gobs_bytes = need;
+  }
+  int* d_rows = static_cast<int*>(h->gobs);
+  double* d_w = static_cast<double*>(h->gobs) + row_d;
+  double* d_d = d_w + n_obs;
+  HIPCALL(hipMemcpyAsync(d_rows, obs_rows, sizeof(int) * n_obs, hipMemcpyHostToDevice, h->stream));
+  HIPCALL(hipMemcpyAsync(d_w, obs_w, sizeof(double) * n_obs, hipMemcpyHostToDevice, h->stream));
+  const int64_t ld = ws.cols.ld;
+  const int slices = grid_of(n, kObsSpan);
+  std::vector<double> stats;
+  int32_t a_it = 1, a_cv = 1;
+  double a_rr = 0.0;
+  if (kind == 0) {  // the same adjoint column for every scenario: solved once per call
+    hipLaunchKernelGGL(k_b_obs, dim3(slices, 1), dim3(kObsThreads), 0, h->stream, nullptr, ld, n,
+                       0, n_obs, d_rows, d_w, nullptr, ws.C, nullptr);
+    HIPCALL(hipGetLastError());
+    h->b_launches += 1;
+    CHECK(batch_solve_cols(h, ws, 1, ws.C, ws.L, rtol, &a_it, &a_rr, &a_cv, stats));
+    CHECK(batch_zero_cols(h, ws.L, ld, 1, stats));
+  }
+  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
+    const int nc = std::min(chunk, n_cols - c0);
+    CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
+    CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.X, rtol, iters ? iters + c0 : nullptr,
+                           relres ? relres + c0 : nullptr, converged ? converged + c0 : nullptr,
+                           stats));
+    CHECK(batch_zero_cols(h, ws.X, ld, nc, stats));  // b = 0: x = 0 exactly
+    int32_t* a_iters = iters ? iters + n_cols + c0 : nullptr;
+    double* a_relres = relres ? relres + n_cols + c0 : nullptr;
+    int32_t* a_conv = converged ? converged + n_cols + c0 : nullptr;
+    if (kind == 1) {
+      HIPCALL(hipMemcpyAsync(d_d, obs_d + (int64_t)c0 * n_obs, sizeof(double) * n_obs * nc,
+                             hipMemcpyHostToDevice, h->stream));
+      hipLaunchKernelGGL(k_b_obs, dim3(slices, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n,
+                         1, n_obs, d_rows, d_w, d_d, ws.C, ws.gJ);
+      HIPCALL(hipGetLastError());
+      h->b_launches += 1;
+      CHECK(batch_solve_cols(h, ws, nc, ws.C, ws.L, rtol, a_iters, a_relres, a_conv, stats));
+      CHECK(batch_zero_cols(h, ws.L, ld, nc, stats));
+    } else {
+      hipLaunchKernelGGL(k_b_obs, dim3(1, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n, 0,
+                         n_obs, d_rows, d_w, nullptr, nullptr, ws.gJ);
+      HIPCALL(hipGetLastError());
+      h->b_launches += 1;
+      for (int c = 0; c < nc; ++c) {
+        if (a_iters) a_iters[c] = a_it;
+        if (a_relres) a_relres[c] = a_rr;
+        if (a_conv) a_conv[c] = a_cv;
+      }
+    }
+    CHECK(batch_edge_form(h, ws, nc, kind == 1 ? ld : 0));
+    // the chunk's outputs straight into the caller's arrays (no staging, no host unpack)
+    HIPCALL(hipMemcpyAsync(value + c0, ws.gJ, sizeof(double) * nc, hipMemcpyDeviceToHost,
+                           h->stream));
+    HIPCALL(hipMemcpyAsync(grad_R + (int64_t)c0 * E, ws.gR, sizeof(double) * E * nc,
+                           hipMemcpyDeviceToHost, h->stream));
+    if (grad_f)
+      HIPCALL(hipMemcpyAsync(grad_f + (int64_t)c0 * E, ws.gf, sizeof(double) * E * nc,
+                             hipMemcpyDeviceToHost, h->stream));
+    if (grad_bc)
+      HIPCALL(hipMemcpyAsync(grad_bc + (int64_t)c0 * 2 * E, ws.gbc, sizeof(double) * 2 * E * nc,
+                             hipMemcpyDeviceToHost, h->stream));
+    HIPCALL(hipStreamSynchronize(h->stream));
   }
   return NX_OK;
 }

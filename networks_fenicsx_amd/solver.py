@@ -50,7 +50,7 @@ from . import _lib
 from .assembly import DeviceMatrix, DeviceVector, HydraulicNetworkAssembler
 from .timing import timed
 
-__all__ = ["Solver", "KSPInfo", "BatchResult"]
+__all__ = ["Solver", "KSPInfo", "BatchResult", "GradientResult"]
 
 _DEFAULTS = {
     "ksp_type": "preonly",
@@ -125,6 +125,29 @@ class BatchResult:
         xdev = np.empty(self.x.shape[1], dtype=np.float64)  # block order -> device layout
         xdev[np.concatenate([asm._block_rows(i) for i in range(len(fns))])] = self.x[j]
         return asm.scatter_solution(xdev, fns)
+
+
+class GradientResult:
+    """What :meth:`Solver.gradient` returns: per scenario the objective and its derivatives.
+
+    ``value``: ``(B,)``; ``dR``, ``df``: ``(B, num_edges)`` in ``graph.edges()`` order -- with
+    respect to every edge's resistance and source; ``dp_bc``: ``(B, num_nodes)`` -- with respect
+    to the nodal boundary pressure, zero off the boundary nodes; ``iterations``,
+    ``residual_norms``, ``converged``: ``(B, 2)`` each, the forward and the adjoint solve;
+    ``info``: the dict of ``nx_get_batch_info`` (launches, refined, fallback, chunk)."""
+
+    def __init__(self, value, dR, df, dp_bc, iterations, residual_norms, converged, info):
+        self.value = value
+        self.dR = dR
+        self.df = df
+        self.dp_bc = dp_bc
+        self.iterations = np.asarray(iterations)
+        self.residual_norms = np.asarray(residual_norms)
+        self.converged = np.asarray(converged, dtype=bool)
+        self.info = dict(info)
+
+    def __len__(self) -> int:
+        return self.value.shape[0]
 
 
 def _truthy(v) -> bool:
@@ -298,6 +321,85 @@ class Solver:
             bad = np.flatnonzero(~conv)
             raise _lib.NxNotConverged(
                 f"solve_many: columns {bad.tolist()} did not converge (relative residuals "
+                f"{rr[bad].tolist()} > rtol {self._rtol:.1e})")
+        return res
+
+    @timed("nxfx:Solver:gradient")
+    def gradient(self, p_bc, f=None, *, rows, weights=None, data=None) -> "GradientResult":
+        """Adjoint gradients of an observed-row objective for B scenarios against the matrix
+        of the last ``compute_forms`` (``nx_batch_gradient``: two batched direct solves, no
+        solution leaves the device).
+
+        ``p_bc`` / ``f``: as for :meth:`solve_many`. ``rows``: distinct indices into the
+        reference block order (the columns of ``BatchResult.x``); ``weights``: one per row
+        (default ones). ``data`` None: the linear objective ``J_j = sum_i w_i x_j[r_i]``;
+        otherwise ``(B, n_obs)`` (or ``(n_obs,)``, the same for every scenario): the least
+        squares objective ``J_j = 1/2 sum_i w_i (x_j[r_i] - d_ji)^2``. Returns a
+        :class:`GradientResult`: the objective and its derivatives with respect to every
+        edge's ``R`` and source and every boundary node's pressure.
+
+        It runs where ``solve_many`` takes its batched path; elsewhere -- several ranks,
+        general degrees, ``ksp_type="minres"``, ``pc_type="none"``, the lumped mass -- it
+        raises ``NotImplementedError`` (there is no host fallback). The reference has no
+        counterpart."""
+        if self._closed:
+            raise RuntimeError("the solver has been destroyed")
+        asm = self.assembler
+        if getattr(asm, "_coefficients", None) is None:
+            raise RuntimeError("compute_forms() must be called before gradient()")
+        if getattr(asm, "_nranks", 1) > 1:
+            raise NotImplementedError("gradient runs on one rank")
+        if tuple(asm.degrees) != (1, 0):
+            raise NotImplementedError(
+                f"gradient needs the P1/DG0 discretisation, not degrees {tuple(asm.degrees)}")
+        if not self._direct:
+            raise NotImplementedError("gradient needs the direct solve (ksp_type='preonly'), "
+                                      "not MINRES")
+        if not self._pc:
+            raise NotImplementedError("gradient needs the tree decomposition (pc_type != 'none')")
+        if not self._pc_exact:
+            raise NotImplementedError("gradient needs the consistent mass (pc_mass='lumped' "
+                                      "is not exact)")
+        edge_bc, edge_f, f_const = asm.scenario_coefficients(p_bc, f)
+        B = edge_bc.shape[0]
+        h = asm.handle
+        rows = np.asarray(rows)
+        if rows.ndim != 1 or rows.size < 1 or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError("rows must be a 1-D array of at least one integer index")
+        if rows.min() < 0 or rows.max() >= h.n_rows:
+            raise ValueError(f"rows must lie in [0, {h.n_rows})")
+        if np.unique(rows).size != rows.size:
+            raise ValueError("rows must be distinct")
+        w = np.ones(rows.size) if weights is None else np.asarray(weights, dtype=np.float64)
+        if w.shape != (rows.size,):
+            raise ValueError("weights must have one value per observed row")
+        if data is not None:
+            data = np.asarray(data, dtype=np.float64)
+            if data.shape == (rows.size,):
+                data = np.broadcast_to(data, (B, rows.size))
+            if data.shape != (B, rows.size):
+                raise ValueError(f"data must be ({B}, {rows.size}) or ({rows.size},)")
+        self._configure()
+        if not asm.lhs_current:  # the matrix of the last compute_forms (its R), values only
+            asm.assemble(assemble_lhs=True, assemble_rhs=False)
+        if not h.batch_supported():
+            raise NotImplementedError("gradient: the batched direct solve does not apply to this "
+                                      "handle (nx_batch_supported)")
+        dev_rows = asm.block_order_rows()[rows]
+        value, gR, gbc, gf, it, rr, conv = h.batch_gradient(
+            edge_bc, edge_f, f_const, self._rtol, rows=dev_rows, weights=w, data=data)
+        # edge slots -> graph.edges() order, flux end rows -> boundary nodes (gathers: every
+        # output is copied out of the handle's page-locked buffer, which the next call of this
+        # batch size then reuses)
+        slot, node_idx, node_sign = asm.gradient_maps()
+        dR = np.take(gR, slot, axis=1)
+        df = np.take(gf, slot, axis=1)
+        dp_bc = np.take(gbc.reshape(B, -1), node_idx, axis=1) * node_sign
+        res = GradientResult(value.copy(), dR, df, dp_bc, it, rr, conv, h.batch_info())
+        if self._raise and not conv.all():
+            bad = np.flatnonzero(~conv.all(axis=1))
+            raise _lib.NxNotConverged(
+                f"gradient: columns {bad.tolist()} did not converge (relative residuals "
                 f"{rr[bad].tolist()} > rtol {self._rtol:.1e})")
         return res
 

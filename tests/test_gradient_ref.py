@@ -1,0 +1,66 @@
+"""The CPU adjoint (tests/gradient_ref.py) against central finite differences of the oracle's
+own forward solve, before it is trusted as the yardstick of tests/test_gpu_gradient.py.
+
+Differences in every ``R_e`` (step ``1e-5 R_e``), every boundary node's ``p_bc`` and every
+``f_e`` (step ``1e-3``: x is linear in both, so J is at most quadratic and the central
+difference has no truncation error). Bar: 1e-7 of ``max |g|`` per gradient (the R differences'
+truncation is ~1e-10 and their rounding ~1e-11 of it; 7e-10 was observed)."""
+
+import numpy as np
+import pytest
+
+from cases import CASES, CYCLIC, p_y
+from gradient_ref import AdjointRef, forward, objective
+from networks_fenicsx_amd import NetworkMesh
+from oracle import nx_oracle as O
+
+BAR = 1e-7
+
+
+def _setup(case):
+    if case in CASES:
+        make, N, strategy, pbc = CASES[case]
+    else:
+        (make, N), strategy, pbc = CYCLIC[case], None, p_y
+    m = NetworkMesh(make(), N=N, color_strategy=strategy)
+    src, dst = m.edges
+    P = O.build_problem(m.node_coordinates, src, dst, N, m.edge_colors)
+    E = m.num_edges
+    R = 0.5 + (np.arange(E) % 3) / 2.0
+    f = 0.1 + 0.02 * (np.arange(E) % 5)
+    pb = np.asarray(pbc(P.pos3.T.copy()), dtype=np.float64)
+    return P, R, f, pb
+
+
+@pytest.mark.parametrize("case", ["Y_N4", "edge_info_N10"])
+@pytest.mark.parametrize("kind", ["linear", "lsq"])
+def test_adjoint_matches_finite_differences(case, kind):
+    P, R, f, pb = _setup(case)
+    rng = np.random.default_rng(3)
+    rows = rng.choice(P.n_dofs, size=12, replace=False)
+    w = 0.5 + rng.random(12)
+    data = None if kind == "linear" else rng.standard_normal(12)
+    g = AdjointRef(P, R).gradient(pb, f, rows, w, data)
+
+    def J(pb_, f_, R_):
+        return objective(forward(P, pb_, f_, R_), rows, w, data)
+
+    assert g["value"] == pytest.approx(J(pb, f, R), rel=1e-13, abs=1e-15)
+    E = P.src.size
+    fd_R = np.zeros(E)
+    fd_f = np.zeros(E)
+    for e in range(E):
+        d = np.zeros(E)
+        d[e] = 1e-5 * R[e]
+        fd_R[e] = (J(pb, f, R + d) - J(pb, f, R - d)) / (2 * d[e])
+        d[e] = 1e-3
+        fd_f[e] = (J(pb, f + d, R) - J(pb, f - d, R)) / 2e-3
+    fd_p = np.zeros(pb.size)
+    for v in np.concatenate([P.leaf_in, P.root_out]):
+        d = np.zeros(pb.size)
+        d[v] = 1e-3
+        fd_p[v] = (J(pb + d, f, R) - J(pb - d, f, R)) / 2e-3
+    for name, fd in (("dR", fd_R), ("df", fd_f), ("dp_bc", fd_p)):
+        err = np.abs(g[name] - fd).max() / np.abs(fd).max()
+        print(f"{case} {kind} {name}: {err:.2e} of max|g|")
+        assert err <= BAR, (name, err)
