@@ -599,6 +599,16 @@ int nx_get_direct_sup(nx_network_t* h, int32_t* sup);
  * decomposition and per contents of R: new boundary values or a new source do not rebuild
  * it). Either pointer may be NULL. Replaces nothing in the reference. */
 int nx_get_direct_dense(nx_network_t* h, int32_t* ran, int32_t* builds);
+/* The CSR values kept across assemblies while R is unchanged (one rank, P1/DG0; DESIGN.md
+ * section 3c, round 8): the values depend on the geometry, N and R alone, so once a launch has
+ * written all of them for the resident R, later assemblies and fused steps store only the rhs
+ * (NXHIP_KEEP_VALUES=0, read per solve, makes every one store them). *last_step_kept = 1 when
+ * the last assembly launch or fused step that was asked for the matrix left the values in
+ * device memory alone; *value_writes = how many launches of this handle have written them.
+ * R set to new contents -- changed and changed back included -- is written again once.
+ * Either pointer may be NULL. Replaces the caller-side choice between the reference's
+ * assemble_lhs and assemble_rhs (assembly.py:333-358, solver.py:101). */
+int nx_get_values_kept(nx_network_t* h, int32_t* last_step_kept, int64_t* value_writes);
 /* (path 2: the (k, 0) condensed route of nx_fe_set_direct; path 4: the continuous-pressure
  * node-condensed route of nx_fe_set_cp; path 3: several ranks, the
  * exchange step k_dir_xr / k_dir_xg, one launch per rank.)

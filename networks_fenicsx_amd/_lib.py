@@ -77,6 +77,7 @@ _SIGS = {
     "nx_get_direct_path": (C.c_int, [_h, _pi32]),
     "nx_get_direct_sup": (C.c_int, [_h, _pi32]),
     "nx_get_direct_dense": (C.c_int, [_h, _pi32, _pi32]),
+    "nx_get_values_kept": (C.c_int, [_h, _pi32, _pi64]),
     "nx_debug_set_wait_polls": (C.c_int, [_h, C.c_uint32]),
     "nx_debug_xr_rehearse": (C.c_int, [_h, _f64, _i32, _pd]),
     "nx_reset_profile": (C.c_int, [_h]),
@@ -585,6 +586,15 @@ class Handle:
         r, b = C.c_int32(0), C.c_int32(0)
         check(lib().nx_get_direct_dense(self.ptr, C.byref(r), C.byref(b)))
         return {"ran": bool(r.value), "builds": int(b.value)}
+
+    def values_kept(self) -> dict:
+        """The CSR values kept while R is unchanged (nx_get_values_kept; DESIGN.md section 3c,
+        round 8): ``kept`` -- the last assembly or fused step left the values in device memory
+        alone (it stored the rhs only); ``writes`` -- how many launches of this handle have
+        written them."""
+        k, w = C.c_int32(0), C.c_int64(0)
+        check(lib().nx_get_values_kept(self.ptr, C.byref(k), C.byref(w)))
+        return {"kept": bool(k.value), "writes": int(w.value)}
 
     def direct_path(self) -> str:
         """What the last direct solve ran (nx_get_direct_path): ``"fused"`` (k_dir_step, one

@@ -4085,7 +4085,9 @@ __device__ __forceinline__ void dir_chain_asm(const PcArgs& pa, const DirStep& d
 // over the lanes: whole cache lines per store; the tensors of the entry's cells fetched by
 // shuffles, ~2x the issue time) -- the workgroups that store while waiting for the top part,
 // where the issue time is hidden and partially written lines would cost HBM traffic.
-template <int W, int CPL, bool UNIT = false>
+// KV (k_dir_step_kv): the CSR segment is left alone -- the values in device memory are
+// already those of this R (nx_network::val_version) -- and only the rhs is stored.
+template <int W, int CPL, bool UNIT = false, bool KV = false>
 __device__ __forceinline__ void dir_chain_store(const PcArgs& pa, const DirStep& da, bool active,
                                                 const DirLane<W, CPL>& L) {
   ChainLane<W, CPL> ch;
@@ -4108,7 +4110,7 @@ __device__ __forceinline__ void dir_chain_store(const PcArgs& pa, const DirStep&
     if (!NX_LEDGER(da, 2)) da.rhs[ch.dof_qN] = L.bN;
     if (da.dq) da.dq[qb + (flip ? 0 : N)] = ch.rhoN;
   }
-  if (NX_LEDGER(da, 1)) return;
+  if (KV || NX_LEDGER(da, 1)) return;
   // the CSR segment, each lane its own cells' rows (edge order: cell g owns p_g's 2 entries
   // and q_{g+1}'s 5 -- q_N's 3 + s_dst for g = N - 1 -- from q0len + 7 g on; cell 0 also the
   // q_0 row): values as decode_entry lists them, the next edge cell's masses from the
@@ -5541,7 +5543,8 @@ __device__ __forceinline__ void dir_sup_store_x(const PcArgs& pa, const DirStep&
 // group) or re-assembled from their records (chain cb + group - g0 per pass). Only the lane
 // groups [g0, g1) store (the others -- whole waves -- stay free of outstanding stores, so their
 // polls and loads are not queued behind them).
-template <int W, int CPL, bool UNIT = false>
+// KV: without the values (the multiplier rows' +-1 entries, the chains' CSR segments).
+template <int W, int CPL, bool UNIT = false, bool KV = false>
 __device__ __forceinline__ void dir_stores_v2(const PcArgs& pa, const DirStep& da, int jb, bool lm,
                                               int cs, int ce, bool keep, DirLane<W, CPL>& L,
                                               int g0 = 0, int g1 = kPcThreads / W) {
@@ -5549,16 +5552,16 @@ __device__ __forceinline__ void dir_stores_v2(const PcArgs& pa, const DirStep& d
   const int grp = (int)threadIdx.x / W;
   const bool mine = grp >= g0 && grp < g1;
   if (lm && mine) {
-    const int64_t nlm = da.nnz_lm > da.B ? da.nnz_lm : da.B;
+    const int64_t nlm = KV ? da.B : da.nnz_lm > da.B ? da.nnz_lm : da.B;
     const int nthr = (g1 - g0) * W;
     for (int k = (int)threadIdx.x - g0 * W; k < kPcThreads; k += nthr)
       for (int64_t i = (int64_t)jb * kPcThreads + k; i < nlm; i += (int64_t)nj * kPcThreads) {
-        if (i < da.nnz_lm && !NX_LEDGER(da, 16)) da.val_lm[i] = da.lm_val[i];
+        if (!KV && i < da.nnz_lm && !NX_LEDGER(da, 16)) da.val_lm[i] = da.lm_val[i];
         if (i < da.B && !NX_LEDGER(da, 16)) da.rhs_lm[i] = 0.0;
       }
   }
   if (keep) {
-    if (mine) dir_chain_store<W, CPL, UNIT>(pa, da, cs + grp < ce, L);
+    if (mine) dir_chain_store<W, CPL, UNIT, KV>(pa, da, cs + grp < ce, L);
     return;
   }
   const int per = g1 - g0;
@@ -5568,7 +5571,7 @@ __device__ __forceinline__ void dir_stores_v2(const PcArgs& pa, const DirStep& d
       ChainRec r;
       chain_rec_load(da, c, c < ce, r);
       dir_chain_asm_rec<W, CPL>(pa, r, c < ce, L);
-      dir_chain_store<W, CPL, UNIT>(pa, da, c < ce, L);
+      dir_chain_store<W, CPL, UNIT, KV>(pa, da, c < ce, L);
     }
   }
 }
@@ -5929,9 +5932,16 @@ __device__ __forceinline__ bool dir_publish_xr(const PcArgs& pa, const DirStep& 
 // layout, direct mode's content), the arrival counter itself is the hand-off, and every
 // workgroup forms the top values it needs as dot products of rows of G = the inverse of the
 // top part's Schur matrix (ensure_top_inverse) with the summed inputs.
-template <int W, int CPL, bool XR, bool SUP, bool DENSE = false>
+// KV (k_dir_step_kv, the dense step while the CSR values in device memory are those of the
+// resident R): the same step without the value stores (dir_stores_v2 / dir_chain_store); every
+// wave stores its rhs share in the wait, so the kernel's tail re-assembles nothing; rhs, x,
+// posts, partials, the published state and all the arithmetic as they are. No step reads
+// da.val or da.val_lm (the residual is formed from the lanes' registers, the multiplier rows'
+// from the posts), so nothing else changes.
+template <int W, int CPL, bool XR, bool SUP, bool DENSE = false, bool KV = false>
 __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& da, int job) {
   static_assert(!DENSE || (SUP && !XR), "the dense top: one rank, superposition");
+  static_assert(!KV || DENSE, "the values-free step: the dense top's");
   extern __shared__ double dsm[];
   __shared__ int sFlag, sTopJob, sIdx;
   int* stash = reinterpret_cast<int*>(dsm);  // the job's statics (fixed offsets)
@@ -6087,8 +6097,10 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
     sup_s = true;
     NX_DSTAMP(20);
     // own stores in the wait, but not wave 0's (it polls and loads: nothing queued before them)
-    dir_stores_v2<W, CPL, true>(pa, da, job, true, c0, c1, true, L, gF);
-    defer_free = true;
+    // (KV: wave 0's too -- its rhs share is 2 KB, nothing to queue behind; the kernel's tail
+    // then needs no re-assembly: measured 1.3 us of kernel time, r08g)
+    dir_stores_v2<W, CPL, true, KV>(pa, da, job, true, c0, c1, true, L, KV ? 0 : gF);
+    defer_free = !KV;
     NX_DSTAMP(8);
     if (threadIdx.x < 64) {
       int ok = 0;
@@ -6385,9 +6397,9 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
       dir_chain_asm_rec<W, CPL>(pa, rec, lane_on, L);
     }
     if (late_store) {  // one job: the top solver's own
-      dir_stores_v2<W, CPL>(pa, da, job, true, c0, c1, true, L);
+      dir_stores_v2<W, CPL, false, KV>(pa, da, job, true, c0, c1, true, L);
     } else {  // the free waves' chains
-      dir_chain_store<W, CPL>(pa, da, lane_on, L);
+      dir_chain_store<W, CPL, false, KV>(pa, da, lane_on, L);
     }
   }
   vm_drain();
@@ -6399,6 +6411,13 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
 template <int W, int CPL, bool SUP = false>
 __global__ __launch_bounds__(kPcThreads) void k_dir_step(PcArgs pa, DirStep da) {
   dir_step_body<W, CPL, false, SUP, SUP>(pa, da, blockIdx.x);
+}
+
+// the dense step without the CSR value stores (launch_dstep_wc: the values in device memory
+// are those of the resident R); its own name: profiles and bench.py's counters tell them apart
+template <int W, int CPL>
+__global__ __launch_bounds__(kPcThreads) void k_dir_step_kv(PcArgs pa, DirStep da) {
+  dir_step_body<W, CPL, false, true, true, true>(pa, da, blockIdx.x);
 }
 
 // superposition with the top part solved by the last workgroup to arrive (no top part, a top
@@ -7715,6 +7734,18 @@ struct nx_network {
   std::vector<double> R_host;  // the last R (E entries)
   int64_t r_version = 0, g_version = -1;
   int g_builds = 0;
+  // the device CSR values' validity stamp (round 8): h->val holds the COMPLETE values of R
+  // version val_version (-1: not known to). The rule: set to the r_version a launch ran with
+  // only after a launch that writes every value -- launch_assembly with lhs (stream-ordered
+  // ahead of every reader), a storing fused step once its state was published; reset to -1
+  // before a storing fused step is launched (one that gives up leaves part of its stores out);
+  // never set by a debug build's step whose ledger drops the values (bits 1, 16), by a handle
+  // of several ranks (group, communicator) or of general degrees (fe). R reaches the device
+  // only through nx_set_coefficients' bit-for-bit compare (r_version), so "values current"
+  // is val_version == r_version (values_current); R changed and changed back counts as new.
+  int64_t val_version = -1;
+  int last_kept = 0;       // the last assembly launch or fused step left the values alone
+  int64_t val_writes = 0;  // launches of this handle that wrote them (nx_get_values_kept)
   bool last_sup = false;    // the last one-launch step ran the superposition instantiation
   unsigned* d_tsync = nullptr;  // k_dir_team_up's arrival counter (several ranks; pc_bufs)
   bool need_r = false;     // the last pass kept no residual: a refinement step forms it first
@@ -10463,12 +10494,30 @@ NX_API int nx_set_source(nx_network_t* h, const double* edge_f) {
 
 namespace {
 
+// The CSR values kept while R is unchanged (nx_network::val_version): the handles that stamp
+// (one rank, P1/DG0), and whether an assembly may leave the values alone -- they are those of
+// the resident R, and NXHIP_KEEP_VALUES=0 (read per solve: tests and the A/B switch it) does
+// not force the stores.
+bool keep_stamps(const nx_network* h) {
+  return !h->fe && h->group == nullptr && !proc_rank(h) && h->nranks == 1;
+}
+bool values_current(const nx_network* h) {
+  if (!keep_stamps(h) || h->val_version != h->r_version) return false;
+  const char* e = std::getenv("NXHIP_KEEP_VALUES");
+  return e == nullptr || std::atoi(e) != 0;
+}
+
 // Launch the assembly kernel (values and / or rhs; the lumped mass dq with the values unless
 // dq says otherwise) on stream s (the handle's by default).
 int launch_assembly(nx_network* h, int lhs, int rhs, int dq = -1, hipStream_t s = nullptr) {
   if (!s) s = h->stream;
   if (dq < 0) dq = lhs;
   if (dq) h->dq_stale = false;
+  if (lhs) {  // every value, stream-ordered ahead of its readers: the stamp (val_version)
+    h->val_writes += 1;
+    h->last_kept = 0;
+    h->val_version = keep_stamps(h) && s == h->stream ? h->r_version : -1;
+  }
   if (h->fe) {  // general degrees: one thread per nonzero / rhs row
     FeArgs a{h->edge_x, h->edge_R, h->edge_bc, h->f, h->edge_f, h->N, h->fe_kind, h->fe_tval,
              h->fe_aptr, h->fe_aidx, h->fe_aent, h->fe_bptr, h->fe_bidx, h->fe_bent,
@@ -10524,12 +10573,24 @@ int ensure_dq(nx_network* h) {
   return launch_assembly(h, 0, 0, 1);
 }
 
+// A pending assembly of values and rhs while the values in device memory are those of the
+// resident R: the same launch without the values (the kernels honour lhs; the lumped mass dq
+// as with them). An assembly of the values alone launches as it did.
+int launch_assembly_kept(nx_network* h, int lhs, int rhs) {
+  if (lhs && rhs && values_current(h)) {
+    CHECK(launch_assembly(h, 0, rhs, 1));
+    h->last_kept = 1;
+    return NX_OK;
+  }
+  return launch_assembly(h, lhs, rhs);
+}
+
 int flush_assembly(nx_network* h) {
   if (!h || !(h->pend_lhs || h->pend_rhs)) return NX_OK;
   const int lhs = h->pend_lhs, rhs = h->pend_rhs;
   h->pend_lhs = h->pend_rhs = 0;
   CHECK(set_device(h));
-  CHECK(launch_assembly(h, lhs, rhs));
+  CHECK(launch_assembly_kept(h, lhs, rhs));
   if (h->prof && (h->E > 0 || h->fe)) {  // profiling: the assembly kernel's own events
     HIPCALL(hipEventSynchronize(h->ev[1]));
     float ms = 0.f;
@@ -10795,8 +10856,12 @@ void opt_in_lds(const void* fn, int bytes);
 template <int CPL>
 bool sup_launch(const DirStep& da);
 size_t dense_lds_extra(const nx_network* h);
+// Returns whether the launched step stores the CSR values (every instantiation but the dense
+// <8, 2> step's values-free one, k_dir_step_kv, which run_dstep asks for with kv while the
+// values in device memory are current). A storing step's stamp is reset here, before its
+// launch (nx_network::val_version; run_dstep sets it again once the state was published).
 template <int W, int CPL>
-void launch_dstep_wc(nx_network* h, double rtol, bool prof) {
+bool launch_dstep_wc(nx_network* h, double rtol, bool prof, bool kv) {
   DirStep da = dir_args(h, rtol);
   const bool sup = sup_launch<CPL>(da);
   h->last_sup = sup;
@@ -10811,23 +10876,33 @@ void launch_dstep_wc(nx_network* h, double rtol, bool prof) {
     lds += dense_lds_extra(h);
   }
   const hipEvent_t e0 = prof ? h->dev[0] : nullptr, e1 = prof ? h->dev[1] : nullptr;
+  if constexpr (W == 8 && CPL == 2) {
+    if (dense && kv) {
+      opt_in_lds(reinterpret_cast<const void*>(&k_dir_step_kv<W, CPL>), kDirLdsMax);
+      hipExtLaunchKernelGGL((k_dir_step_kv<W, CPL>), dim3(h->pc_jobs), dim3(kPcThreads), lds,
+                            h->stream, e0, e1, 0, h->pa, da);
+      return false;
+    }
+  }
+  h->val_version = -1;
   if constexpr (CPL <= 2) {
     if (dense) {
       opt_in_lds(reinterpret_cast<const void*>(&k_dir_step<W, CPL, true>), kDirLdsMax);
       hipExtLaunchKernelGGL((k_dir_step<W, CPL, true>), dim3(h->pc_jobs), dim3(kPcThreads), lds,
                             h->stream, e0, e1, 0, h->pa, da);
-      return;
+      return true;
     }
     if (sup) {
       opt_in_lds(reinterpret_cast<const void*>(&k_dir_step_ts<W, CPL>), kDirLdsMax);
       hipExtLaunchKernelGGL((k_dir_step_ts<W, CPL>), dim3(h->pc_jobs), dim3(kPcThreads), lds,
                             h->stream, e0, e1, 0, h->pa, da);
-      return;
+      return true;
     }
   }
   opt_in_lds(reinterpret_cast<const void*>(&k_dir_step<W, CPL>), kDirLdsMax);
   hipExtLaunchKernelGGL((k_dir_step<W, CPL>), dim3(h->pc_jobs), dim3(kPcThreads), lds, h->stream,
                         e0, e1, 0, h->pa, da);
+  return true;
 }
 
 // Several ranks: k_dir_team_up, the assembly + up sweep + top part of one rank (half 0 of
@@ -10905,20 +10980,36 @@ int ensure_top_inverse(nx_network* h) {
 int run_dstep(nx_network* h, double rtol, bool prof) {
   h->dense_now = dstep_dense_on(h);
   if (h->dense_now) CHECK(ensure_top_inverse(h));
+  // (ensure_top_inverse's dq-only assembly launch writes no values: the stamp stands)
+  const bool kv = values_current(h);
+  const int64_t rv = h->r_version;
+  bool stored = true;
   switch (h->dstep_variant) {
-    case 0: launch_dstep_wc<16, 1>(h, rtol, prof); break;
-    case 1: launch_dstep_wc<16, 2>(h, rtol, prof); break;
-    case 2: launch_dstep_wc<16, 4>(h, rtol, prof); break;
-    case 3: launch_dstep_wc<64, 2>(h, rtol, prof); break;
-    case 5: launch_dstep_wc<8, 2>(h, rtol, prof); break;
-    case 7: launch_dstep_wc<8, 4>(h, rtol, prof); break;
-    case 10: launch_dstep_wc<8, 3>(h, rtol, prof); break;
-    default: launch_dstep_wc<64, 4>(h, rtol, prof); break;
+    case 0: stored = launch_dstep_wc<16, 1>(h, rtol, prof, kv); break;
+    case 1: stored = launch_dstep_wc<16, 2>(h, rtol, prof, kv); break;
+    case 2: stored = launch_dstep_wc<16, 4>(h, rtol, prof, kv); break;
+    case 3: stored = launch_dstep_wc<64, 2>(h, rtol, prof, kv); break;
+    case 5: stored = launch_dstep_wc<8, 2>(h, rtol, prof, kv); break;
+    case 7: stored = launch_dstep_wc<8, 4>(h, rtol, prof, kv); break;
+    case 10: stored = launch_dstep_wc<8, 3>(h, rtol, prof, kv); break;
+    default: stored = launch_dstep_wc<64, 4>(h, rtol, prof, kv); break;
   }
   HIPCALL(hipGetLastError());
   h->dstep_epoch += 1;
   h->seq += 1;
-  return wait_published(h);
+  CHECK(wait_published(h));
+  // published: every workgroup passed both hand-offs, so a storing step's values are all out
+  // (the kernel's tail stores are stream-ordered ahead of every later reader)
+  if (stored) {
+    bool whole = keep_stamps(h);
+#ifdef NX_PHASE_TIMING
+    if (const char* e = std::getenv("NXHIP_LEDGER")) whole = whole && (std::atoi(e) & 17) == 0;
+#endif
+    h->val_version = whole ? rv : -1;
+    h->val_writes += 1;
+  }
+  h->last_kept = stored ? 0 : 1;
+  return NX_OK;
 }
 
 int launch_direct(nx_network* h, double rtol, int refine, bool prof = false) {
@@ -11704,7 +11795,10 @@ int solve_direct(const Team& t, double rtol, int32_t* iters, double* relres,
     with_asm = true;
     for (int r = 0; r < t.P; ++r) with_asm = with_asm && t.hs[r]->pend_lhs && t.hs[r]->pend_rhs;
   }
-  if (with_asm && dstep_on(h)) {  // the fused step: assembly + solve + check in one launch
+  // one rank: a pending rhs alone heads the fused step too while the values in device memory
+  // are those of the resident R (assemble(lhs = False, rhs = True) after a current matrix)
+  const bool rhs_asm = !multi && !with_asm && h->pend_rhs && !h->pend_lhs && values_current(h);
+  if ((with_asm || rhs_asm) && dstep_on(h)) {  // the fused step: assembly + solve + check in one launch
     const int rc = run_dstep(h, rtol, prof1);
     if (rc == NX_OK) {
       h->pend_lhs = h->pend_rhs = 0;
@@ -11779,7 +11873,7 @@ int solve_direct(const Team& t, double rtol, int32_t* iters, double* relres,
   // the join, more than the 17 us assembly they would hide; r02 trace)
   auto body = [&](int refine, bool asmb) -> int {
     if (multi) return launch_direct_team(t, rtol, refine, asmb);
-    if (asmb) CHECK(launch_assembly(h, 1, 1));
+    if (asmb) CHECK(launch_assembly_kept(h, 1, 1));  // (one rank: the values kept while current)
     return launch_direct(h, rtol, refine);
   };
   // several ranks: graph replay; one rank: the launches issued directly
@@ -13487,6 +13581,14 @@ NX_API int nx_get_direct_dense(nx_network_t* h, int32_t* ran, int32_t* builds) {
   if (!h) return fail(NX_ERR_ARG, "null handle");
   if (ran) *ran = h->last_dense ? 1 : 0;
   if (builds) *builds = h->g_builds;
+  return NX_OK;
+}
+
+NX_API int nx_get_values_kept(nx_network_t* h, int32_t* last_step_kept, int64_t* value_writes) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  // (no flush: a deferred nx_assemble stays deferred, as for nx_get_direct_path)
+  if (last_step_kept) *last_step_kept = h->last_kept;
+  if (value_writes) *value_writes = h->val_writes;
   return NX_OK;
 }
 
