@@ -619,6 +619,18 @@ int nx_get_values_kept(nx_network_t* h, int32_t* last_step_kept, int64_t* value_
  * on this handle from then on (until the next nx_set_preconditioner). Replaces nothing in
  * the reference. */
 int nx_debug_set_wait_polls(nx_network_t* h, uint32_t polls);
+/* Test hook: the kernels' segment cross-lane helpers (seg_up / seg_down / seg_xor, their _nc
+ * variants, seg_bcast0, seg_incl_scan, seg_sum, wave_sum: DPP row moves for segments of 4, 8
+ * and 16 lanes) beside the plain __shfl* they replace, on the same input, in one launch of
+ * one 1024-thread workgroup on the current device. in_d / in_i: 1024 values, one per lane.
+ * Outputs: *n_slots slots of 1024 values each (cap_slots: what the four arrays hold; 64 is
+ * enough), new_* by the helpers and ref_* by the shuffles. Slots, for W = 4, 8, 16 in turn:
+ * for O = 1, 2, .. < W the moves up, down, xor, up_nc, down_nc; then bcast0, inclusive scan,
+ * sum; the last slot is wave_sum. The three sums are zero in the int outputs. Replaces nothing
+ * in the reference. */
+int nx_test_seg_shuffle(const double* in_d, const int32_t* in_i, int32_t cap_slots,
+                        double* new_d, double* ref_d, int32_t* new_i, int32_t* ref_i,
+                        int32_t* n_slots);
 /* Rehearsal hook: the exchange step (k_dir_xr) of group member h ALONE, reps timed launches
  * (*ms: average kernel time, HIP events on the dispatch), its two exchanges emulated from
  * the sums the group's previous graph-path direct solve left -- the per-rank time of a

@@ -80,6 +80,7 @@ _SIGS = {
     "nx_get_values_kept": (C.c_int, [_h, _pi32, _pi64]),
     "nx_debug_set_wait_polls": (C.c_int, [_h, C.c_uint32]),
     "nx_debug_xr_rehearse": (C.c_int, [_h, _f64, _i32, _pd]),
+    "nx_test_seg_shuffle": (C.c_int, [_pd, _pi32, _i32, _pd, _pd, _pi32, _pi32, _pi32]),
     "nx_reset_profile": (C.c_int, [_h]),
     "nx_bench_spmv": (C.c_int, [_h, _i32, _pd]),
     "nx_bench_spmv_cold": (C.c_int, [_h, _i32, _pi32, _pd]),

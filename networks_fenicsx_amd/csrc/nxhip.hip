@@ -460,10 +460,139 @@ __global__ __launch_bounds__(kBlock) void k_assemble(AsmArgs a) {
 
 
 // ------------------------------------------------------------------------------------
+// Cross-lane moves inside a segment of W consecutive lanes by a compile-time offset O. For
+// W = 4, 8, 16 the segment lies inside one 16-lane DPP row, and the move is a v_mov_b32_dpp
+// per half of a double: no LDS instruction (ds_bpermute), no lane-address arithmetic, no
+// lgkmcnt wait. Other widths go through __shfl*. The data moved is what __shfl_up / _down /
+// _xor (v, O, W) and __shfl(v, 0, W) return, bit for bit: seg_up / seg_down give a lane whose
+// source lies outside the segment its own value. The _nc variants leave those lanes
+// unspecified (one select less): only where the caller discards them. All of them are called
+// with the whole segment active, as the shuffles are.
+namespace dpp {
+constexpr int quad(int a, int b, int c, int d) { return a | (b << 2) | (c << 4) | (d << 6); }
+constexpr int row_shl(int n) { return 0x100 + n; }  // lane i <- lane i + n of its row
+constexpr int row_shr(int n) { return 0x110 + n; }  // lane i <- lane i - n of its row
+constexpr int row_ror(int n) { return 0x120 + n; }
+// bank = 4 lanes of a row; a lane whose bank is masked out, or whose source lies outside the
+// row, keeps old
+constexpr int kBanksLo = 0x5, kBanksHi = 0xa;  // lanes 0-3 and 8-11 / 4-7 and 12-15
+template <int CTRL, int BANKS = 0xf, class T>
+__device__ __forceinline__ T mov(T old, T v) {
+  return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xf, BANKS, false);
+}
+// the same with no old value: such a lane's result is unspecified (and no register is tied)
+template <int CTRL, class T>
+__device__ __forceinline__ T movu(T v) {
+  return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, false);
+}
+constexpr bool seg(int W) { return W == 4 || W == 8 || W == 16; }
+}  // namespace dpp
+
+template <int W, int O, class T>
+__device__ __forceinline__ T seg_up_nc(T v) {
+  static_assert(O > 0 && O < W && (O & (O - 1)) == 0, "offset: a power of two below W");
+  if constexpr (dpp::seg(W)) return dpp::movu<dpp::row_shr(O)>(v);
+  else return __shfl_up(v, O, W);
+}
+
+template <int W, int O, class T>
+__device__ __forceinline__ T seg_down_nc(T v) {
+  static_assert(O > 0 && O < W && (O & (O - 1)) == 0, "offset: a power of two below W");
+  if constexpr (dpp::seg(W)) return dpp::movu<dpp::row_shl(O)>(v);
+  else return __shfl_down(v, O, W);
+}
+
+template <int W, int O, class T>
+__device__ __forceinline__ T seg_up(T v) {
+  static_assert(O > 0 && O < W && (O & (O - 1)) == 0, "offset: a power of two below W");
+  if constexpr (W == 16) {
+    return dpp::mov<dpp::row_shr(O)>(v, v);  // (outside the row: old)
+  } else if constexpr (W == 8 && O == 4) {
+    return dpp::mov<dpp::row_shr(4), dpp::kBanksHi>(v, v);
+  } else if constexpr (W == 8) {
+    const T t = dpp::movu<dpp::row_shr(O)>(v);
+    return (int)(threadIdx.x & 7) >= O ? t : v;
+  } else if constexpr (W == 4) {
+    return dpp::movu<O == 1 ? dpp::quad(0, 0, 1, 2) : dpp::quad(0, 1, 0, 1)>(v);
+  } else {
+    return __shfl_up(v, O, W);
+  }
+}
+
+template <int W, int O, class T>
+__device__ __forceinline__ T seg_down(T v) {
+  static_assert(O > 0 && O < W && (O & (O - 1)) == 0, "offset: a power of two below W");
+  if constexpr (W == 16) {
+    return dpp::mov<dpp::row_shl(O)>(v, v);
+  } else if constexpr (W == 8 && O == 4) {
+    return dpp::mov<dpp::row_shl(4), dpp::kBanksLo>(v, v);
+  } else if constexpr (W == 8) {
+    const T t = dpp::movu<dpp::row_shl(O)>(v);
+    return (int)(threadIdx.x & 7) + O < 8 ? t : v;
+  } else if constexpr (W == 4) {
+    return dpp::movu<O == 1 ? dpp::quad(1, 2, 3, 3) : dpp::quad(2, 3, 2, 3)>(v);
+  } else {
+    return __shfl_down(v, O, W);
+  }
+}
+
+template <int W, int O, class T>
+__device__ __forceinline__ T seg_xor(T v) {
+  static_assert(O > 0 && O < W && (O & (O - 1)) == 0, "offset: a power of two below W");
+  if constexpr (!dpp::seg(W)) {
+    return __shfl_xor(v, O, W);
+  } else if constexpr (O == 1) {
+    return dpp::movu<dpp::quad(1, 0, 3, 2)>(v);  // (every lane has its source)
+  } else if constexpr (O == 2) {
+    return dpp::movu<dpp::quad(2, 3, 0, 1)>(v);
+  } else if constexpr (O == 4) {
+    // lane i <- i + 4, which is right in lanes 0-3 and 8-11; then lanes 4-7 and 12-15 <- i - 4
+    const T t = dpp::movu<dpp::row_shl(4)>(v);
+    return dpp::mov<dpp::row_shr(4), dpp::kBanksHi>(t, v);
+  } else {
+    return dpp::movu<dpp::row_ror(8)>(v);
+  }
+}
+
+// the value of the segment's lane 0 in every lane
+template <int W, class T>
+__device__ __forceinline__ T seg_bcast0(T v) {
+  if constexpr (!dpp::seg(W)) {
+    return __shfl(v, 0, W);
+  } else {
+    T t = dpp::movu<dpp::quad(0, 0, 0, 0)>(v);  // every quad: its lane 0
+    if constexpr (W == 8) t = dpp::mov<dpp::row_shr(4), dpp::kBanksHi>(t, t);
+    if constexpr (W == 16) {
+      t = dpp::mov<dpp::row_shr(4), 0x2>(t, t);  // lanes 4-7 <- 0-3
+      t = dpp::mov<dpp::row_shr(8), 0xc>(t, t);  // lanes 8-15 <- 0-7
+    }
+    return t;
+  }
+}
+
+// f(IntC<O>) for O = 1, 2, 4, ... below W: the scans' steps, their offsets compile-time (the
+// builtin wants an immediate)
+template <int O>
+struct IntC {
+  static constexpr int value = O;
+};
+template <int W, int O = 1, class F>
+__device__ __forceinline__ void seg_steps(F&& f) {
+  if constexpr (O < W) {
+    f(IntC<O>{});
+    seg_steps<W, 2 * O>(f);
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // Reductions: deterministic (fixed grid, fixed order), no atomics.
 __device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v += __shfl_xor(v, 32, 64);
+  v += __shfl_xor(v, 16, 64);
+  v += seg_xor<16, 8>(v);  // (the butterfly's order, so the sum's bits)
+  v += seg_xor<16, 4>(v);
+  v += seg_xor<16, 2>(v);
+  v += seg_xor<16, 1>(v);
   return v;
 }
 
@@ -1260,19 +1389,22 @@ __device__ __forceinline__ int lane_of() {
 template <int W>
 __device__ __forceinline__ double seg_incl_scan(double v) {
   const int l = threadIdx.x & (W - 1);
-#pragma unroll
-  for (int o = 1; o < W; o <<= 1) {
-    const double t = __shfl_up(v, o, W);
-    if (l >= o) v += t;
-  }
+  seg_steps<W>([&](auto o) {
+    constexpr int O = decltype(o)::value;
+    const double t = seg_up_nc<W, O>(v);  // (_nc: lanes below O do not take t)
+    if (l >= O) v += t;
+  });
   return v;
 }
 
-template <int W>
+template <int W, int O = W / 2>
 __device__ __forceinline__ double seg_sum(double v) {
-#pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, W);
-  return v;
+  if constexpr (O > 0) {
+    v += seg_xor<W, O>(v);
+    return seg_sum<W, O / 2>(v);
+  } else {
+    return v;
+  }
 }
 
 // Cells / fluxes of one chain seen by one lane: chain order runs top -> bottom.
@@ -1367,15 +1499,16 @@ __device__ __forceinline__ void chain_mass_solve(const PcArgs& pa, const ChainLa
       B = -lk[t] * B + v[t];
       A = -lk[t] * A;
     }
-#pragma unroll
-  for (int o = 1; o < W; o <<= 1) {
-    const double Ap = __shfl_up(A, o, W), Bp = __shfl_up(B, o, W);
-    if (l >= o) {
+  seg_steps<W>([&](auto o) {
+    constexpr int O = decltype(o)::value;
+    // (_nc: lanes below O do not take Ap, Bp)
+    const double Ap = seg_up_nc<W, O>(A), Bp = seg_up_nc<W, O>(B);
+    if (l >= O) {
       B = A * Bp + B;
       A = A * Ap;
     }
-  }
-  double y = __shfl_up(B, 1, W);  // y at the end of the previous lane (0 before q_0)
+  });
+  double y = seg_up_nc<W, 1>(B);  // y at the end of the previous lane (0 before q_0: _nc)
   if (l == 0) y = 0.0;
 #pragma unroll
   for (int t = 0; t < NE; ++t)
@@ -1393,15 +1526,16 @@ __device__ __forceinline__ void chain_mass_solve(const PcArgs& pa, const ChainLa
       B = iu[t] * (v[t] - B);
       A = -iu[t] * A;
     }
-#pragma unroll
-  for (int o = 1; o < W; o <<= 1) {
-    const double An = __shfl_down(A, o, W), Bn = __shfl_down(B, o, W);
-    if (l + o < W) {
+  seg_steps<W>([&](auto o) {
+    constexpr int O = decltype(o)::value;
+    // (_nc: the last O lanes do not take An, Bn)
+    const double An = seg_down_nc<W, O>(A), Bn = seg_down_nc<W, O>(B);
+    if (l + O < W) {
       B = A * Bn + B;
       A = A * An;
     }
-  }
-  double x = __shfl_down(B, 1, W);  // x at the start of the next lane (0 after q_N)
+  });
+  double x = seg_down_nc<W, 1>(B);  // x at the start of the next lane (0 after q_N: _nc)
   if (l == W - 1) x = 0.0;
   const double imo = 1.0 / ch.mo;
 #pragma unroll
@@ -1692,7 +1826,9 @@ __device__ __forceinline__ void direct_cell_inputs(const PcArgs& pa, const Chain
   chain_mass_solve<W, CPL>(pa, ch, bq, bqN, yv);
   const int N = pa.N;
   const int l = lane_of<W>();
-  const double nxt0 = __shfl_down(yv[0], 1, W);
+  // (_nc: the segment's last lane holds chain cell W CPL - 1 >= N - 1 in its last element,
+  // whose next flux is q_N or which is not valid: it never reads nxt0)
+  const double nxt0 = seg_down_nc<W, 1>(yv[0]);
 #pragma unroll
   for (int t = 0; t < CPL; ++t) {
     const int k = l * CPL + t;
@@ -1700,7 +1836,7 @@ __device__ __forceinline__ void direct_cell_inputs(const PcArgs& pa, const Chain
     const double d = yv[t] - ynext;
     vc[t] = ch.valid[t] ? (flip ? -d : d) - vc[t] : 0.0;
   }
-  const double y0 = __shfl(yv[0], 0, W), yN = __shfl(yv[CPL], (N - 1) / CPL, W);
+  const double y0 = seg_bcast0<W>(yv[0]), yN = __shfl(yv[CPL], (N - 1) / CPL, W);
   ytop = flip ? y0 : -y0;  // top = chain position 0 = the edge's source unless flipped
   ybot = flip ? -yN : yN;
 }
@@ -1728,7 +1864,7 @@ __device__ __forceinline__ void direct_flux_cons(const ChainLane<W, CPL>& ch, in
   for (int t = 0; t < CPL; ++t)
     if (ch.valid[t]) loc += bc[t];
   const double incl = seg_incl_scan<W>(loc);
-  double run = __shfl_up(incl, 1, W);  // cells before this lane's first
+  double run = seg_up_nc<W, 1>(incl);  // cells before this lane's first (_nc: lane 0 takes 0)
   if (l == 0) run = 0.0;
   double P[CPL + 1];
   double s1 = 0.0, s2 = 0.0;
@@ -1811,9 +1947,11 @@ __device__ __forceinline__ void direct_residual(const PcArgs& pa, const ChainLan
 #pragma unroll
   for (int t = 0; t < CPL; ++t) md[t] = 2.0 * mo[t];
   // cell k - 1 of element 0 and flux k + 1 of the last element live in the neighbour lanes
-  const double mdP = __shfl_up(md[CPL - 1], 1, W), moP = __shfl_up(mo[CPL - 1], 1, W);
-  const double xcP = __shfl_up(xc[CPL - 1], 1, W), xqP = __shfl_up(xq[CPL - 1], 1, W);
-  const double xqX = __shfl_down(xq[0], 1, W);
+  // (_nc: the values from below are read at k > 0 in element 0, so not by lane 0; xqX by a
+  // valid last element whose next flux is not q_N, so not by the segment's last lane)
+  const double mdP = seg_up_nc<W, 1>(md[CPL - 1]), moP = seg_up_nc<W, 1>(mo[CPL - 1]);
+  const double xcP = seg_up_nc<W, 1>(xc[CPL - 1]), xqP = seg_up_nc<W, 1>(xq[CPL - 1]);
+  const double xqX = seg_down_nc<W, 1>(xq[0]);
 #pragma unroll
   for (int t = 0; t < CPL; ++t) {
     if (!ch.valid[t]) continue;
@@ -3982,7 +4120,8 @@ __device__ __forceinline__ void dir_lane_chain(const PcArgs& pa, const DirLane<W
 #pragma unroll
   for (int t = 0; t < CPL; ++t) md[t] = L.md(t);
   const double* mo = L.mo;
-  const double mdP = __shfl_up(md[CPL - 1], 1, W), moP = __shfl_up(mo[CPL - 1], 1, W);
+  // (_nc: cell k - 1's masses are read at k > 0 in element 0, so not by lane 0)
+  const double mdP = seg_up_nc<W, 1>(md[CPL - 1]), moP = seg_up_nc<W, 1>(mo[CPL - 1]);
 #pragma unroll
   for (int t = 0; t < CPL; ++t) {
     const int k = l * CPL + t;
@@ -4023,7 +4162,9 @@ __device__ __forceinline__ void dir_lane_chain(const PcArgs& pa, const DirLane<W
     if (ch.has_last) ch.rhoN = flip ? mdl + mol : mol + mdl;
   }
   // ChainLane::setup's mo: the edge's q_0 lumped mass / 3 (chain flux 0, or N when flipped)
-  const double dq0 = flip ? __shfl(ch.rhoN, (N - 1) / CPL, W) : __shfl(ch.rho[0], 0, W);
+  // (both moves before the choice: every lane of the segment takes part in each)
+  const double dqN = __shfl(ch.rhoN, (N - 1) / CPL, W), dqF = seg_bcast0<W>(ch.rho[0]);
+  const double dq0 = flip ? dqN : dqF;
   ch.mo = active ? dq0 / 3.0 : 1.0;
   ch.finish();
 }
@@ -4148,8 +4289,10 @@ __device__ __forceinline__ void dir_chain_store(const PcArgs& pa, const DirStep&
   }
   const int s0 = L.s, q0len = 3 + s0;
   const int sdst = L.seglen - (7 * N + 1 + s0);
-  const double moD = __shfl_down(L.mo[0], 1, W), mdD = 2.0 * moD;
-  const double moU = __shfl_up(L.mo[CPL - 1], 1, W), mdU = 2.0 * moU;
+  // (_nc: read for the next edge cell g + 1 <= N - 1 -- chain cell k + 1 from the last
+  // element, so not by the segment's last lane; chain cell k - 1 from element 0, not by lane 0)
+  const double moD = seg_down_nc<W, 1>(L.mo[0]), mdD = 2.0 * moD;
+  const double moU = seg_up_nc<W, 1>(L.mo[CPL - 1]), mdU = 2.0 * moU;
   double* __restrict__ v = da.val + L.sg0;
 #pragma unroll
   for (int t = 0; t < CPL; ++t) {
@@ -15646,6 +15789,112 @@ NX_API int nx_group_destroy(nx_group_t* g) {
   if (g->xg_host) (void)hipHostFree(g->xg_host);
   (void)hipStreamDestroy(g->stream);
   delete g;
+  return NX_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Test hook (tests/test_gpu_seg_shuffle.py): every segment helper beside the plain __shfl* it
+// replaces, on the same input, one 1024-thread workgroup. Slot s of an output holds 1024
+// values (thread order). Slots, for W = 4, 8, 16 in turn: for O = 1, 2, .. < W the five
+// moves up, down, xor, up_nc, down_nc; then bcast0, seg_incl_scan, seg_sum; last wave_sum.
+// The int outputs leave the three sums' slots zero.
+constexpr int kSegTestSlots = (5 * 2 + 3) + (5 * 3 + 3) + (5 * 4 + 3) + 1;
+constexpr int kSegTestLanes = 1024;
+
+template <int W, class T>
+__device__ __forceinline__ void seg_test_w(T v, int& s, T* __restrict__ a, T* __restrict__ b) {
+  const int i = threadIdx.x;
+  seg_steps<W>([&](auto o) {
+    constexpr int O = decltype(o)::value;
+    T* an = a + (size_t)s * kSegTestLanes + i;
+    T* bn = b + (size_t)s * kSegTestLanes + i;
+    an[0 * kSegTestLanes] = seg_up<W, O>(v);
+    bn[0 * kSegTestLanes] = __shfl_up(v, O, W);
+    an[1 * kSegTestLanes] = seg_down<W, O>(v);
+    bn[1 * kSegTestLanes] = __shfl_down(v, O, W);
+    an[2 * kSegTestLanes] = seg_xor<W, O>(v);
+    bn[2 * kSegTestLanes] = __shfl_xor(v, O, W);
+    an[3 * kSegTestLanes] = seg_up_nc<W, O>(v);
+    bn[3 * kSegTestLanes] = __shfl_up(v, O, W);
+    an[4 * kSegTestLanes] = seg_down_nc<W, O>(v);
+    bn[4 * kSegTestLanes] = __shfl_down(v, O, W);
+    s += 5;
+  });
+  a[(size_t)s * kSegTestLanes + i] = seg_bcast0<W>(v);
+  b[(size_t)s * kSegTestLanes + i] = __shfl(v, 0, W);
+  ++s;
+  T scan_new = 0, scan_ref = 0, sum_new = 0, sum_ref = 0;
+  if constexpr (sizeof(T) == sizeof(double)) {
+    scan_new = seg_incl_scan<W>(v);
+    sum_new = seg_sum<W>(v);
+    scan_ref = v;
+    for (int o = 1; o < W; o <<= 1) {
+      const double t = __shfl_up(scan_ref, o, W);
+      if ((i & (W - 1)) >= o) scan_ref += t;
+    }
+    sum_ref = v;
+    for (int o = W / 2; o > 0; o >>= 1) sum_ref += __shfl_xor(sum_ref, o, W);
+  }
+  a[(size_t)s * kSegTestLanes + i] = scan_new;
+  b[(size_t)s * kSegTestLanes + i] = scan_ref;
+  ++s;
+  a[(size_t)s * kSegTestLanes + i] = sum_new;
+  b[(size_t)s * kSegTestLanes + i] = sum_ref;
+  ++s;
+}
+
+__global__ void __launch_bounds__(kSegTestLanes)
+k_test_seg_shuffle(const double* __restrict__ in_d, const int* __restrict__ in_i,
+                   double* __restrict__ new_d, double* __restrict__ ref_d,
+                   int* __restrict__ new_i, int* __restrict__ ref_i) {
+  const int i = threadIdx.x;
+  const double v = in_d[i];
+  const int w = in_i[i];
+  int s = 0;
+  seg_test_w<4>(v, s, new_d, ref_d);
+  seg_test_w<8>(v, s, new_d, ref_d);
+  seg_test_w<16>(v, s, new_d, ref_d);
+  new_d[(size_t)s * kSegTestLanes + i] = wave_sum(v);
+  double r = v;
+  for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+  ref_d[(size_t)s * kSegTestLanes + i] = r;
+  s = 0;
+  seg_test_w<4>(w, s, new_i, ref_i);
+  seg_test_w<8>(w, s, new_i, ref_i);
+  seg_test_w<16>(w, s, new_i, ref_i);
+  new_i[(size_t)s * kSegTestLanes + i] = 0;
+  ref_i[(size_t)s * kSegTestLanes + i] = 0;
+}
+
+NX_API int nx_test_seg_shuffle(const double* in_d, const int32_t* in_i, int32_t cap_slots,
+                               double* new_d, double* ref_d, int32_t* new_i, int32_t* ref_i,
+                               int32_t* n_slots) {
+  if (!in_d || !in_i || !new_d || !ref_d || !new_i || !ref_i || !n_slots)
+    return fail(NX_ERR_ARG, "null argument");
+  *n_slots = kSegTestSlots;
+  if (cap_slots < kSegTestSlots) return fail(NX_ERR_ARG, "outputs hold too few slots");
+  const size_t n = kSegTestLanes, m = (size_t)kSegTestSlots * kSegTestLanes;
+  char* buf = nullptr;
+  HIPCALL(hipMalloc(&buf, (n + 2 * m) * (sizeof(double) + sizeof(int))));
+  double* d_in = reinterpret_cast<double*>(buf);
+  double* d_new = d_in + n;
+  double* d_ref = d_new + m;
+  int* i_in = reinterpret_cast<int*>(d_ref + m);
+  int* i_new = i_in + n;
+  int* i_ref = i_new + m;
+  hipError_t e = hipMemcpy(d_in, in_d, n * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(i_in, in_i, n * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    k_test_seg_shuffle<<<1, kSegTestLanes>>>(d_in, i_in, d_new, d_ref, i_new, i_ref);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(new_d, d_new, m * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ref_d, d_ref, m * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(new_i, i_new, m * sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ref_i, i_ref, m * sizeof(int), hipMemcpyDeviceToHost);
+  (void)hipFree(buf);
+  if (e != hipSuccess) return fail(NX_ERR_HIP, hipGetErrorString(e));
   return NX_OK;
 }
 
