@@ -518,6 +518,70 @@ int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
                       const double* obs_d, double* value, double* grad_R, double* grad_bc,
                       double* grad_f, int32_t* iters, double* relres, int32_t* converged);
 
+/*
+ * Ensembles: many resistance fields in one batched pass -- scenario j solves A(R_j) x_j = b_j,
+ * a matrix per column (the reference would loop compute_forms + assemble + solve,
+ * assembly.py:165-262, 329-368). The batched sweeps see R through the lumped flux mass alone, so
+ * the chunk's set-up kernel (k_e_setup, in place of the rhs kernel) writes every column's own
+ * lumped mass beside its right-hand side, with the assembly's expressions, and the true
+ * residual (k_e_res) walks the handle's CSR pattern and regenerates the R-dependent values --
+ * the flux-flux entries of an edge -- per column from R_j; the +-1 couplings and the multiplier
+ * rows are read from the assembled values. A column whose R_j is the resident R has
+ * nx_batch_solve's bits.
+ *
+ * nx_ensemble_supported: *ok = 1 where nx_batch_supported says 1 on a forest (tree_exact, no
+ * cycle correction set: that correction is per matrix, 2 n_cyc solves per column); elsewhere
+ * the two calls below return NX_ERR_STATE.
+ *
+ * nx_ensemble_solve: n_cols scenarios.
+ *   edge_R    n_cols x E, finite and positive (as nx_set_coefficients' edge_R, per scenario)
+ *   edge_bc / edge_f / f_const / rtol / order / out / iters / relres / converged
+ *             as nx_batch_solve
+ * A pending deferred assembly is flushed first; the matrix must have been assembled (for any
+ * R: only its R-independent values are read). Nothing of the handle is written: its edge_R,
+ * values, lumped mass (not formed either), rhs, x, tmp, published state and snapshots stay as
+ * they were. Chunks as nx_batch_solve; a workspace that serves ensembles carries E (N + 1) + E
+ * more doubles per column (allocated on the first ensemble call). Per column: solve, true
+ * residual against its own matrix, one refinement pass over the list of columns above rtol.
+ * A column still above rtol is NOT handed to the single-column path (that path solves the
+ * handle's matrix): it is reported converged = 0, iterations = 2, and the caller decides.
+ * b = 0 gives x = 0, relres = 0, converged = 1. A column's bits do not depend on the other
+ * columns, its position, n_cols or the chunk size.
+ * NX_ERR_ARG: n_cols < 1, NULL edge_R / edge_bc / out, an R that is not finite and positive.
+ * Launches (nx_get_batch_info reports these calls too; fallback stays 0): 7 per chunk -- set-up,
+ * up, top, down, residual, norms, gather -- and 6 more for a chunk with a refinement pass.
+ *
+ * nx_ensemble_gradient: nx_batch_gradient with scenario j evaluated at R_j (edge_R as above,
+ * the other arguments and outputs as nx_batch_gradient). The forward and the adjoint solve of a
+ * column both run against the column's matrix, so the adjoint is per column for both kinds
+ * (kind 0 has no shared adjoint column here); the derivative formulas are taken at R = 1 and
+ * are nx_batch_gradient's. grad_R == NULL is legal: the objective alone -- the forward solve
+ * and the observation kernel, no adjoint, n_cols doubles copied to the host (grad_bc / grad_f
+ * are then ignored and the adjoint halves of iters / relres / converged left as they were).
+ * Launches per chunk with S = 5: 1 + S + 1 + S + 1 = 13 (both kinds), 1 + S + 1 = 7 for the
+ * objective alone, 6 more for each refinement pass.
+ *
+ * nx_stash_solution: for a caller that loops nx_set_coefficients / nx_assemble / nx_solve over
+ * scenarios on a handle that cannot take the calls above, and wants the handle back as it was.
+ * restore = 0 saves x, tmp, the rhs and the published state of the last solve (a pending
+ * deferred assembly is flushed first) into a buffer of the handle's (3 n_col doubles, allocated
+ * on first use, freed by nx_destroy); restore = 1 puts them back, after flushing the assembly
+ * of the coefficients the caller has put back, and forgets them (NX_ERR_STATE if nothing is
+ * saved). The coefficients and the matrix values are the caller's to put back.
+ */
+int nx_ensemble_supported(nx_network_t* h, int32_t* ok);
+int nx_ensemble_solve(nx_network_t* h, int32_t n_cols, const double* edge_R,
+                      const double* edge_bc, const double* edge_f, const double* f_const,
+                      double rtol, int32_t order, double* out, int32_t* iters, double* relres,
+                      int32_t* converged);
+int nx_ensemble_gradient(nx_network_t* h, int32_t n_cols, const double* edge_R,
+                         const double* edge_bc, const double* edge_f, const double* f_const,
+                         double rtol, int32_t kind, int32_t n_obs, const int32_t* obs_rows,
+                         const double* obs_w, const double* obs_d, double* value, double* grad_R,
+                         double* grad_bc, double* grad_f, int32_t* iters, double* relres,
+                         int32_t* converged);
+int nx_stash_solution(nx_network_t* h, int32_t restore);
+
 /* Copy the owned part of the solution / rhs to the host (n_rows doubles). */
 int nx_get_solution(nx_network_t* h, double* x);
 int nx_get_rhs(nx_network_t* h, double* b);

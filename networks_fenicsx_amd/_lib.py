@@ -57,6 +57,12 @@ _SIGS = {
     "nx_get_batch_info": (C.c_int, [_h, _pi32, _pi32, _pi32, _pi32]),
     "nx_batch_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd, _pd,
                                     _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
+    "nx_ensemble_supported": (C.c_int, [_h, _pi32]),
+    "nx_ensemble_solve": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd, _f64, _i32, _pd, _pi32, _pd,
+                                    _pi32]),
+    "nx_ensemble_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd,
+                                       _pd, _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
+    "nx_stash_solution": (C.c_int, [_h, _i32]),
     "nx_get_solution": (C.c_int, [_h, _pd]),
     "nx_get_rhs": (C.c_int, [_h, _pd]),
     "nx_set_output_map": (C.c_int, [_h, _i64, _pi32]),
@@ -451,7 +457,13 @@ class Handle:
         """``nx_batch_gradient``: ``(value (B,), grad_R (B, E), grad_bc (B, E, 2), grad_f
         (B, E), iterations, relres, converged -- (B, 2) each: forward, adjoint)``. ``rows``:
         distinct device rows; ``data`` None: the linear objective, else ``(B, n_obs)``."""
+        return self._gradient_call(None, edge_bc, edge_f, f_const, rtol, rows, weights, data, True)
+
+    def _gradient_call(self, edge_R, edge_bc, edge_f, f_const, rtol, rows, weights, data,
+                       derivatives):
+        """``nx_batch_gradient`` (``edge_R`` None) or ``nx_ensemble_gradient``."""
         B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
+        eR = None if edge_R is None else self._ensemble_R(edge_R, B)
         rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
         w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
         if w.size != rows.size:
@@ -476,16 +488,66 @@ class Handle:
         it = np.zeros((2, B), dtype=np.int32)
         rr = np.zeros((2, B), dtype=np.float64)
         cv = np.zeros((2, B), dtype=np.int32)
-        check(lib().nx_batch_gradient(
-            self.ptr, B, _ptr(bc, C.c_double), _ptr(ef, C.c_double), _ptr(fc, C.c_double),
-            float(rtol), 0 if d is None else 1, int(rows.size), _ptr(rows, C.c_int32),
-            _ptr(w, C.c_double), _ptr(d, C.c_double), _ptr(value, C.c_double),
-            _ptr(gR, C.c_double), _ptr(gbc, C.c_double), _ptr(gf, C.c_double),
-            _ptr(it, C.c_int32), _ptr(rr, C.c_double), _ptr(cv, C.c_int32)))
+        tail = (float(rtol), 0 if d is None else 1, int(rows.size), _ptr(rows, C.c_int32),
+                _ptr(w, C.c_double), _ptr(d, C.c_double), _ptr(value, C.c_double),
+                _ptr(gR if derivatives else None, C.c_double), _ptr(gbc, C.c_double),
+                _ptr(gf, C.c_double), _ptr(it, C.c_int32), _ptr(rr, C.c_double),
+                _ptr(cv, C.c_int32))
+        head = (self.ptr, B) + (() if eR is None else (_ptr(eR, C.c_double),))
+        head += (_ptr(bc, C.c_double), _ptr(ef, C.c_double), _ptr(fc, C.c_double))
+        fn = lib().nx_batch_gradient if eR is None else lib().nx_ensemble_gradient
+        check(fn(*head, *tail))
+        if not derivatives:  # the objective alone: the forward solve's figures
+            return value, None, None, None, it[:1].T.copy(), rr[:1].T.copy(), cv[:1].T.astype(bool)
         return value, gR, gbc, gf, it.T.copy(), rr.T.copy(), cv.T.astype(bool)
 
+    # ------------------------------------------------------------------ ensembles (R per scenario)
+    def ensemble_supported(self) -> bool:
+        """Whether ``nx_ensemble_solve`` / ``nx_ensemble_gradient`` apply to this handle."""
+        ok = C.c_int32(0)
+        check(lib().nx_ensemble_supported(self.ptr, C.byref(ok)))
+        return bool(ok.value)
+
+    def _ensemble_R(self, edge_R, B: int) -> np.ndarray:
+        eR = np.ascontiguousarray(edge_R, dtype=np.float64)
+        if eR.shape != (B, self.n_edges):
+            raise ValueError("edge_R must be (B, E)")
+        return eR
+
+    def ensemble_solve(self, edge_R, edge_bc, edge_f=None, f_const=None, rtol: float = 1e-12,
+                       blocks: bool = True):
+        """``nx_ensemble_solve``: scenario j against its own ``edge_R[j]`` (local edge order);
+        the other arguments and the outputs as :meth:`batch_solve` (the solutions in the
+        page-locked ``batch_output`` pool)."""
+        B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
+        eR = self._ensemble_R(edge_R, B)
+        out = self.batch_output(B)
+        it = np.zeros(B, dtype=np.int32)
+        rr = np.zeros(B, dtype=np.float64)
+        cv = np.zeros(B, dtype=np.int32)
+        check(lib().nx_ensemble_solve(self.ptr, B, _ptr(eR, C.c_double), _ptr(bc, C.c_double),
+                                      _ptr(ef, C.c_double), _ptr(fc, C.c_double), float(rtol),
+                                      1 if blocks else 0, _ptr(out, C.c_double),
+                                      _ptr(it, C.c_int32), _ptr(rr, C.c_double),
+                                      _ptr(cv, C.c_int32)))
+        return out, it, rr, cv.astype(bool)
+
+    def stash_solution(self, restore: bool) -> None:
+        """``nx_stash_solution``: save (False) or put back (True) x, tmp, the rhs and the
+        published state of the last solve around a scenario loop that borrows the handle."""
+        check(lib().nx_stash_solution(self.ptr, 1 if restore else 0))
+
+    def ensemble_gradient(self, edge_R, edge_bc, edge_f=None, f_const=None, rtol: float = 1e-12,
+                          *, rows, weights, data=None, derivatives: bool = True):
+        """``nx_ensemble_gradient``: :meth:`batch_gradient` with scenario j evaluated at
+        ``edge_R[j]``. ``derivatives=False``: the objective alone -- ``(value, None, None, None,
+        iterations, relres, converged -- (B, 1) each: the forward solve)``."""
+        return self._gradient_call(edge_R, edge_bc, edge_f, f_const, rtol, rows, weights, data,
+                                   derivatives)
+
     def batch_info(self) -> dict:
-        """``nx_get_batch_info`` of the last :meth:`batch_solve` or :meth:`batch_gradient`."""
+        """``nx_get_batch_info`` of the last :meth:`batch_solve`, :meth:`batch_gradient`,
+        :meth:`ensemble_solve` or :meth:`ensemble_gradient`."""
         v = [C.c_int32() for _ in range(4)]
         check(lib().nx_get_batch_info(self.ptr, *[C.byref(x) for x in v]))
         return dict(zip(("launches", "refined", "fallback", "chunk"), (int(x.value) for x in v)))

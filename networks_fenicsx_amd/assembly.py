@@ -164,6 +164,28 @@ def batch_coefficients(mesh: NetworkMesh, edge_ids: np.ndarray, p_bc, f=None):
                      f"got shape {fv.shape}")
 
 
+def ensemble_resistances(mesh: NetworkMesh, edge_ids: np.ndarray, R) -> np.ndarray:
+    """The resistances of B scenarios, as ``nx_ensemble_solve`` takes them (no device):
+    ``(B, E)`` in the local edge order ``edge_ids``.
+
+    ``R``: ``(B, num_edges)`` values in ``graph.edges()`` order, or ``(B,)`` constants, one per
+    scenario (a 1-D ``R`` always means B constants, as :func:`batch_coefficients` reads a 1-D
+    ``f``). Every value must be finite and positive."""
+    edge_ids = np.asarray(edge_ids)
+    Rv = np.asarray([c.value if isinstance(c, Constant) else c for c in R]
+                    if isinstance(R, (list, tuple)) else R, dtype=np.float64)
+    if Rv.ndim == 1 and Rv.size >= 1:
+        out = np.repeat(Rv[:, None], edge_ids.size, axis=1)
+    elif Rv.ndim == 2 and Rv.shape[0] >= 1 and Rv.shape[1] == mesh.num_edges:
+        out = Rv[:, edge_ids]
+    else:
+        raise ValueError(f"R must be (B, {mesh.num_edges}) per-edge values or (B,) constants "
+                         f"with B >= 1, got shape {Rv.shape}")
+    if not (np.isfinite(out).all() and (out > 0.0).all()):
+        raise ValueError("R must be finite and positive")
+    return np.ascontiguousarray(out)
+
+
 def _scalar(c, name: str, default: float) -> float:
     if c is None:
         return default
@@ -807,6 +829,40 @@ class HydraulicNetworkAssembler:
     def restore_rhs_coefficients(self) -> None:
         """Put back the boundary values and the source of the last ``compute_forms``."""
         self.set_rhs_coefficients(self._coefficients["edge_bc"], None, None)
+
+    # ------------------------------------------------- ensembles (Solver.solve_ensemble)
+    def ensemble_coefficients(self, R, p_bc=None, f=None):
+        """``(edge_R (B, E), edge_bc (B, E, 2), edge_f (B, E) | None, f_const (B,) | None)`` in
+        the local edge order: :func:`ensemble_resistances` and :func:`batch_coefficients`;
+        ``p_bc`` None: the boundary data of the last ``compute_forms`` on every scenario."""
+        mesh, edge_ids = self._network_mesh, self._edge_ids
+        edge_R = ensemble_resistances(mesh, edge_ids, R)
+        B = edge_R.shape[0]
+        if p_bc is None:
+            p_bc = np.tile(np.asarray(self._coefficients["p_bc"], dtype=np.float64), (B, 1))
+        edge_bc, edge_f, f_const = batch_coefficients(mesh, edge_ids, p_bc, f)
+        if edge_bc.shape[0] != B:
+            raise ValueError(f"R gives {B} scenarios, p_bc {edge_bc.shape[0]}")
+        return edge_R, edge_bc, edge_f, f_const
+
+    def set_scenario_coefficients(self, edge_R: np.ndarray, edge_bc: np.ndarray,
+                                  f_const: float | None, edge_f: np.ndarray | None) -> None:
+        """One scenario's R, boundary values and source (local edge order) to the device;
+        ``f_const`` and ``edge_f`` both None: the source of the last ``compute_forms``."""
+        if edge_f is None and f_const is None:
+            f0 = self._coefficients["f"]
+            edge_f, f_const = (f0, 0.0) if isinstance(f0, np.ndarray) else (None, float(f0))
+        self._handle.set_coefficients(edge_R, 1.0, 0.0 if f_const is None else f_const, edge_bc)
+        self._handle.set_source(edge_f)
+
+    def restore_coefficients(self) -> None:
+        """Put back every coefficient of the last ``compute_forms``, R included."""
+        co = self._coefficients
+        R0, f0 = co["R"], co["f"]
+        R_edge, R_const = (R0, 1.0) if isinstance(R0, np.ndarray) else (None, float(R0))
+        f_edge, f_val = (f0, 0.0) if isinstance(f0, np.ndarray) else (None, float(f0))
+        self._handle.set_coefficients(R_edge, R_const, f_val, co["edge_bc"])
+        self._handle.set_source(f_edge)
 
     # --------------------------------------------------------------- accessors
     @property

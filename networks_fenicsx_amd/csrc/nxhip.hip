@@ -3574,6 +3574,10 @@ struct BatchCols {
   int64_t ld;       // doubles between two columns of a vector
   int64_t n_chain, n_slot;  // doubles between two columns of the chain / slot arrays
   double *chain_T, *chain_It, *chain_Ib, *slot_D, *slot_J, *slot_A, *slot_B, *slot_z;
+  // nx_ensemble_solve: every column's own lumped mass (column c at dq + c n_dq; the sweeps see
+  // R nowhere else), or null: the handle's
+  const double* dq;
+  int64_t n_dq;
 };
 
 __device__ __forceinline__ int batch_col(const BatchCols& bc, int i) {
@@ -3590,6 +3594,7 @@ __device__ __forceinline__ PcArgs batch_col_args(const PcArgs& pa, const BatchCo
   p.slot_A = bc.slot_A + col * bc.n_slot;
   p.slot_B = bc.slot_B + col * bc.n_slot;
   p.slot_z = bc.slot_z + col * bc.n_slot;
+  if (bc.dq) p.dq = bc.dq + col * bc.n_dq;
   return p;
 }
 
@@ -3969,6 +3974,164 @@ __global__ __launch_bounds__(kBlock) void k_b_edge_form(FormArgs a) {
     a.gf[col * E + e] = accf;
     a.gbc[(col * E + e) * 2] = l[0];
     a.gbc[(col * E + e) * 2 + 1] = l[2 * N];
+  }
+}
+
+// --------------------------------------------------------------------------------------
+// Ensembles (nx_ensemble_solve): a matrix per column, A(R_c). The sweeps see R through the
+// lumped mass alone (ChainLane::setup), so a chunk's set-up writes every column's own dq beside
+// its right-hand side, and the true residual regenerates the R-dependent entries per column.
+//
+// k_e_setup stands in for k_b_rhs: one thread per flux vertex (edge e, k = 0 .. N) forms the
+// lengths of the cells on both sides once (vertex, sqrt, no contraction, as k_assemble_seg) and
+// writes, per column c, k_b_rhs's entries with its expressions and dq_c[e (N + 1) + k] from
+// R_c[e] with k_assemble's expressions in its order (md = R h / 3, mo = R h / 6; interior
+// (mo_{k-1} + md_{k-1}) + (md_k + mo_k), k = 0: md_0 + mo_0, k = N: mo_{N-1} + md_{N-1}): with
+// R_c the resident R, the handle's dq bit for bit. The threads after them zero the multiplier
+// rows. edge_R: column c's resistances at edge_R + c E.
+__global__ __launch_bounds__(kBlock) void k_e_setup(EdgeArgs ea, int64_t n_lm, int ncols,
+                                                    const double* __restrict__ edge_R,
+                                                    const double* __restrict__ edge_bc,
+                                                    const double* __restrict__ edge_f,
+                                                    int64_t ef_ld,
+                                                    const double* __restrict__ f_const,
+                                                    double* __restrict__ out, int64_t ld,
+                                                    double* __restrict__ dq, int64_t n_dq) {
+#pragma clang fp contract(off)
+  const int N = ea.N;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t nv = ea.E * (int64_t)(N + 1);
+  if (i >= nv) {
+    const int64_t j = i - nv;
+    if (j < n_lm)
+      for (int c = 0; c < ncols; ++c) out[c * ld + ea.E * (int64_t)(2 * N + 1) + j] = 0.0;
+    return;
+  }
+  const int64_t e = i / (N + 1);
+  const int k = (int)(i - e * (N + 1));
+  const int64_t base = e * (2 * N + 1);
+  const double invN = 1.0 / (double)N;
+  double x0[3], x1[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    x0[c] = ea.edge_x[6 * e + c];
+    x1[c] = ea.edge_x[6 * e + 3 + c];
+  }
+  const double hL = k > 0 ? form_cell_len(x0, x1, k - 1, N, invN) : 0.0;
+  const double hR = k < N ? form_cell_len(x0, x1, k, N, invN) : 0.0;
+  for (int c = 0; c < ncols; ++c) {
+    const double R = edge_R[c * ea.E + e];
+    double d;
+    if (k < N) {
+      const double fe = edge_f ? edge_f[c * ef_ld + e] : f_const[c];
+      out[c * ld + base + 2 * k + 1] = -(fe * hR);  // negated pressure row: -(f h)
+      out[c * ld + base + 2 * k] = (k == 0) ? edge_bc[(c * ea.E + e) * 2] : 0.0;
+      const double md = R * hR / 3.0, mo = R * hR / 6.0;
+      d = md + mo;
+      if (k > 0) {
+        const double mdL = R * hL / 3.0, moL = R * hL / 6.0;
+        d = (moL + mdL) + d;
+      }
+    } else {
+      out[c * ld + base + 2 * N] = edge_bc[(c * ea.E + e) * 2 + 1];
+      const double mdL = R * hL / 3.0, moL = R * hL / 6.0;
+      d = moL + mdL;  // q_N: the last cell only
+    }
+    dq[c * n_dq + i] = d;
+  }
+}
+
+// k_e_res stands in for k_b_res: R = B - A(R_c) X for the listed columns with k_b_res's shape
+// (one row per thread, tiles of kBatchTile columns, the same sums in CSR order, the same
+// partials). The pattern does not depend on R; of the values only the flux-flux entries of an
+// edge do -- a flux row q_k's columns q_{k-1}, q_k, q_{k+1} -- and those are regenerated per
+// column from R_c[e] and the two cell lengths (formed once per row) with k_assemble's
+// expressions: off-diagonal mo, end diagonals md, interior diagonal md_{k-1} + md_k. Every other
+// entry (the +-1 couplings, the multiplier rows) is read from the assembled values. With R_c
+// the resident R, k_b_res's bits.
+__global__ __launch_bounds__(kBlock) void k_e_res(Csr A, EdgeArgs ea,
+                                                  const double* __restrict__ edge_R,
+                                                  const double* __restrict__ X,
+                                                  const double* __restrict__ B,
+                                                  double* __restrict__ R, int64_t ld,
+                                                  const int* __restrict__ list, int ncols,
+                                                  double* __restrict__ part, int nblk) {
+#pragma clang fp contract(off)
+  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool on = row < A.n_rows;
+  const int p0 = on ? A.rowptr[row] : 0, p1 = on ? A.rowptr[row + 1] : 0;
+  const int N = ea.N;
+  // the row's place: flux vertex k of edge e (an even row of the edge's 2 N + 1), or none
+  const int64_t e = on ? row / (2 * N + 1) : ea.E;
+  const int loc = (int)(row - e * (2 * N + 1));
+  const bool flux = e < ea.E && (loc & 1) == 0;
+  const int k = loc >> 1;
+  const int cbase = flux ? (int)(e * (2 * N + 1)) : 0;
+  double hL = 0.0, hR = 0.0;
+  if (flux) {
+    const double invN = 1.0 / (double)N;
+    double x0[3], x1[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      x0[c] = ea.edge_x[6 * e + c];
+      x1[c] = ea.edge_x[6 * e + 3 + c];
+    }
+    if (k > 0) hL = form_cell_len(x0, x1, k - 1, N, invN);
+    if (k < N) hR = form_cell_len(x0, x1, k, N, invN);
+  }
+  for (int c0 = 0; c0 < ncols; c0 += kBatchTile) {
+    const int nt = min(kBatchTile, ncols - c0);
+    int64_t off[kBatchTile];
+    int colv[kBatchTile];
+    double acc[kBatchTile], Rc[kBatchTile];
+#pragma unroll
+    for (int t = 0; t < kBatchTile; ++t) {
+      colv[t] = t < nt ? (list ? list[c0 + t] : c0 + t) : 0;
+      off[t] = colv[t] * ld;
+      acc[t] = 0.0;
+      Rc[t] = flux ? edge_R[colv[t] * ea.E + e] : 0.0;
+    }
+    for (int p = p0; p < p1; ++p) {
+      const double av = A.val[p];
+      const int c = A.col[p];
+      // which regenerated entry: 0 none, 1 q_{k-1} (mo of the left cell), 2 the diagonal,
+      // 3 q_{k+1} (mo of the right cell)
+      const int dk = c - cbase - 2 * k;
+      const int kind =
+          (flux && ((dk == -2 && k > 0) || dk == 0 || (dk == 2 && k < N))) ? 2 + dk / 2 : 0;
+#pragma unroll
+      for (int t = 0; t < kBatchTile; ++t)
+        if (t < nt) {
+          double a = av;
+          if (kind == 1) {
+            a = Rc[t] * hL / 6.0;
+          } else if (kind == 3) {
+            a = Rc[t] * hR / 6.0;
+          } else if (kind == 2) {
+            const double mdL = Rc[t] * hL / 3.0, mdR = Rc[t] * hR / 3.0;
+            a = k == 0 ? mdR : (k == N ? mdL : mdL + mdR);
+          }
+          const double prod = a * X[off[t] + c];
+          acc[t] += prod;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < kBatchTile; ++t) {
+      if (t >= nt) break;  // block-uniform
+      double rr = 0.0, bb = 0.0;
+      if (on) {
+        const double bv = B[off[t] + row];
+        const double rv = bv - acc[t];
+        R[off[t] + row] = rv;
+        rr = rv * rv;
+        bb = bv * bv;
+      }
+      double* pc = part + 2 * (int64_t)colv[t] * nblk;
+      block_sum_store(rr, pc + blockIdx.x);
+      __syncthreads();
+      block_sum_store(bb, pc + nblk + blockIdx.x);
+      __syncthreads();
+    }
   }
 }
 
@@ -8019,8 +8182,16 @@ struct nx_network {
   // nx_batch_gradient: whether the workspace carries the adjoint columns (kept once a
   // gradient call asked for them), and the observation list's device copy (rows | w | data)
   bool bws_grad = false;
+  // nx_ensemble_solve / nx_ensemble_gradient: whether it carries every column's own lumped
+  // mass and R (kept once an ensemble call has asked for them)
+  bool bws_ens = false;
   void* gobs = nullptr;
   size_t gobs_bytes = 0;
+  // nx_stash_solution: x | tmp | rhs (3 n_col) and the published state (a BatchSaved, malloc'ed)
+  // while a scenario loop borrows the handle; allocated on first use, freed in nx_destroy
+  double* stash = nullptr;
+  void* stash_state = nullptr;
+  bool stash_set = false;
   int64_t cpc_version = -1;  // R's version its capacitance matrix was built for (fe_cp_solve)
   bool cpc_failed = false;   // a singular capacitance matrix: the solves run MINRES
   int cpc_builds = 0;
@@ -10538,6 +10709,8 @@ NX_API int nx_destroy(nx_network_t* h) {
     if (p) (void)hipFree(p);
   if (h->bws) (void)hipFree(h->bws);
   if (h->gobs) (void)hipFree(h->gobs);
+  if (h->stash) (void)hipFree(h->stash);
+  std::free(h->stash_state);
   if (h->h_st) (void)hipHostFree(h->h_st);
   if (h->h_last) (void)hipHostFree(h->h_last);
   for (auto& e : h->ev)
@@ -12918,18 +13091,20 @@ struct BatchWs {
                           // or a fallback solve borrows them (3 n_col)
   double *C, *L;          // nx_batch_gradient (bws_grad): adjoint rhs and solution, cap x ld
   double *gJ, *gR, *gf, *gbc;  // and its outputs: cap, cap x E, cap x E, cap x 2 E
+  double *edq, *eR;       // ensembles (bws_ens): the column's lumped mass and R, cap x E (N + 1), cap x E
   int* list;              // cap
   int nblk;
 };
 
-size_t batch_col_doubles(const nx_network* h, bool grad) {
+size_t batch_col_doubles(const nx_network* h, bool grad, bool ens) {
   const int64_t E = h->E, S = std::max<int64_t>(h->pc_slots, 1), m = 2 * (int64_t)h->n_cyc;
   const int nblk = grid_of(h->n_own, kBlock);
   const int64_t g = grad ? 2 * h->n_col + 4 * E + 1 : 0;  // X stays resident beside C and L
-  return (size_t)(4 * h->n_col + 3 * E + 5 * S + 3 * E + 1 + 2 * nblk + 2 + m + g);
+  const int64_t en = ens ? E * (int64_t)(h->N + 1) + E : 0;  // the column's own dq and R
+  return (size_t)(4 * h->n_col + 3 * E + 5 * S + 3 * E + 1 + 2 * nblk + 2 + m + g + en);
 }
-size_t batch_bytes(const nx_network* h, int cap, bool grad) {
-  return 8 * (batch_col_doubles(h, grad) * (size_t)cap + (size_t)(3 * h->n_col)) +
+size_t batch_bytes(const nx_network* h, int cap, bool grad, bool ens) {
+  return 8 * (batch_col_doubles(h, grad, ens) * (size_t)cap + (size_t)(3 * h->n_col)) +
          sizeof(int) * (size_t)cap + 64;
 }
 BatchWs batch_carve(const nx_network* h, int cap) {
@@ -12974,6 +13149,10 @@ BatchWs batch_carve(const nx_network* h, int cap) {
     w.gf = take(cap * E);
     w.gbc = take(cap * 2 * E);
   }
+  if (h->bws_ens) {
+    w.edq = take(cap * E * (int64_t)(h->N + 1));
+    w.eR = take(cap * E);
+  }
   w.list = reinterpret_cast<int*>(p);
   return w;
 }
@@ -12989,34 +13168,37 @@ bool batch_ok(const nx_network* h) {
 // size follows the decomposition's slots and the cycle chains, which nx_set_preconditioner
 // and nx_set_cycles change after a workspace was allocated (nx_batch_rhs is legal before
 // either), so the allocated bytes are checked, not the column count alone.
-bool batch_fits(const nx_network* h, int chunk, bool grad) {
+bool batch_fits(const nx_network* h, int chunk, bool grad, bool ens) {
   return h->bws != nullptr && chunk <= h->bws_cap && (!grad || h->bws_grad) &&
-         batch_bytes(h, h->bws_cap, h->bws_grad) <= h->bws_bytes;
+         (!ens || h->bws_ens) &&
+         batch_bytes(h, h->bws_cap, h->bws_grad, h->bws_ens) <= h->bws_bytes;
 }
 
 // The chunk size of this call and a workspace that holds it: NXHIP_BATCH_CHUNK (read per
 // call) or the largest of <= kBatchChunkMax whose workspace fits kBatchMemShare of the free
 // device memory; a failed allocation halves it down to 1.
-int batch_workspace(nx_network* h, int n_cols, int* chunk_out, bool grad = false) {
+int batch_workspace(nx_network* h, int n_cols, int* chunk_out, bool grad = false,
+                    bool ens = false) {
   grad = grad || h->bws_grad;
+  ens = ens || h->bws_ens;
   int chunk = std::min(n_cols, kBatchChunkMax);
   const char* e = std::getenv("NXHIP_BATCH_CHUNK");
   if (e != nullptr && std::atoi(e) > 0) {
     chunk = std::min(std::min(std::atoi(e), kBatchChunkEnvMax), n_cols);
-  } else if (!batch_fits(h, chunk, grad)) {
+  } else if (!batch_fits(h, chunk, grad, ens)) {
     size_t fr = 0, tot = 0;
     HIPCALL(hipMemGetInfo(&fr, &tot));
     const double room = kBatchMemShare * (double)fr;
-    while (chunk > 1 && (double)batch_bytes(h, chunk, grad) > room) --chunk;
+    while (chunk > 1 && (double)batch_bytes(h, chunk, grad, ens) > room) --chunk;
   }
-  if (!batch_fits(h, chunk, grad)) {
+  if (!batch_fits(h, chunk, grad, ens)) {
     HIPCALL(hipStreamSynchronize(h->stream));
     if (h->bws) (void)hipFree(h->bws);
     h->bws = nullptr;
     h->bws_cap = 0;
     h->bws_bytes = 0;
     for (;;) {
-      if (hipMalloc(&h->bws, batch_bytes(h, chunk, grad)) == hipSuccess) break;
+      if (hipMalloc(&h->bws, batch_bytes(h, chunk, grad, ens)) == hipSuccess) break;
       (void)hipGetLastError();
       h->bws = nullptr;
       if (chunk == 1) return fail(NX_ERR_HIP, "nx_batch_solve: no memory for one column's workspace");
@@ -13024,16 +13206,37 @@ int batch_workspace(nx_network* h, int n_cols, int* chunk_out, bool grad = false
     }
     h->bws_cap = chunk;
     h->bws_grad = grad;
-    h->bws_bytes = batch_bytes(h, chunk, grad);
+    h->bws_ens = ens;
+    h->bws_bytes = batch_bytes(h, chunk, grad, ens);
   }
   *chunk_out = chunk;
   return NX_OK;
 }
 
-// The chunk's inputs to the device and its right-hand sides into ws.B (one launch).
+// An ensemble's columns (nx_ensemble_solve): every workspace column solves its own matrix
+// A(R_c). The sweeps take the column's lumped mass, the residual the column's R; a column still
+// above rtol after the refinement pass is reported unconverged -- the single-column path solves
+// against the handle's matrix, which is not the column's. Null where a descriptor is taken: the
+// handle's matrix for every column.
+struct BatchEns {
+  const double* dq;  // cap x n_dq
+  int64_t n_dq;
+  const double* R;   // cap x E
+};
+BatchEns batch_ens(const nx_network* h, const BatchWs& ws) {
+  return BatchEns{ws.edq, h->E * (int64_t)(h->N + 1), ws.eR};
+}
+
+// The chunk's inputs to the device and its right-hand sides into ws.B (one launch). edge_R
+// (host, n_cols x E; an ensemble): the chunk's R columns go to ws.eR as well, and the launch
+// writes every column's lumped mass beside its right-hand side (k_e_setup).
 int batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const double* edge_bc,
-                    const double* edge_f, const double* f_const) {
+                    const double* edge_f, const double* f_const,
+                    const double* edge_R = nullptr) {
   const int64_t E = h->E;
+  if (edge_R)
+    HIPCALL(hipMemcpyAsync(ws.eR, edge_R + (int64_t)c0 * E, sizeof(double) * E * nc,
+                           hipMemcpyHostToDevice, h->stream));
   HIPCALL(hipMemcpyAsync(ws.bc, edge_bc + (int64_t)c0 * 2 * E, sizeof(double) * 2 * E * nc,
                          hipMemcpyHostToDevice, h->stream));
   const double* ef = nullptr;
@@ -13055,9 +13258,14 @@ int batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const doub
     HIPCALL(hipStreamSynchronize(h->stream));  // (fc leaves scope)
   }
   const int64_t nthr = E * (int64_t)(h->N + 1) + h->B;
-  hipLaunchKernelGGL(k_b_rhs, dim3(grid_of(nthr, kBlock)), dim3(kBlock), 0, h->stream,
-                     EdgeArgs{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N}, h->B, nc, ws.bc, ef,
-                     ef_ld, ws.fc, ws.B, ws.cols.ld);
+  const EdgeArgs ea{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N};
+  if (edge_R)
+    hipLaunchKernelGGL(k_e_setup, dim3(grid_of(nthr, kBlock)), dim3(kBlock), 0, h->stream, ea,
+                       h->B, nc, ws.eR, ws.bc, ef, ef_ld, ws.fc, ws.B, ws.cols.ld, ws.edq,
+                       E * (int64_t)(h->N + 1));
+  else
+    hipLaunchKernelGGL(k_b_rhs, dim3(grid_of(nthr, kBlock)), dim3(kBlock), 0, h->stream, ea, h->B,
+                       nc, ws.bc, ef, ef_ld, ws.fc, ws.B, ws.cols.ld);
   HIPCALL(hipGetLastError());
   h->b_launches += 1;
   return NX_OK;
@@ -13067,13 +13275,15 @@ int batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const doub
 // down sweeps, then the cycle correction.
 template <int W, int CPL>
 void batch_sweeps_wc(nx_network* h, const BatchWs& ws, const int* list, int nc, const double* in,
-                     double* out) {
+                     double* out, const BatchEns* ens) {
   PcArgs pa = h->pa;
   pa.accum = 0;
   pa.fres = 0;
   pa.topdown = 0;
   BatchCols bc = ws.cols;
   bc.list = list;
+  bc.dq = ens ? ens->dq : nullptr;
+  bc.n_dq = ens ? ens->n_dq : 0;
   if (h->pc_jobs > 0) {
     hipLaunchKernelGGL((k_b_up<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, h->stream, pa,
                        bc, in);
@@ -13096,18 +13306,18 @@ void batch_sweeps_wc(nx_network* h, const BatchWs& ws, const int* list, int nc, 
   }
 }
 int batch_sweeps(nx_network* h, const BatchWs& ws, const int* list, int nc, const double* in,
-                 double* out) {
+                 double* out, const BatchEns* ens = nullptr) {
   switch (h->pc_variant) {
-    case 0: batch_sweeps_wc<16, 1>(h, ws, list, nc, in, out); break;
-    case 1: batch_sweeps_wc<16, 2>(h, ws, list, nc, in, out); break;
-    case 2: batch_sweeps_wc<16, 4>(h, ws, list, nc, in, out); break;
-    case 3: batch_sweeps_wc<64, 2>(h, ws, list, nc, in, out); break;
-    case 5: batch_sweeps_wc<8, 2>(h, ws, list, nc, in, out); break;
-    case 6: batch_sweeps_wc<4, 4>(h, ws, list, nc, in, out); break;
-    case 7: batch_sweeps_wc<8, 4>(h, ws, list, nc, in, out); break;
-    case 8: batch_sweeps_wc<64, 8>(h, ws, list, nc, in, out); break;
-    case 9: batch_sweeps_wc<64, 16>(h, ws, list, nc, in, out); break;
-    default: batch_sweeps_wc<64, 4>(h, ws, list, nc, in, out); break;
+    case 0: batch_sweeps_wc<16, 1>(h, ws, list, nc, in, out, ens); break;
+    case 1: batch_sweeps_wc<16, 2>(h, ws, list, nc, in, out, ens); break;
+    case 2: batch_sweeps_wc<16, 4>(h, ws, list, nc, in, out, ens); break;
+    case 3: batch_sweeps_wc<64, 2>(h, ws, list, nc, in, out, ens); break;
+    case 5: batch_sweeps_wc<8, 2>(h, ws, list, nc, in, out, ens); break;
+    case 6: batch_sweeps_wc<4, 4>(h, ws, list, nc, in, out, ens); break;
+    case 7: batch_sweeps_wc<8, 4>(h, ws, list, nc, in, out, ens); break;
+    case 8: batch_sweeps_wc<64, 8>(h, ws, list, nc, in, out, ens); break;
+    case 9: batch_sweeps_wc<64, 16>(h, ws, list, nc, in, out, ens); break;
+    default: batch_sweeps_wc<64, 4>(h, ws, list, nc, in, out, ens); break;
   }
   HIPCALL(hipGetLastError());
   return NX_OK;
@@ -13116,9 +13326,15 @@ int batch_sweeps(nx_network* h, const BatchWs& ws, const int* list, int nc, cons
 // R = Bv - A Xv and the two norms of nc columns; stats (host, 2 per workspace column) filled
 // for them after one synchronisation.
 int batch_residual(nx_network* h, const BatchWs& ws, const double* Xv, const double* Bv,
-                   const int* list, int nc, std::vector<double>& stats, int cap) {
-  hipLaunchKernelGGL(k_b_res, dim3(ws.nblk), dim3(kBlock), 0, h->stream, csr_of(h), Xv, Bv,
-                     ws.R, ws.cols.ld, list, nc, ws.part, ws.nblk);
+                   const int* list, int nc, std::vector<double>& stats, int cap,
+                   const BatchEns* ens = nullptr) {
+  if (ens)  // against every column's own matrix
+    hipLaunchKernelGGL(k_e_res, dim3(ws.nblk), dim3(kBlock), 0, h->stream, csr_of(h),
+                       EdgeArgs{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N}, ens->R, Xv, Bv,
+                       ws.R, ws.cols.ld, list, nc, ws.part, ws.nblk);
+  else
+    hipLaunchKernelGGL(k_b_res, dim3(ws.nblk), dim3(kBlock), 0, h->stream, csr_of(h), Xv, Bv,
+                       ws.R, ws.cols.ld, list, nc, ws.part, ws.nblk);
   hipLaunchKernelGGL(k_b_norms, dim3(nc), dim3(kReduceThreads), 0, h->stream, ws.part, ws.nblk,
                      list, ws.stats);
   HIPCALL(hipGetLastError());
@@ -13196,15 +13412,16 @@ int batch_fallback(nx_network* h, const BatchWs& ws, const double* Bv, double* X
 // true residual, one refinement pass over the list of columns above rtol, the single-column
 // path for a column still above it. iters / relres / converged: this chunk's entries (any
 // may be null). stats (host) keeps ||r||^2 | ||b||^2 per column: a column with ||b|| = 0 is
-// reported converged and its caller writes the exact zero.
+// reported converged and its caller writes the exact zero. ens: every column against its own
+// matrix, and no single-column path (BatchEns): such a column stays converged = 0, 2 iterations.
 int batch_solve_cols(nx_network* h, const BatchWs& ws, int nc, const double* Bv, double* Xv,
                      double rtol, int32_t* iters, double* relres, int32_t* converged,
-                     std::vector<double>& stats) {
+                     std::vector<double>& stats, const BatchEns* ens = nullptr) {
   const int cap = h->bws_cap;
   const int64_t n = h->n_own, ld = ws.cols.ld;
   std::vector<int> redo, fall;
-  CHECK(batch_sweeps(h, ws, nullptr, nc, Bv, Xv));
-  CHECK(batch_residual(h, ws, Xv, Bv, nullptr, nc, stats, cap));
+  CHECK(batch_sweeps(h, ws, nullptr, nc, Bv, Xv, ens));
+  CHECK(batch_residual(h, ws, Xv, Bv, nullptr, nc, stats, cap, ens));
   for (int c = 0; c < nc; ++c) {
     const double rr = stats[2 * c], bb = stats[2 * c + 1];
     const double r = batch_relres(rr, bb);
@@ -13217,18 +13434,18 @@ int batch_solve_cols(nx_network* h, const BatchWs& ws, int nc, const double* Bv,
     const int nr = (int)redo.size();
     HIPCALL(hipMemcpyAsync(ws.list, redo.data(), sizeof(int) * nr, hipMemcpyHostToDevice,
                            h->stream));
-    CHECK(batch_sweeps(h, ws, ws.list, nr, ws.R, ws.D));
+    CHECK(batch_sweeps(h, ws, ws.list, nr, ws.R, ws.D, ens));
     hipLaunchKernelGGL(k_b_add, dim3(grid_of(n, kBlock), nr), dim3(kBlock), 0, h->stream, Xv,
                        ws.D, ld, ws.list, n);
     h->b_launches += 1;
-    CHECK(batch_residual(h, ws, Xv, Bv, ws.list, nr, stats, cap));
+    CHECK(batch_residual(h, ws, Xv, Bv, ws.list, nr, stats, cap, ens));
     h->b_refined += nr;
     for (int c : redo) {
       const double r = batch_relres(stats[2 * c], stats[2 * c + 1]);
       if (iters) iters[c] = 2;
       if (relres) relres[c] = r;
       if (converged) converged[c] = r <= rtol ? 1 : 0;
-      if (!(r <= rtol)) fall.push_back(c);
+      if (!(r <= rtol) && !ens) fall.push_back(c);
     }
   }
   for (int c : fall) {  // still above rtol: the single-column path (with its MINRES)
@@ -13378,25 +13595,48 @@ NX_API int nx_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc
   return NX_OK;
 }
 
-NX_API int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
-                             const double* edge_f, const double* f_const, double rtol,
-                             int32_t kind, int32_t n_obs, const int32_t* obs_rows,
-                             const double* obs_w, const double* obs_d, double* value,
-                             double* grad_R, double* grad_bc, double* grad_f, int32_t* iters,
-                             double* relres, int32_t* converged) {
+namespace {
+
+// Non-finite or non-positive R anywhere in an ensemble's n_cols x E resistances.
+bool ensemble_R_bad(const double* edge_R, int64_t count) {
+  for (int64_t i = 0; i < count; ++i)
+    if (!(edge_R[i] > 0.0) || !std::isfinite(edge_R[i])) return true;
+  return false;
+}
+
+// Where the ensemble calls apply: the batched kernels on a forest (the cycle correction is
+// per matrix: 2 n_cyc solves per column).
+bool ensemble_ok(const nx_network* h) { return batch_ok(h) && h->tree_exact && h->n_cyc == 0; }
+
+// nx_batch_gradient (edge_R null: every scenario against the handle's matrix) and
+// nx_ensemble_gradient (edge_R: n_cols x E, every scenario against its own matrix; the adjoint
+// column is then per scenario for both kinds, and grad_R null means the objective alone).
+int batch_gradient_run(nx_network* h, int32_t n_cols, const double* edge_R, const double* edge_bc,
+                       const double* edge_f, const double* f_const, double rtol, int32_t kind,
+                       int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
+                       const double* obs_d, double* value, double* grad_R, double* grad_bc,
+                       double* grad_f, int32_t* iters, double* relres, int32_t* converged) {
+  const bool ens = edge_R != nullptr;
   const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
   CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
   if (!h) return fail(NX_ERR_ARG, "null handle");
   if (n_cols < 1) return fail(NX_ERR_ARG, "n_cols must be >= 1");
-  if (!edge_bc || !value || !grad_R) return fail(NX_ERR_ARG, "edge_bc / value / grad_R is NULL");
+  if (!edge_bc || !value || (!ens && !grad_R))
+    return fail(NX_ERR_ARG, "edge_bc / value / grad_R is NULL");
   if (n_obs < 1 || !obs_rows || !obs_w) return fail(NX_ERR_ARG, "at least one observed row");
   if (kind != 0 && kind != 1) return fail(NX_ERR_ARG, "kind: 0 linear, 1 least squares");
   if (kind == 1 && !obs_d) return fail(NX_ERR_ARG, "the least-squares objective needs obs_d");
-  if (!batch_ok(h))
-    return fail(NX_ERR_STATE, "nx_batch_gradient: the batched direct solve does not apply to "
-                              "this handle (nx_batch_supported)");
-  if (!h->have_lhs) return fail(NX_ERR_STATE, "assemble the matrix before nx_batch_gradient");
+  if (ens ? !ensemble_ok(h) : !batch_ok(h))
+    return fail(NX_ERR_STATE, ens ? "nx_ensemble_gradient: the batched ensemble does not apply "
+                                    "to this handle (nx_ensemble_supported)"
+                                  : "nx_batch_gradient: the batched direct solve does not apply "
+                                    "to this handle (nx_batch_supported)");
+  if (!h->have_lhs)
+    return fail(NX_ERR_STATE, ens ? "assemble the matrix before nx_ensemble_gradient"
+                                  : "assemble the matrix before nx_batch_gradient");
   const int64_t n = h->n_own, E = h->E;
+  if (ens && ensemble_R_bad(edge_R, (int64_t)n_cols * E))
+    return fail(NX_ERR_ARG, "nx_ensemble_gradient: R must be finite and positive");
   {
     std::vector<char> seen((size_t)n, 0);
     for (int i = 0; i < n_obs; ++i) {
@@ -13408,12 +13648,14 @@ NX_API int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge
   }
   CHECK(set_device(h));
   h->b_refined = h->b_fallback = 0;
-  h->b_launches = made_current + (h->dq_stale ? 1 : 0);
+  h->b_launches = made_current + (!ens && h->dq_stale ? 1 : 0);
   int chunk = 0;
-  CHECK(batch_workspace(h, n_cols, &chunk, true));
+  CHECK(batch_workspace(h, n_cols, &chunk, true, ens));
   h->b_chunk = chunk;
   const BatchWs ws = batch_carve(h, h->bws_cap);
-  CHECK(batch_make_current(h, ws));
+  const BatchEns be = batch_ens(h, ws);
+  const BatchEns* ep = ens ? &be : nullptr;
+  if (!ens) CHECK(batch_make_current(h, ws));  // (an ensemble reads no dq of the handle's)
   // the observation list on the device: rows (ints, padded to doubles) | w | the chunk's data
   const size_t row_d = ((size_t)n_obs + 1) / 2;
   const size_t need = 8 * (row_d + (size_t)n_obs + (size_t)n_obs * (size_t)chunk);
@@ -13435,7 +13677,8 @@ NX_API int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge
   std::vector<double> stats;
   int32_t a_it = 1, a_cv = 1;
   double a_rr = 0.0;
-  if (kind == 0) {  // the same adjoint column for every scenario: solved once per call
+  const bool one_adj = kind == 0 && !ens;
+  if (one_adj) {  // the same adjoint column for every scenario: solved once per call
     hipLaunchKernelGGL(k_b_obs, dim3(slices, 1), dim3(kObsThreads), 0, h->stream, nullptr, ld, n,
                        0, n_obs, d_rows, d_w, nullptr, ws.C, nullptr);
     HIPCALL(hipGetLastError());
@@ -13445,22 +13688,33 @@ NX_API int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge
   }
   for (int c0 = 0; c0 < n_cols; c0 += chunk) {
     const int nc = std::min(chunk, n_cols - c0);
-    CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
+    CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const, edge_R));
     CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.X, rtol, iters ? iters + c0 : nullptr,
                            relres ? relres + c0 : nullptr, converged ? converged + c0 : nullptr,
-                           stats));
+                           stats, ep));
     CHECK(batch_zero_cols(h, ws.X, ld, nc, stats));  // b = 0: x = 0 exactly
     int32_t* a_iters = iters ? iters + n_cols + c0 : nullptr;
     double* a_relres = relres ? relres + n_cols + c0 : nullptr;
     int32_t* a_conv = converged ? converged + n_cols + c0 : nullptr;
-    if (kind == 1) {
+    if (kind == 1)
       HIPCALL(hipMemcpyAsync(d_d, obs_d + (int64_t)c0 * n_obs, sizeof(double) * n_obs * nc,
                              hipMemcpyHostToDevice, h->stream));
-      hipLaunchKernelGGL(k_b_obs, dim3(slices, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n,
-                         1, n_obs, d_rows, d_w, d_d, ws.C, ws.gJ);
+    if (!grad_R) {  // (an ensemble's) objective alone: no adjoint, n_cols doubles to the host
+      hipLaunchKernelGGL(k_b_obs, dim3(1, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n, kind,
+                         n_obs, d_rows, d_w, kind ? d_d : nullptr, nullptr, ws.gJ);
       HIPCALL(hipGetLastError());
       h->b_launches += 1;
-      CHECK(batch_solve_cols(h, ws, nc, ws.C, ws.L, rtol, a_iters, a_relres, a_conv, stats));
+      HIPCALL(hipMemcpyAsync(value + c0, ws.gJ, sizeof(double) * nc, hipMemcpyDeviceToHost,
+                             h->stream));
+      HIPCALL(hipStreamSynchronize(h->stream));
+      continue;
+    }
+    if (!one_adj) {
+      hipLaunchKernelGGL(k_b_obs, dim3(slices, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n,
+                         kind, n_obs, d_rows, d_w, kind ? d_d : nullptr, ws.C, ws.gJ);
+      HIPCALL(hipGetLastError());
+      h->b_launches += 1;
+      CHECK(batch_solve_cols(h, ws, nc, ws.C, ws.L, rtol, a_iters, a_relres, a_conv, stats, ep));
       CHECK(batch_zero_cols(h, ws.L, ld, nc, stats));
     } else {
       hipLaunchKernelGGL(k_b_obs, dim3(1, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n, 0,
@@ -13473,7 +13727,7 @@ NX_API int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge
         if (a_conv) a_conv[c] = a_cv;
       }
     }
-    CHECK(batch_edge_form(h, ws, nc, kind == 1 ? ld : 0));
+    CHECK(batch_edge_form(h, ws, nc, one_adj ? 0 : ld));
     // the chunk's outputs straight into the caller's arrays (no staging, no host unpack)
     HIPCALL(hipMemcpyAsync(value + c0, ws.gJ, sizeof(double) * nc, hipMemcpyDeviceToHost,
                            h->stream));
@@ -13488,6 +13742,114 @@ NX_API int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge
     HIPCALL(hipStreamSynchronize(h->stream));
   }
   return NX_OK;
+}
+
+}  // namespace
+
+NX_API int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                             const double* edge_f, const double* f_const, double rtol,
+                             int32_t kind, int32_t n_obs, const int32_t* obs_rows,
+                             const double* obs_w, const double* obs_d, double* value,
+                             double* grad_R, double* grad_bc, double* grad_f, int32_t* iters,
+                             double* relres, int32_t* converged) {
+  return batch_gradient_run(h, n_cols, nullptr, edge_bc, edge_f, f_const, rtol, kind, n_obs,
+                            obs_rows, obs_w, obs_d, value, grad_R, grad_bc, grad_f, iters, relres,
+                            converged);
+}
+
+// ---- ensembles: a resistance field per scenario ---------------------------
+NX_API int nx_ensemble_supported(nx_network_t* h, int32_t* ok) {
+  if (!h || !ok) return fail(NX_ERR_ARG, "null argument");
+  *ok = ensemble_ok(h) ? 1 : 0;
+  return NX_OK;
+}
+
+NX_API int nx_ensemble_solve(nx_network_t* h, int32_t n_cols, const double* edge_R,
+                             const double* edge_bc, const double* edge_f, const double* f_const,
+                             double rtol, int32_t order, double* out, int32_t* iters,
+                             double* relres, int32_t* converged) {
+  const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  CHECK(batch_check_args(h, n_cols, edge_bc, out));
+  if (!edge_R) return fail(NX_ERR_ARG, "edge_R is NULL");
+  if (!ensemble_ok(h)) {
+    if (batch_ok(h) && h->n_cyc > 0)
+      return fail(NX_ERR_STATE, "nx_ensemble_solve: a graph with cycles (the correction is per "
+                                "matrix); loop over nx_set_coefficients / nx_solve");
+    return fail(NX_ERR_STATE, "nx_ensemble_solve: the batched ensemble does not apply to this "
+                              "handle (nx_ensemble_supported)");
+  }
+  if (!h->have_lhs) return fail(NX_ERR_STATE, "assemble the matrix before nx_ensemble_solve");
+  if (order != 0 && !h->out_idx) return fail(NX_ERR_STATE, "nx_set_output_map first");
+  if (ensemble_R_bad(edge_R, (int64_t)n_cols * h->E))
+    return fail(NX_ERR_ARG, "nx_ensemble_solve: R must be finite and positive");
+  CHECK(set_device(h));
+  h->b_refined = h->b_fallback = 0;
+  h->b_launches = made_current;  // (the handle's lumped mass is not read: no ensure_dq)
+  int chunk = 0;
+  CHECK(batch_workspace(h, n_cols, &chunk, false, true));
+  h->b_chunk = chunk;
+  const BatchWs ws = batch_carve(h, h->bws_cap);
+  const BatchEns be = batch_ens(h, ws);
+  const int64_t n = h->n_own, ld = ws.cols.ld;
+  std::vector<double> stats;
+  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
+    const int nc = std::min(chunk, n_cols - c0);
+    CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const, edge_R));
+    CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.X, rtol, iters ? iters + c0 : nullptr,
+                           relres ? relres + c0 : nullptr, converged ? converged + c0 : nullptr,
+                           stats, &be));
+    const double* src = ws.X;
+    if (order != 0) {
+      hipLaunchKernelGGL(k_b_gather, dim3(grid_of(n, kBlock), nc), dim3(kBlock), 0, h->stream, ws.X,
+                         ld, h->out_idx, n, ws.D);
+      HIPCALL(hipGetLastError());
+      h->b_launches += 1;
+      src = ws.D;
+    }
+    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * n, src, sizeof(double) * n * nc,
+                           hipMemcpyDeviceToHost, h->stream));
+    HIPCALL(hipStreamSynchronize(h->stream));
+    for (int c = 0; c < nc; ++c)  // b = 0: x = 0 exactly (no division by ||b||)
+      if (stats[2 * c + 1] == 0.0) std::fill_n(out + (int64_t)(c0 + c) * n, n, 0.0);
+  }
+  return NX_OK;
+}
+
+NX_API int nx_stash_solution(nx_network_t* h, int32_t restore) {
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first (it writes the rhs)
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (restore && !h->stash_set) return fail(NX_ERR_STATE, "nx_stash_solution: nothing saved");
+  CHECK(set_device(h));
+  if (!h->stash) {
+    HIPCALL(hipMalloc((void**)&h->stash, sizeof(double) * 3 * (size_t)std::max<int64_t>(h->n_col, 1)));
+    h->stash_state = std::malloc(sizeof(BatchSaved));
+    if (!h->stash_state) return fail(NX_ERR_HIP, "nx_stash_solution: no host memory");
+  }
+  BatchWs ws{};
+  ws.save = h->stash;
+  BatchSaved* sv = static_cast<BatchSaved*>(h->stash_state);
+  if (restore) {
+    CHECK(batch_restore(h, ws, *sv, true));
+    h->stash_set = false;
+  } else {
+    CHECK(batch_save(h, ws, sv, true));
+    HIPCALL(hipStreamSynchronize(h->stream));
+    h->stash_set = true;
+  }
+  return NX_OK;
+}
+
+NX_API int nx_ensemble_gradient(nx_network_t* h, int32_t n_cols, const double* edge_R,
+                                const double* edge_bc, const double* edge_f,
+                                const double* f_const, double rtol, int32_t kind, int32_t n_obs,
+                                const int32_t* obs_rows, const double* obs_w, const double* obs_d,
+                                double* value, double* grad_R, double* grad_bc, double* grad_f,
+                                int32_t* iters, double* relres, int32_t* converged) {
+  if (!edge_R) return fail(NX_ERR_ARG, "edge_R is NULL");
+  return batch_gradient_run(h, n_cols, edge_R, edge_bc, edge_f, f_const, rtol, kind, n_obs,
+                            obs_rows, obs_w, obs_d, value, grad_R, grad_bc, grad_f, iters, relres,
+                            converged);
 }
 
 NX_API int nx_get_solution(nx_network_t* h, double* xo) {

@@ -93,13 +93,14 @@ BATCH_SINGLE_MAX_ROWS = 1 << 18
 
 
 class BatchResult:
-    """What :meth:`Solver.solve_many` returns.
+    """What :meth:`Solver.solve_many` and :meth:`Solver.solve_ensemble` return.
 
     ``x``: ``(B, n)``, every row in the reference's block order -- the concatenated functions
     ``[flux_color_0 .., pressure, global_flux]`` that ``solve()`` returns;
     ``iterations``, ``residual_norms``, ``converged``: ``(B,)`` each; ``path``: ``"batched"``
     (``nx_batch_solve``) or ``"sequential"`` (the per-scenario loop); ``info``: the dict of
-    ``nx_get_batch_info`` (launches, refined, fallback, chunk)."""
+    ``nx_get_batch_info`` (launches, refined, fallback, chunk; for ``solve_ensemble``
+    ``fallback`` counts the scenarios solved again by its sequential path)."""
 
     def __init__(self, assembler, x, iterations, residual_norms, converged, path, info):
         self._assembler = assembler
@@ -134,7 +135,8 @@ class GradientResult:
     respect to every edge's resistance and source; ``dp_bc``: ``(B, num_nodes)`` -- with respect
     to the nodal boundary pressure, zero off the boundary nodes; ``iterations``,
     ``residual_norms``, ``converged``: ``(B, 2)`` each, the forward and the adjoint solve;
-    ``info``: the dict of ``nx_get_batch_info`` (launches, refined, fallback, chunk)."""
+    ``info``: the dict of ``nx_get_batch_info`` (launches, refined, fallback, chunk). With
+    ``derivatives=False`` the derivatives are None and the three ``(B, 1)``: the forward solve."""
 
     def __init__(self, value, dR, df, dp_bc, iterations, residual_norms, converged, info):
         self.value = value
@@ -324,8 +326,94 @@ class Solver:
                 f"{rr[bad].tolist()} > rtol {self._rtol:.1e})")
         return res
 
+    def _ensemble_batched(self) -> bool:
+        """Whether the options and the handle put an ensemble on the batched path (the handle
+        configured as :meth:`solve` does it first)."""
+        asm = self.assembler
+        return (tuple(asm.degrees) == (1, 0) and self._direct and self._pc and self._pc_exact
+                and asm.handle.ensemble_supported())
+
+    @timed("nxfx:Solver:solve_ensemble")
+    def solve_ensemble(self, R, p_bc=None, f=None) -> "BatchResult":
+        """Solve B scenarios that differ in the resistance field: scenario j solves the system
+        of ``R[j]``. ``R``: ``(B, num_edges)`` in ``graph.edges()`` order, or ``(B,)`` constants;
+        ``p_bc``: None (the boundary data of the last ``compute_forms`` on every scenario) or B
+        items as :meth:`solve_many` takes them; ``f``: as for :meth:`solve_many`.
+
+        Where ``nx_ensemble_supported`` holds (P1/DG0, one rank, the direct solve, a forest)
+        the scenarios go through ``nx_ensemble_solve`` in one batched pass
+        (``path == "batched"``): a matrix per column, none of them assembled. The matrix of the
+        last ``compute_forms`` is assembled first if it is not current (the residual reads its
+        R-independent entries). A scenario the batched pass reports unconverged is solved again
+        by the sequential path and counted in ``info["fallback"]``.
+
+        Otherwise -- a graph with cycles, general degrees, ``ksp_type="minres"``,
+        ``pc_type="none"``, the lumped mass, or ``NXHIP_BATCH=0`` -- the per-scenario loop runs
+        (``"sequential"``): the scenario's coefficients are uploaded, R included, then assembly,
+        solve, gather. Afterwards the coefficients of the last ``compute_forms`` are put back,
+        the system is assembled again and the handle's solution, rhs and last-solve figures
+        are restored (``nx_stash_solution``), so a later ``solve()`` returns the bits it returned before. The reference has no
+        counterpart (it would loop ``compute_forms`` / ``assemble`` / ``solve``)."""
+        if self._closed:
+            raise RuntimeError("the solver has been destroyed")
+        asm = self.assembler
+        if getattr(asm, "_coefficients", None) is None:
+            raise RuntimeError("compute_forms() must be called before solve_ensemble()")
+        if getattr(asm, "_nranks", 1) > 1:
+            raise NotImplementedError("solve_ensemble runs on one rank; with several ranks loop "
+                                      "over compute_forms / assemble / solve")
+        edge_R, edge_bc, edge_f, f_const = asm.ensemble_coefficients(R, p_bc, f)
+        B = edge_R.shape[0]
+        h = asm.handle
+        self._configure()
+        batched = os.environ.get("NXHIP_BATCH", "") != "0" and self._ensemble_batched()
+        info = {"launches": 0, "refined": 0, "fallback": 0, "chunk": 1}
+        if batched:
+            if not asm.lhs_current:  # (the residual reads the +-1 entries of the values)
+                asm.assemble(assemble_lhs=True, assemble_rhs=False)
+            x, it, rr, conv = h.ensemble_solve(edge_R, edge_bc, edge_f, f_const, self._rtol,
+                                               blocks=True)
+            info = h.batch_info()
+            todo = np.flatnonzero(~conv)
+            info["fallback"] = int(todo.size)
+        else:
+            x = h.batch_output(B)  # page-locked and reused, as the batched path's
+            it = np.zeros(B, dtype=np.int32)
+            rr = np.zeros(B, dtype=np.float64)
+            conv = np.zeros(B, dtype=bool)
+            todo = np.arange(B)
+        if todo.size:
+            self._ensemble_loop(todo, edge_R, edge_bc, edge_f, f_const, x, it, rr, conv)
+        res = BatchResult(asm, x, it, rr, conv, "batched" if batched else "sequential", info)
+        if self._raise and not conv.all():
+            bad = np.flatnonzero(~conv)
+            raise _lib.NxNotConverged(
+                f"solve_ensemble: columns {bad.tolist()} did not converge (relative residuals "
+                f"{rr[bad].tolist()} > rtol {self._rtol:.1e})")
+        return res
+
+    def _ensemble_loop(self, todo, edge_R, edge_bc, edge_f, f_const, x, it, rr, conv) -> None:
+        """The sequential path of :meth:`solve_ensemble` on the scenarios ``todo``."""
+        asm = self.assembler
+        h = asm.handle
+        ce = self._check_every or (4 if asm.preconditioned else 32)
+        h.stash_solution(False)
+        try:
+            for j in todo:
+                asm.set_scenario_coefficients(edge_R[j], edge_bc[j],
+                                              None if f_const is None else float(f_const[j]),
+                                              None if edge_f is None else edge_f[j])
+                h.assemble(True, True)
+                it[j], rr[j], conv[j] = h.solve(self._rtol, self._maxit, ce)
+                h.solution_blocks(x[j])
+        finally:
+            asm.restore_coefficients()
+            asm.assemble(assemble_lhs=True, assemble_rhs=True)
+            h.stash_solution(True)  # (flushes that assembly, then x, rhs, the last solve's figures)
+
     @timed("nxfx:Solver:gradient")
-    def gradient(self, p_bc, f=None, *, rows, weights=None, data=None) -> "GradientResult":
+    def gradient(self, p_bc, f=None, *, rows, weights=None, data=None, R=None,
+                 derivatives: bool = True) -> "GradientResult":
         """Adjoint gradients of an observed-row objective for B scenarios against the matrix
         of the last ``compute_forms`` (``nx_batch_gradient``: two batched direct solves, no
         solution leaves the device).
@@ -341,12 +429,22 @@ class Solver:
         It runs where ``solve_many`` takes its batched path; elsewhere -- several ranks,
         general degrees, ``ksp_type="minres"``, ``pc_type="none"``, the lumped mass -- it
         raises ``NotImplementedError`` (there is no host fallback). The reference has no
-        counterpart."""
+        counterpart.
+
+        ``R`` (``(B, num_edges)`` or ``(B,)`` constants, as :meth:`solve_ensemble`): scenario j
+        is evaluated at ``R[j]`` instead of the last ``compute_forms``' R
+        (``nx_ensemble_gradient``; a forest only, elsewhere ``NotImplementedError``), and
+        ``p_bc`` may be None (the last ``compute_forms``' boundary data).
+        ``derivatives=False`` (with ``R``): the objective values alone -- the forward solves,
+        no adjoint; ``dR``, ``df`` and ``dp_bc`` are None and ``iterations``,
+        ``residual_norms``, ``converged`` are ``(B, 1)``."""
         if self._closed:
             raise RuntimeError("the solver has been destroyed")
         asm = self.assembler
         if getattr(asm, "_coefficients", None) is None:
             raise RuntimeError("compute_forms() must be called before gradient()")
+        if R is None and not derivatives:
+            raise NotImplementedError("derivatives=False needs R (the ensemble call)")
         if getattr(asm, "_nranks", 1) > 1:
             raise NotImplementedError("gradient runs on one rank")
         if tuple(asm.degrees) != (1, 0):
@@ -360,7 +458,11 @@ class Solver:
         if not self._pc_exact:
             raise NotImplementedError("gradient needs the consistent mass (pc_mass='lumped' "
                                       "is not exact)")
-        edge_bc, edge_f, f_const = asm.scenario_coefficients(p_bc, f)
+        if R is None:
+            edge_R = None
+            edge_bc, edge_f, f_const = asm.scenario_coefficients(p_bc, f)
+        else:
+            edge_R, edge_bc, edge_f, f_const = asm.ensemble_coefficients(R, p_bc, f)
         B = edge_bc.shape[0]
         h = asm.handle
         rows = np.asarray(rows)
@@ -386,8 +488,24 @@ class Solver:
             raise NotImplementedError("gradient: the batched direct solve does not apply to this "
                                       "handle (nx_batch_supported)")
         dev_rows = asm.block_order_rows()[rows]
-        value, gR, gbc, gf, it, rr, conv = h.batch_gradient(
-            edge_bc, edge_f, f_const, self._rtol, rows=dev_rows, weights=w, data=data)
+        if edge_R is not None:
+            if not h.ensemble_supported():
+                raise NotImplementedError("gradient(R=...): the batched ensemble does not apply "
+                                          "to this handle (nx_ensemble_supported)")
+            value, gR, gbc, gf, it, rr, conv = h.ensemble_gradient(
+                edge_R, edge_bc, edge_f, f_const, self._rtol, rows=dev_rows, weights=w,
+                data=data, derivatives=derivatives)
+        else:
+            value, gR, gbc, gf, it, rr, conv = h.batch_gradient(
+                edge_bc, edge_f, f_const, self._rtol, rows=dev_rows, weights=w, data=data)
+        if gR is None:  # the objective alone
+            res = GradientResult(value.copy(), None, None, None, it, rr, conv, h.batch_info())
+            if self._raise and not conv.all():
+                bad = np.flatnonzero(~conv.all(axis=1))
+                raise _lib.NxNotConverged(
+                    f"gradient: columns {bad.tolist()} did not converge (relative residuals "
+                    f"{rr[bad].tolist()} > rtol {self._rtol:.1e})")
+            return res
         # edge slots -> graph.edges() order, flux end rows -> boundary nodes (gathers: every
         # output is copied out of the handle's page-locked buffer, which the next call of this
         # batch size then reuses)
