@@ -582,6 +582,71 @@ int nx_ensemble_gradient(nx_network_t* h, int32_t n_cols, const double* edge_R,
                          int32_t* converged);
 int nx_stash_solution(nx_network_t* h, int32_t restore);
 
+/*
+ * Hessian-vector products of nx_batch_gradient's objective: per scenario j the product H_j v_j
+ * of the objective's Hessian with respect to (R, edge_bc, f) with a direction v_j = (dir_R,
+ * dir_bc, dir_f), exact, in four batched direct solves (the reference has no counterpart). A is
+ * affine in R, b linear in (edge_bc, f) and the device matrix symmetric, so with
+ *   Ad = sum_e dir_R[e] dA/dR_e   (dir_R[e] times the R = 1 P1 mass on edge e's flux rows)
+ *   bd = the right-hand side nx_batch_rhs forms from (dir_bc, dir_f)
+ * the solves are: forward A x = b and adjoint A mu = c(x) (nx_batch_gradient's), the tangent
+ * A xd = bd - Ad x, and the second-order adjoint A mud = cd - Ad mu with cd = w_i xd[r_i] on the
+ * observed rows (kind 1) or 0 (kind 0). With form(l, x)[e] the cell sum of grad_R above:
+ *   hess_R[j, e]     = -(form(mud, x)[e] + form(mu, xd)[e])
+ *   hess_bc[j, e, .] = mud at the edge's q_0 / q_N row
+ *   hess_f[j, e]     = -sum_k h_k mud[p_k]
+ * and grad_R / grad_bc / grad_f (each may be NULL) are nx_batch_gradient's, bit for bit, from
+ * the same pass. gauss_newton = 1 (kind 1 only): the second-order adjoint is A mud = cd and
+ * hess_R = -form(mud, x) -- the product with J^T W J of the observed values' Jacobian, positive
+ * semidefinite; no adjoint mu is solved (three solves), grad_* are ignored.
+ *   dir_R   n_cols x E or NULL;  dir_bc  n_cols x E x 2 or NULL;  dir_f  n_cols x E or NULL
+ *           (a NULL part is zero -- never the handle's source; any sign is legal)
+ *   value   n_cols;  hess_R  n_cols x E;  hess_bc  n_cols x E x 2 or NULL;  hess_f  n_cols x E
+ *           or NULL;  the other arguments as nx_batch_gradient
+ *   iters / relres / converged  4 x n_cols each or NULL: forward, adjoint, tangent, second-order
+ *           adjoint columns (gauss_newton: the adjoint quarter is left as it was; kind 0: its
+ *           one adjoint column's figures for every scenario)
+ * Every solve takes nx_batch_solve's per-column policy (residual check, refinement pass,
+ * single-column fallback); a zero right-hand side gives an exact zero, converged. Supported
+ * where nx_batch_supported says 1, else NX_ERR_STATE; the handle is left as nx_batch_gradient
+ * leaves it. The workspace of a handle that has asked grows by two more vectors and 5 E doubles
+ * per column (tangent, second-order adjoint; dir_R, hess_R, hess_f, hess_bc), behind everything
+ * the earlier calls use; dir_bc / dir_f pass through the forward inputs' buffers. A column's
+ * bits do not depend on the other columns, its position, n_cols or the chunk size.
+ * NX_ERR_ARG: nx_batch_gradient's cases (hess_R in grad_R's place), all three of dir_R / dir_bc /
+ * dir_f NULL, gauss_newton not 0 / 1, gauss_newton with kind 0.
+ *
+ * nx_get_batch_info then reports this call (refined: the columns of all four solves). Steady
+ * launches when nothing is refined, S = 5 on a forest and 7 with cycles as above; the count
+ * does not depend on n_cols inside a chunk nor on which direction parts are NULL:
+ *   kind 1            per chunk  1 (rhs) + S + 1 (k_b_obs) + S + 1 (rhs of the direction)
+ *                                + 1 (k_b_mass_apply) + S + 1 (k_b_obs_dir) + 1 (k_b_mass_apply)
+ *                                + S + 1 (k_b_edge_form2) = 4 S + 7: 27 / 35
+ *   kind 0            per call   1 (k_b_obs) + S: 6 / 8;  per chunk  3 S + 7: 22 / 28
+ *   gauss_newton      per chunk  3 S + 6: 21 / 27   (no adjoint solve, one k_b_mass_apply)
+ * and 6 / 8 more for each refinement pass.
+ *
+ * nx_ensemble_hvp: the same with scenario j evaluated at R_j (edge_R as nx_ensemble_solve): all
+ * four solves of a column run against the column's matrix, dA/dR_e does not depend on R, the
+ * adjoint is per column for both kinds. No single-column fallback: a column still above rtol
+ * is reported converged = 0 in its quarter. Supported where nx_ensemble_supported says 1.
+ * Launches per chunk with S = 5: 4 S + 7 = 27 (both kinds), 3 S + 6 = 21 with gauss_newton.
+ */
+int nx_batch_hvp(nx_network_t* h, int32_t n_cols, const double* edge_bc, const double* edge_f,
+                 const double* f_const, double rtol, int32_t kind, int32_t n_obs,
+                 const int32_t* obs_rows, const double* obs_w, const double* obs_d,
+                 const double* dir_R, const double* dir_bc, const double* dir_f,
+                 int32_t gauss_newton, double* value, double* grad_R, double* grad_bc,
+                 double* grad_f, double* hess_R, double* hess_bc, double* hess_f, int32_t* iters,
+                 double* relres, int32_t* converged);
+int nx_ensemble_hvp(nx_network_t* h, int32_t n_cols, const double* edge_R, const double* edge_bc,
+                    const double* edge_f, const double* f_const, double rtol, int32_t kind,
+                    int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
+                    const double* obs_d, const double* dir_R, const double* dir_bc,
+                    const double* dir_f, int32_t gauss_newton, double* value, double* grad_R,
+                    double* grad_bc, double* grad_f, double* hess_R, double* hess_bc,
+                    double* hess_f, int32_t* iters, double* relres, int32_t* converged);
+
 /* Copy the owned part of the solution / rhs to the host (n_rows doubles). */
 int nx_get_solution(nx_network_t* h, double* x);
 int nx_get_rhs(nx_network_t* h, double* b);

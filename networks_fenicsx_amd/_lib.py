@@ -63,6 +63,12 @@ _SIGS = {
     "nx_ensemble_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd,
                                        _pd, _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
     "nx_stash_solution": (C.c_int, [_h, _i32]),
+    "nx_batch_hvp": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd, _pd,
+                               _pd, _pd, _pd, _i32, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _pi32,
+                               _pd, _pi32]),
+    "nx_ensemble_hvp": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd,
+                                  _pd, _pd, _pd, _pd, _i32, _pd, _pd, _pd, _pd, _pd, _pd, _pd,
+                                  _pi32, _pd, _pi32]),
     "nx_get_solution": (C.c_int, [_h, _pd]),
     "nx_get_rhs": (C.c_int, [_h, _pd]),
     "nx_set_output_map": (C.c_int, [_h, _i64, _pi32]),
@@ -545,9 +551,68 @@ class Handle:
         return self._gradient_call(edge_R, edge_bc, edge_f, f_const, rtol, rows, weights, data,
                                    derivatives)
 
+    def batch_hvp(self, edge_bc, edge_f=None, f_const=None, rtol: float = 1e-12, *, rows,
+                  weights, data=None, dir_R=None, dir_bc=None, dir_f=None, edge_R=None,
+                  gauss_newton: bool = False):
+        """``nx_batch_hvp`` (``edge_R`` None) or ``nx_ensemble_hvp``: ``(value (B,), grad_R,
+        grad_bc, grad_f, hess_R (B, E), hess_bc (B, E, 2), hess_f (B, E), iterations, relres,
+        converged)``. The directions ``dir_R (B, E)``, ``dir_bc (B, E, 2)``, ``dir_f (B, E)``
+        are in the local edge order, None meaning zero. Full mode: the three gradients as
+        :meth:`batch_gradient` and the status arrays ``(B, 4)`` -- forward, adjoint, tangent,
+        second-order adjoint; ``gauss_newton``: the gradients are None and the status arrays
+        ``(B, 3)`` -- forward, tangent, second-order adjoint."""
+        B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
+        eR = None if edge_R is None else self._ensemble_R(edge_R, B)
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != rows.size:
+            raise ValueError("one weight per observed row")
+        d = None if data is None else np.ascontiguousarray(data, dtype=np.float64)
+        if d is not None and d.shape != (B, rows.size):
+            raise ValueError("data must be (B, n_obs)")
+        E = self.n_edges
+        dirs = []
+        for name, v, shape in (("dir_R", dir_R, (B, E)), ("dir_bc", dir_bc, (B, E, 2)),
+                               ("dir_f", dir_f, (B, E))):
+            v = None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+            if v is not None and v.shape != shape:
+                raise ValueError(f"{name} must be {shape}")
+            dirs.append(v)
+        # one page-locked buffer for the seven outputs, pooled per batch size as the gradient's
+        pools = self.__dict__.setdefault("_batch_pools", {})
+        pool = pools.pop(("hvp", B), None)
+        if pool is None:
+            pool = PinnedPool(B * (8 * E + 1))
+            while len(pools) >= self._BATCH_POOLS:
+                pools.pop(next(iter(pools))).close()
+        pools[("hvp", B)] = pool
+        buf = pool.take()
+        value, blocks = buf[:B], buf[B:].reshape(8, B * E)
+        gR, gf, hR, hf = (blocks[i].reshape(B, E) for i in (0, 1, 4, 5))
+        gbc, hbc = blocks[2:4].reshape(B, E, 2), blocks[6:8].reshape(B, E, 2)
+        it = np.zeros((4, B), dtype=np.int32)
+        rr = np.zeros((4, B), dtype=np.float64)
+        cv = np.zeros((4, B), dtype=np.int32)
+        gn = bool(gauss_newton)
+        head = (self.ptr, B) + (() if eR is None else (_ptr(eR, C.c_double),))
+        head += (_ptr(bc, C.c_double), _ptr(ef, C.c_double), _ptr(fc, C.c_double))
+        tail = (float(rtol), 0 if d is None else 1, int(rows.size), _ptr(rows, C.c_int32),
+                _ptr(w, C.c_double), _ptr(d, C.c_double), *[_ptr(v, C.c_double) for v in dirs],
+                1 if gn else 0, _ptr(value, C.c_double),
+                *[_ptr(None if gn else g, C.c_double) for g in (gR, gbc, gf)],
+                _ptr(hR, C.c_double), _ptr(hbc, C.c_double), _ptr(hf, C.c_double),
+                _ptr(it, C.c_int32), _ptr(rr, C.c_double), _ptr(cv, C.c_int32))
+        fn = lib().nx_batch_hvp if eR is None else lib().nx_ensemble_hvp
+        check(fn(*head, *tail))
+        if gn:
+            keep = [0, 2, 3]
+            return (value, None, None, None, hR, hbc, hf, it[keep].T.copy(), rr[keep].T.copy(),
+                    cv[keep].T.astype(bool))
+        return value, gR, gbc, gf, hR, hbc, hf, it.T.copy(), rr.T.copy(), cv.T.astype(bool)
+
     def batch_info(self) -> dict:
         """``nx_get_batch_info`` of the last :meth:`batch_solve`, :meth:`batch_gradient`,
-        :meth:`ensemble_solve` or :meth:`ensemble_gradient`."""
+        :meth:`ensemble_solve`, :meth:`ensemble_gradient` or :meth:`batch_hvp`."""
         v = [C.c_int32() for _ in range(4)]
         check(lib().nx_get_batch_info(self.ptr, *[C.byref(x) for x in v]))
         return dict(zip(("launches", "refined", "fallback", "chunk"), (int(x.value) for x in v)))

@@ -186,6 +186,58 @@ def ensemble_resistances(mesh: NetworkMesh, edge_ids: np.ndarray, R) -> np.ndarr
     return np.ascontiguousarray(out)
 
 
+def hvp_directions(mesh: NetworkMesh, edge_ids: np.ndarray, B: int, v_R=None, v_p_bc=None,
+                   v_f=None):
+    """The direction of B Hessian-vector products, as ``nx_batch_hvp`` takes it (no device):
+    ``(dir_R (B, E) | None, dir_bc (B, E, 2) | None, dir_f (B, E) | None)`` in the local edge
+    order ``edge_ids``. A part given as None stays None and means zero -- never the resident
+    source, as ``batch_coefficients(f=None)`` would read it.
+
+    ``v_R``: ``(B, num_edges)`` or ``(num_edges,)`` (the same for every scenario) in
+    ``graph.edges()`` order; a direction, so any sign is accepted. ``v_p_bc``: nodal values
+    ``(B, num_nodes)`` or ``(num_nodes,)``, mapped by :func:`edge_boundary_rhs` (linear: only
+    the boundary nodes' entries matter). ``v_f``: ``(B, num_edges)``, ``(num_edges,)`` or
+    ``(B,)`` constants, one per scenario (where ``num_edges == B`` a 1-D ``v_f`` is read per
+    edge). Every value must be finite; all three None is an error."""
+    edge_ids = np.asarray(edge_ids)
+    E, nn = mesh.num_edges, mesh.num_nodes
+    if B < 1:
+        raise ValueError("at least one scenario is needed")
+    if v_R is None and v_p_bc is None and v_f is None:
+        raise ValueError("a direction is needed: v_R, v_p_bc or v_f")
+
+    def rows_of(v, name, width):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 1 and a.size == width:
+            a = np.broadcast_to(a, (B, width))
+        if a.shape != (B, width):
+            raise ValueError(f"{name} must be ({B}, {width}) or ({width},), got shape {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"{name} must be finite")
+        return a
+
+    dir_R = dir_bc = dir_f = None
+    if v_R is not None:
+        dir_R = np.ascontiguousarray(rows_of(v_R, "v_R", E)[:, edge_ids])
+    if v_p_bc is not None:
+        vp = rows_of(v_p_bc, "v_p_bc", nn)
+        dir_bc = np.empty((B, edge_ids.size, 2), dtype=np.float64)
+        for j in range(B):
+            dir_bc[j] = edge_boundary_rhs(mesh, edge_ids, vp[j])
+    if v_f is not None:
+        a = np.asarray(v_f, dtype=np.float64)
+        if a.ndim == 1 and a.size == B and a.size != E:  # B constants
+            if not np.isfinite(a).all():
+                raise ValueError("v_f must be finite")
+            dir_f = np.repeat(a[:, None], edge_ids.size, axis=1)
+        else:
+            try:
+                dir_f = np.ascontiguousarray(rows_of(a, "v_f", E)[:, edge_ids])
+            except ValueError as exc:
+                raise ValueError(f"{exc} (or ({B},) constants)") from None
+    return dir_R, dir_bc, dir_f
+
+
 def _scalar(c, name: str, default: float) -> float:
     if c is None:
         return default
@@ -844,6 +896,10 @@ class HydraulicNetworkAssembler:
         if edge_bc.shape[0] != B:
             raise ValueError(f"R gives {B} scenarios, p_bc {edge_bc.shape[0]}")
         return edge_R, edge_bc, edge_f, f_const
+
+    def hvp_directions(self, B: int, v_R=None, v_p_bc=None, v_f=None):
+        """:func:`hvp_directions` for this assembler's mesh and local edges."""
+        return hvp_directions(self._network_mesh, self._edge_ids, B, v_R, v_p_bc, v_f)
 
     def set_scenario_coefficients(self, edge_R: np.ndarray, edge_bc: np.ndarray,
                                   f_const: float | None, edge_f: np.ndarray | None) -> None:

@@ -3978,6 +3978,313 @@ __global__ __launch_bounds__(kBlock) void k_b_edge_form(FormArgs a) {
 }
 
 // --------------------------------------------------------------------------------------
+// Hessian-vector products of the observed-row objective (nx_batch_hvp). A is
+// affine in R, b linear in (edge_bc, f) and A_dev symmetric, so with a direction (v_R, v_bc,
+// v_f) the tangent A xd = bd - Ad x and the second-order adjoint A ld = cd - Ad l (Ad =
+// sum_e v_R[e] dA/dR_e, bd = k_b_rhs of (v_bc, v_f), cd = W xd on the observed rows or 0) are
+// two more batched solves; the outputs are contractions over the edge's rows.
+//
+// k_b_mass_apply: Y -= Ad Z per (column, edge), grid = (edge blocks, columns), the lane shapes
+// of k_b_edge_form. dA/dR_e is the R = 1 P1 mass on the edge's flux vertex rows, so with the
+// cell lengths h_k as form_cell_len forms them (h_{-1} = h_N = 0: one cell at either end)
+//   Y[q_k] = Y[q_k] - v_R[col, e] * t_k,
+//   t_k = ((h_{k-1}/6) z_{k-1} + (h_{k-1}/3 + h_k/3) z_k) + (h_k/6) z_{k+1}
+// -- the three products summed left to right, no contraction. Column col of Z at col z_ld
+// (z_ld = 0: the one adjoint column of the linear objective). Z and Y never alias.
+struct MassArgs {
+  EdgeArgs ea;
+  const double* Z;
+  int64_t z_ld;
+  const double* vR;  // column col at col E
+  double* Y;
+  int64_t ld;
+};
+
+__device__ __forceinline__ double mass_row(double hm, double h, double zm, double z, double zp) {
+#pragma clang fp contract(off)
+  const double a = (hm / 6.0) * zm, b = (hm / 3.0 + h / 3.0) * z, c = (h / 6.0) * zp;
+  return (a + b) + c;
+}
+
+// Small N (N < S <= 32): one S-lane segment per edge, lane k holds vertex q_k and cell k
+// (lane N the closing vertex, no cell); the neighbours' z and the cell before come by the
+// segment moves.
+template <int S>
+__global__ __launch_bounds__(kBlock) void k_b_mass_apply_seg(MassArgs a) {
+#pragma clang fp contract(off)
+  constexpr int EPW = 64 / S;
+  const int lane = threadIdx.x & 63;
+  const int sub = lane / S, cl = lane % S;
+  const int64_t E = a.ea.E;
+  const int64_t e0 = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * EPW;
+  if (e0 >= E) return;  // wave-uniform
+  const int ne = (int)min<int64_t>(EPW, E - e0);
+  const int64_t e = e0 + min(sub, ne - 1);  // idle segments shadow the last edge
+  const bool mine = sub < ne;
+  const int N = a.ea.N;
+  const int col = blockIdx.y;
+  const int64_t base = e * (2 * N + 1);
+  const double* z = a.Z + col * a.z_ld + base;
+  double zq = 0.0, h = 0.0;
+  if (mine && cl <= N) zq = z[2 * cl];
+  if (mine && cl < N) {
+    double x0[3], x1[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      x0[c] = a.ea.edge_x[6 * e + c];
+      x1[c] = a.ea.edge_x[6 * e + 3 + c];
+    }
+    h = form_cell_len(x0, x1, cl, N, 1.0 / (double)N);
+  }
+  // (a lane with no source in its segment takes its own value: its h on that side is 0)
+  const double zm = seg_up<S, 1>(zq), zp = seg_down<S, 1>(zq);
+  double hm = seg_up<S, 1>(h);
+  if (cl == 0) hm = 0.0;
+  if (mine && cl <= N) {
+    const double t = mass_row(hm, h, zm, zq, zp);
+    double* y = a.Y + col * a.ld + base + 2 * cl;
+    *y = *y - a.vR[col * E + e] * t;
+  }
+}
+
+// N >= 32: one wave per edge, the vertices q_0 .. q_N in chunks of 64 taken in order; across a
+// chunk boundary the neighbour's z is one uniform load and the cell before is formed again.
+__global__ __launch_bounds__(kBlock) void k_b_mass_apply(MassArgs a) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int64_t E = a.ea.E;
+  const int64_t e = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (e >= E) return;  // wave-uniform
+  const int N = a.ea.N;
+  const double invN = 1.0 / (double)N;
+  const int col = blockIdx.y;
+  const int64_t base = e * (2 * N + 1);
+  const double* z = a.Z + col * a.z_ld + base;
+  double* y = a.Y + col * a.ld + base;
+  const double v = a.vR[col * E + e];
+  double x0[3], x1[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    x0[c] = a.ea.edge_x[6 * e + c];
+    x1[c] = a.ea.edge_x[6 * e + 3 + c];
+  }
+  for (int c0 = 0; c0 <= N; c0 += 64) {
+    const int nv = min(64, N + 1 - c0);  // vertices of this chunk
+    const int k = c0 + lane;
+    double zq = 0.0, h = 0.0;
+    if (lane < nv) zq = z[2 * k];
+    if (lane < nv && k < N) h = form_cell_len(x0, x1, k, N, invN);
+    // the vertex before the chunk and the one after it (uniform; the edge's own ends: none)
+    const double zb = c0 > 0 ? z[2 * (c0 - 1)] : 0.0;
+    const double hb = c0 > 0 ? form_cell_len(x0, x1, c0 - 1, N, invN) : 0.0;
+    const double ze = c0 + nv <= N ? z[2 * (c0 + nv)] : 0.0;
+    double zm = __shfl(zq, max(lane - 1, 0), 64), hm = __shfl(h, max(lane - 1, 0), 64);
+    double zp = __shfl(zq, min(lane + 1, 63), 64);
+    if (lane == 0) {
+      zm = zb;
+      hm = hb;
+    }
+    if (lane == nv - 1) zp = ze;
+    if (lane < nv) {
+      const double t = mass_row(hm, h, zm, zq, zp);
+      y[2 * k] = y[2 * k] - v * t;
+    }
+  }
+}
+
+// The second-order adjoint's right-hand side before k_b_mass_apply: every workgroup zeroes its
+// slice of C's column (k_b_obs's slices); least squares (kind 1) then writes w_i xd[r_i] at the
+// observed rows that fall into it, the linear objective (kind 0) nothing (its cd is 0).
+__global__ __launch_bounds__(kObsThreads) void k_b_obs_dir(const double* __restrict__ Xd,
+                                                           int64_t ld, int64_t n, int kind,
+                                                           int n_obs,
+                                                           const int* __restrict__ rows,
+                                                           const double* __restrict__ w,
+                                                           double* __restrict__ C) {
+#pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const double* xd = Xd + col * ld;
+  double* c = C + col * ld;
+  const int64_t r0 = (int64_t)blockIdx.x * kObsSpan, r1 = min<int64_t>(n, r0 + kObsSpan);
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += kObsThreads) c[i] = 0.0;
+  if (!kind) return;  // grid-uniform
+  __syncthreads();
+  for (int i = threadIdx.x; i < n_obs; i += kObsThreads) {
+    const int r = rows[i];
+    if (r >= r0 && r < r1) c[r] = w[i] * xd[r];
+  }
+}
+
+// k_b_edge_form2: per (column, edge) every output of a Hessian-vector product in one pass over
+// the edge's rows, k_b_edge_form's lane shapes, expressions (form_cell_R) and sums:
+//   HR[e]  = -(form(ld, x)[e] + form(l, xd)[e])   (a cell's two terms added, then summed)
+//   Hf[e]  = sum_k -(h_k ld[p_k]),   Hbc[e] = ld[q_0], ld[q_N]
+// and, with L (full mode), k_b_edge_form's gR, gf, gbc from the same loads, bit for bit. L
+// null (Gauss-Newton): HR[e] = -form(ld, x)[e], no gradient. Column col of L at col l_ld.
+struct Form2Args {
+  EdgeArgs ea;
+  const double *X, *Xd, *L, *Ld;
+  int64_t ld, l_ld;
+  double *gR, *gf, *gbc, *HR, *Hf, *Hbc;
+};
+
+template <int S>
+__global__ __launch_bounds__(kBlock) void k_b_edge_form2_seg(Form2Args a) {
+#pragma clang fp contract(off)
+  constexpr int EPW = 64 / S;
+  const int lane = threadIdx.x & 63;
+  const int sub = lane / S, cl = lane % S;
+  const int64_t E = a.ea.E;
+  const int64_t e0 = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * EPW;
+  if (e0 >= E) return;  // wave-uniform
+  const int ne = (int)min<int64_t>(EPW, E - e0);
+  const int64_t e = e0 + min(sub, ne - 1);  // idle segments shadow the last edge
+  const bool mine = sub < ne;
+  const bool full = a.L != nullptr;  // grid-uniform
+  const int N = a.ea.N;
+  const int col = blockIdx.y;
+  const int64_t base = e * (2 * N + 1);
+  const double* x = a.X + col * a.ld + base;
+  const double* xd = a.Xd + col * a.ld + base;
+  const double* l = full ? a.L + col * a.l_ld + base : nullptr;
+  const double* ld = a.Ld + col * a.ld + base;
+  double xq = 0.0, lq = 0.0, lp = 0.0, xdq = 0.0, ldq = 0.0, ldp = 0.0, h = 0.0;
+  if (mine && cl <= N) {
+    xq = x[2 * cl];
+    ldq = ld[2 * cl];
+    if (full) {
+      lq = l[2 * cl];
+      xdq = xd[2 * cl];
+    }
+  }
+  if (mine && cl < N) {
+    ldp = ld[2 * cl + 1];
+    if (full) lp = l[2 * cl + 1];
+    double x0[3], x1[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      x0[c] = a.ea.edge_x[6 * e + c];
+      x1[c] = a.ea.edge_x[6 * e + 3 + c];
+    }
+    h = form_cell_len(x0, x1, cl, N, 1.0 / (double)N);
+  }
+  // q_{k+1} from the next lane (lane N and the lanes after it: unused)
+  const double xq1 = seg_down<S, 1>(xq), ldq1 = seg_down<S, 1>(ldq);
+  const double lq1 = seg_down<S, 1>(lq), xdq1 = seg_down<S, 1>(xdq);
+  double tR = 0.0, tf = 0.0, tH = 0.0, tHf = 0.0;
+  if (mine && cl < N) {
+    tH = form_cell_R(h, xq, xq1, ldq, ldq1);
+    tHf = -(h * ldp);
+    if (full) {
+      tH = tH + form_cell_R(h, xdq, xdq1, lq, lq1);
+      tR = form_cell_R(h, xq, xq1, lq, lq1);
+      tf = -(h * lp);
+    }
+  }
+#pragma unroll
+  for (int o = S / 2; o > 0; o >>= 1) {
+    tR += __shfl_xor(tR, o, 64);
+    tf += __shfl_xor(tf, o, 64);
+    tH += __shfl_xor(tH, o, 64);
+    tHf += __shfl_xor(tHf, o, 64);
+  }
+  if (mine && cl == 0) {
+    a.HR[col * E + e] = -tH;
+    a.Hf[col * E + e] = tHf;
+    a.Hbc[(col * E + e) * 2] = ldq;
+    if (full) {
+      a.gR[col * E + e] = -tR;
+      a.gf[col * E + e] = tf;
+      a.gbc[(col * E + e) * 2] = lq;
+    }
+  }
+  if (mine && cl == N) {
+    a.Hbc[(col * E + e) * 2 + 1] = ldq;
+    if (full) a.gbc[(col * E + e) * 2 + 1] = lq;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_b_edge_form2(Form2Args a) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int64_t E = a.ea.E;
+  const int64_t e = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (e >= E) return;  // wave-uniform
+  const bool full = a.L != nullptr;  // grid-uniform
+  const int N = a.ea.N;
+  const double invN = 1.0 / (double)N;
+  const int col = blockIdx.y;
+  const int64_t base = e * (2 * N + 1);
+  const double* x = a.X + col * a.ld + base;
+  const double* xd = a.Xd + col * a.ld + base;
+  const double* l = full ? a.L + col * a.l_ld + base : x;  // (never read when !full)
+  const double* ld = a.Ld + col * a.ld + base;
+  double x0[3], x1[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    x0[c] = a.ea.edge_x[6 * e + c];
+    x1[c] = a.ea.edge_x[6 * e + 3 + c];
+  }
+  double accR = 0.0, accf = 0.0, accH = 0.0, accHf = 0.0;
+  for (int c0 = 0; c0 < N; c0 += 64) {
+    const int nc = min(64, N - c0);
+    const int k = c0 + lane;
+    double xq = 0.0, lq = 0.0, lp = 0.0, xdq = 0.0, ldq = 0.0, ldp = 0.0, h = 0.0;
+    if (lane < nc) {
+      xq = x[2 * k];
+      ldq = ld[2 * k];
+      ldp = ld[2 * k + 1];
+      if (full) {
+        lq = l[2 * k];
+        lp = l[2 * k + 1];
+        xdq = xd[2 * k];
+      }
+      h = form_cell_len(x0, x1, k, N, invN);
+    }
+    const int ke = 2 * (c0 + nc);  // the chunk's closing vertex: uniform loads
+    const double xe = x[ke], lde = ld[ke];
+    const double le = full ? l[ke] : 0.0, xde = full ? xd[ke] : 0.0;
+    const int nx = min(lane + 1, 63);
+    double xq1 = __shfl(xq, nx, 64), ldq1 = __shfl(ldq, nx, 64);
+    double lq1 = __shfl(lq, nx, 64), xdq1 = __shfl(xdq, nx, 64);
+    if (lane == nc - 1) {
+      xq1 = xe;
+      ldq1 = lde;
+      lq1 = le;
+      xdq1 = xde;
+    }
+    double tR = 0.0, tf = 0.0, tH = 0.0, tHf = 0.0;
+    if (lane < nc) {
+      tH = form_cell_R(h, xq, xq1, ldq, ldq1);
+      tHf = -(h * ldp);
+      if (full) {
+        tH = tH + form_cell_R(h, xdq, xdq1, lq, lq1);
+        tR = form_cell_R(h, xq, xq1, lq, lq1);
+        tf = -(h * lp);
+      }
+    }
+    accH += wave_sum(tH);
+    accHf += wave_sum(tHf);
+    if (full) {
+      accR += wave_sum(tR);
+      accf += wave_sum(tf);
+    }
+  }
+  if (lane == 0) {
+    a.HR[col * E + e] = -accH;
+    a.Hf[col * E + e] = accHf;
+    a.Hbc[(col * E + e) * 2] = ld[0];
+    a.Hbc[(col * E + e) * 2 + 1] = ld[2 * N];
+    if (full) {
+      a.gR[col * E + e] = -accR;
+      a.gf[col * E + e] = accf;
+      a.gbc[(col * E + e) * 2] = l[0];
+      a.gbc[(col * E + e) * 2 + 1] = l[2 * N];
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------
 // Ensembles (nx_ensemble_solve): a matrix per column, A(R_c). The sweeps see R through the
 // lumped mass alone (ChainLane::setup), so a chunk's set-up writes every column's own dq beside
 // its right-hand side, and the true residual regenerates the R-dependent entries per column.
@@ -8185,6 +8492,7 @@ struct nx_network {
   // nx_ensemble_solve / nx_ensemble_gradient: whether it carries every column's own lumped
   // mass and R (kept once an ensemble call has asked for them)
   bool bws_ens = false;
+  bool bws_hvp = false;  // nx_batch_hvp asked: the tangent / second adjoint columns, direction, outputs
   void* gobs = nullptr;
   size_t gobs_bytes = 0;
   // nx_stash_solution: x | tmp | rhs (3 n_col) and the published state (a BatchSaved, malloc'ed)
@@ -13092,19 +13400,23 @@ struct BatchWs {
   double *C, *L;          // nx_batch_gradient (bws_grad): adjoint rhs and solution, cap x ld
   double *gJ, *gR, *gf, *gbc;  // and its outputs: cap, cap x E, cap x E, cap x 2 E
   double *edq, *eR;       // ensembles (bws_ens): the column's lumped mass and R, cap x E (N + 1), cap x E
+  double *Xd, *Ld;        // nx_batch_hvp (bws_hvp): tangent and second-order adjoint, cap x ld
+  double *vR;             // the direction's v_R, cap x E (v_bc / v_f reuse bc / ef)
+  double *HR, *Hf, *Hbc;  // and its outputs: cap x E, cap x E, cap x 2 E
   int* list;              // cap
   int nblk;
 };
 
-size_t batch_col_doubles(const nx_network* h, bool grad, bool ens) {
+size_t batch_col_doubles(const nx_network* h, bool grad, bool ens, bool hvp) {
   const int64_t E = h->E, S = std::max<int64_t>(h->pc_slots, 1), m = 2 * (int64_t)h->n_cyc;
   const int nblk = grid_of(h->n_own, kBlock);
   const int64_t g = grad ? 2 * h->n_col + 4 * E + 1 : 0;  // X stays resident beside C and L
   const int64_t en = ens ? E * (int64_t)(h->N + 1) + E : 0;  // the column's own dq and R
-  return (size_t)(4 * h->n_col + 3 * E + 5 * S + 3 * E + 1 + 2 * nblk + 2 + m + g + en);
+  const int64_t hv = hvp ? 2 * h->n_col + 5 * E : 0;  // Xd, Ld; v_R, HR, Hf, Hbc
+  return (size_t)(4 * h->n_col + 3 * E + 5 * S + 3 * E + 1 + 2 * nblk + 2 + m + g + en + hv);
 }
-size_t batch_bytes(const nx_network* h, int cap, bool grad, bool ens) {
-  return 8 * (batch_col_doubles(h, grad, ens) * (size_t)cap + (size_t)(3 * h->n_col)) +
+size_t batch_bytes(const nx_network* h, int cap, bool grad, bool ens, bool hvp) {
+  return 8 * (batch_col_doubles(h, grad, ens, hvp) * (size_t)cap + (size_t)(3 * h->n_col)) +
          sizeof(int) * (size_t)cap + 64;
 }
 BatchWs batch_carve(const nx_network* h, int cap) {
@@ -13153,6 +13465,14 @@ BatchWs batch_carve(const nx_network* h, int cap) {
     w.edq = take(cap * E * (int64_t)(h->N + 1));
     w.eR = take(cap * E);
   }
+  if (h->bws_hvp) {  // (last: what came before keeps its place)
+    w.Xd = take(cap * ld);
+    w.Ld = take(cap * ld);
+    w.vR = take(cap * E);
+    w.HR = take(cap * E);
+    w.Hf = take(cap * E);
+    w.Hbc = take(cap * 2 * E);
+  }
   w.list = reinterpret_cast<int*>(p);
   return w;
 }
@@ -13168,37 +13488,38 @@ bool batch_ok(const nx_network* h) {
 // size follows the decomposition's slots and the cycle chains, which nx_set_preconditioner
 // and nx_set_cycles change after a workspace was allocated (nx_batch_rhs is legal before
 // either), so the allocated bytes are checked, not the column count alone.
-bool batch_fits(const nx_network* h, int chunk, bool grad, bool ens) {
+bool batch_fits(const nx_network* h, int chunk, bool grad, bool ens, bool hvp) {
   return h->bws != nullptr && chunk <= h->bws_cap && (!grad || h->bws_grad) &&
-         (!ens || h->bws_ens) &&
-         batch_bytes(h, h->bws_cap, h->bws_grad, h->bws_ens) <= h->bws_bytes;
+         (!ens || h->bws_ens) && (!hvp || h->bws_hvp) &&
+         batch_bytes(h, h->bws_cap, h->bws_grad, h->bws_ens, h->bws_hvp) <= h->bws_bytes;
 }
 
 // The chunk size of this call and a workspace that holds it: NXHIP_BATCH_CHUNK (read per
 // call) or the largest of <= kBatchChunkMax whose workspace fits kBatchMemShare of the free
 // device memory; a failed allocation halves it down to 1.
 int batch_workspace(nx_network* h, int n_cols, int* chunk_out, bool grad = false,
-                    bool ens = false) {
-  grad = grad || h->bws_grad;
+                    bool ens = false, bool hvp = false) {
+  hvp = hvp || h->bws_hvp;
+  grad = grad || hvp || h->bws_grad;  // (the Hessian-vector product implies the gradient's part)
   ens = ens || h->bws_ens;
   int chunk = std::min(n_cols, kBatchChunkMax);
   const char* e = std::getenv("NXHIP_BATCH_CHUNK");
   if (e != nullptr && std::atoi(e) > 0) {
     chunk = std::min(std::min(std::atoi(e), kBatchChunkEnvMax), n_cols);
-  } else if (!batch_fits(h, chunk, grad, ens)) {
+  } else if (!batch_fits(h, chunk, grad, ens, hvp)) {
     size_t fr = 0, tot = 0;
     HIPCALL(hipMemGetInfo(&fr, &tot));
     const double room = kBatchMemShare * (double)fr;
-    while (chunk > 1 && (double)batch_bytes(h, chunk, grad, ens) > room) --chunk;
+    while (chunk > 1 && (double)batch_bytes(h, chunk, grad, ens, hvp) > room) --chunk;
   }
-  if (!batch_fits(h, chunk, grad, ens)) {
+  if (!batch_fits(h, chunk, grad, ens, hvp)) {
     HIPCALL(hipStreamSynchronize(h->stream));
     if (h->bws) (void)hipFree(h->bws);
     h->bws = nullptr;
     h->bws_cap = 0;
     h->bws_bytes = 0;
     for (;;) {
-      if (hipMalloc(&h->bws, batch_bytes(h, chunk, grad, ens)) == hipSuccess) break;
+      if (hipMalloc(&h->bws, batch_bytes(h, chunk, grad, ens, hvp)) == hipSuccess) break;
       (void)hipGetLastError();
       h->bws = nullptr;
       if (chunk == 1) return fail(NX_ERR_HIP, "nx_batch_solve: no memory for one column's workspace");
@@ -13207,7 +13528,8 @@ int batch_workspace(nx_network* h, int n_cols, int* chunk_out, bool grad = false
     h->bws_cap = chunk;
     h->bws_grad = grad;
     h->bws_ens = ens;
-    h->bws_bytes = batch_bytes(h, chunk, grad, ens);
+    h->bws_hvp = hvp;
+    h->bws_bytes = batch_bytes(h, chunk, grad, ens, hvp);
   }
   *chunk_out = chunk;
   return NX_OK;
@@ -13608,6 +13930,44 @@ bool ensemble_R_bad(const double* edge_R, int64_t count) {
 // per matrix: 2 n_cyc solves per column).
 bool ensemble_ok(const nx_network* h) { return batch_ok(h) && h->tree_exact && h->n_cyc == 0; }
 
+// The observed rows of a gradient / Hessian-vector call: in range and distinct.
+int batch_obs_rows_check(int64_t n, int32_t n_obs, const int32_t* obs_rows) {
+  std::vector<char> seen((size_t)n, 0);
+  for (int i = 0; i < n_obs; ++i) {
+    const int64_t r = obs_rows[i];
+    if (r < 0 || r >= n) return fail(NX_ERR_ARG, "an observed row is out of range");
+    if (seen[(size_t)r]) return fail(NX_ERR_ARG, "the observed rows must be distinct");
+    seen[(size_t)r] = 1;
+  }
+  return NX_OK;
+}
+
+// The observation list on the device: rows (ints, padded to doubles) | w | the chunk's data.
+struct ObsDev {
+  int* rows;
+  double *w, *d;
+};
+int batch_obs_upload(nx_network* h, int32_t n_obs, int chunk, const int32_t* obs_rows,
+                     const double* obs_w, ObsDev* od) {
+  const size_t row_d = ((size_t)n_obs + 1) / 2;
+  const size_t need = 8 * (row_d + (size_t)n_obs + (size_t)n_obs * (size_t)chunk);
+  if (need > h->gobs_bytes) {
+    HIPCALL(hipStreamSynchronize(h->stream));
+    if (h->gobs) (void)hipFree(h->gobs);
+    h->gobs = nullptr;
+    h->gobs_bytes = 0;
+    HIPCALL(hipMalloc(&h->gobs, need));
+    h->gobs_bytes = need;
+  }
+  od->rows = static_cast<int*>(h->gobs);
+  od->w = static_cast<double*>(h->gobs) + row_d;
+  od->d = od->w + n_obs;
+  HIPCALL(hipMemcpyAsync(od->rows, obs_rows, sizeof(int) * n_obs, hipMemcpyHostToDevice,
+                         h->stream));
+  HIPCALL(hipMemcpyAsync(od->w, obs_w, sizeof(double) * n_obs, hipMemcpyHostToDevice, h->stream));
+  return NX_OK;
+}
+
 // nx_batch_gradient (edge_R null: every scenario against the handle's matrix) and
 // nx_ensemble_gradient (edge_R: n_cols x E, every scenario against its own matrix; the adjoint
 // column is then per scenario for both kinds, and grad_R null means the objective alone).
@@ -13637,15 +13997,7 @@ int batch_gradient_run(nx_network* h, int32_t n_cols, const double* edge_R, cons
   const int64_t n = h->n_own, E = h->E;
   if (ens && ensemble_R_bad(edge_R, (int64_t)n_cols * E))
     return fail(NX_ERR_ARG, "nx_ensemble_gradient: R must be finite and positive");
-  {
-    std::vector<char> seen((size_t)n, 0);
-    for (int i = 0; i < n_obs; ++i) {
-      const int64_t r = obs_rows[i];
-      if (r < 0 || r >= n) return fail(NX_ERR_ARG, "an observed row is out of range");
-      if (seen[(size_t)r]) return fail(NX_ERR_ARG, "the observed rows must be distinct");
-      seen[(size_t)r] = 1;
-    }
-  }
+  CHECK(batch_obs_rows_check(n, n_obs, obs_rows));
   CHECK(set_device(h));
   h->b_refined = h->b_fallback = 0;
   h->b_launches = made_current + (!ens && h->dq_stale ? 1 : 0);
@@ -13656,22 +14008,10 @@ int batch_gradient_run(nx_network* h, int32_t n_cols, const double* edge_R, cons
   const BatchEns be = batch_ens(h, ws);
   const BatchEns* ep = ens ? &be : nullptr;
   if (!ens) CHECK(batch_make_current(h, ws));  // (an ensemble reads no dq of the handle's)
-  // the observation list on the device: rows (ints, padded to doubles) | w | the chunk's data
-  const size_t row_d = ((size_t)n_obs + 1) / 2;
-  const size_t need = 8 * (row_d + (size_t)n_obs + (size_t)n_obs * (size_t)chunk);
-  if (need > h->gobs_bytes) {
-    HIPCALL(hipStreamSynchronize(h->stream));
-    if (h->gobs) (void)hipFree(h->gobs);
-    h->gobs = nullptr;
-    h->gobs_bytes = 0;
-    HIPCALL(hipMalloc(&h->gobs, need));
-    h->gobs_bytes = need;
-  }
-  int* d_rows = static_cast<int*>(h->gobs);
-  double* d_w = static_cast<double*>(h->gobs) + row_d;
-  double* d_d = d_w + n_obs;
-  HIPCALL(hipMemcpyAsync(d_rows, obs_rows, sizeof(int) * n_obs, hipMemcpyHostToDevice, h->stream));
-  HIPCALL(hipMemcpyAsync(d_w, obs_w, sizeof(double) * n_obs, hipMemcpyHostToDevice, h->stream));
+  ObsDev od{};
+  CHECK(batch_obs_upload(h, n_obs, chunk, obs_rows, obs_w, &od));
+  int* d_rows = od.rows;
+  double *d_w = od.w, *d_d = od.d;
   const int64_t ld = ws.cols.ld;
   const int slices = grid_of(n, kObsSpan);
   std::vector<double> stats;
@@ -13739,6 +14079,214 @@ int batch_gradient_run(nx_network* h, int32_t n_cols, const double* edge_R, cons
     if (grad_bc)
       HIPCALL(hipMemcpyAsync(grad_bc + (int64_t)c0 * 2 * E, ws.gbc, sizeof(double) * 2 * E * nc,
                              hipMemcpyDeviceToHost, h->stream));
+    HIPCALL(hipStreamSynchronize(h->stream));
+  }
+  return NX_OK;
+}
+
+// The direction's right-hand side into ws.B: k_b_rhs on (dir_bc, dir_f), a missing part zero
+// (never the handle's source), through ws.bc / ws.ef, which the forward rhs no longer needs.
+int batch_dir_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const double* dir_bc,
+                        const double* dir_f) {
+  const int64_t E = h->E;
+  if (dir_bc)
+    HIPCALL(hipMemcpyAsync(ws.bc, dir_bc + (int64_t)c0 * 2 * E, sizeof(double) * 2 * E * nc,
+                           hipMemcpyHostToDevice, h->stream));
+  else
+    HIPCALL(hipMemsetAsync(ws.bc, 0, sizeof(double) * 2 * E * nc, h->stream));
+  if (dir_f)
+    HIPCALL(hipMemcpyAsync(ws.ef, dir_f + (int64_t)c0 * E, sizeof(double) * E * nc,
+                           hipMemcpyHostToDevice, h->stream));
+  else
+    HIPCALL(hipMemsetAsync(ws.ef, 0, sizeof(double) * E * nc, h->stream));
+  const int64_t nthr = E * (int64_t)(h->N + 1) + h->B;
+  const EdgeArgs ea{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N};
+  hipLaunchKernelGGL(k_b_rhs, dim3(grid_of(nthr, kBlock)), dim3(kBlock), 0, h->stream, ea, h->B,
+                     nc, ws.bc, ws.ef, E, ws.fc, ws.B, ws.cols.ld);
+  HIPCALL(hipGetLastError());
+  h->b_launches += 1;
+  return NX_OK;
+}
+
+// Y -= (sum_e v_R[e] dA/dR_e) Z on nc columns (k_b_mass_apply*, one launch).
+int batch_mass_apply(nx_network* h, const BatchWs& ws, int nc, const double* Z, int64_t z_ld,
+                     double* Y) {
+  const int64_t E = h->E;
+  const MassArgs ma{EdgeArgs{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N}, Z, z_ld, ws.vR, Y,
+                    ws.cols.ld};
+  constexpr int wpb = kBlock / 64;
+  if (h->N < 16)
+    hipLaunchKernelGGL(k_b_mass_apply_seg<16>, dim3(grid_of(E, wpb * 4), nc), dim3(kBlock), 0,
+                       h->stream, ma);
+  else if (h->N < 32)
+    hipLaunchKernelGGL(k_b_mass_apply_seg<32>, dim3(grid_of(E, wpb * 2), nc), dim3(kBlock), 0,
+                       h->stream, ma);
+  else
+    hipLaunchKernelGGL(k_b_mass_apply, dim3(grid_of(E, wpb), nc), dim3(kBlock), 0, h->stream, ma);
+  HIPCALL(hipGetLastError());
+  h->b_launches += 1;
+  return NX_OK;
+}
+
+int batch_edge_form2(nx_network* h, const BatchWs& ws, int nc, const double* L, int64_t l_ld) {
+  const int64_t E = h->E;
+  const Form2Args fa{EdgeArgs{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N}, ws.X, ws.Xd, L,
+                     ws.Ld, ws.cols.ld, l_ld, ws.gR, ws.gf, ws.gbc, ws.HR, ws.Hf, ws.Hbc};
+  constexpr int wpb = kBlock / 64;
+  if (h->N < 16)
+    hipLaunchKernelGGL(k_b_edge_form2_seg<16>, dim3(grid_of(E, wpb * 4), nc), dim3(kBlock), 0,
+                       h->stream, fa);
+  else if (h->N < 32)
+    hipLaunchKernelGGL(k_b_edge_form2_seg<32>, dim3(grid_of(E, wpb * 2), nc), dim3(kBlock), 0,
+                       h->stream, fa);
+  else
+    hipLaunchKernelGGL(k_b_edge_form2, dim3(grid_of(E, wpb), nc), dim3(kBlock), 0, h->stream, fa);
+  HIPCALL(hipGetLastError());
+  h->b_launches += 1;
+  return NX_OK;
+}
+
+// nx_batch_hvp (edge_R null) and nx_ensemble_hvp (edge_R: every scenario against its own
+// matrix; dA/dR_e does not depend on R, so the direction's kernels are the same). Per chunk:
+// the forward solve, the adjoint (full mode), the tangent A xd = bd - Ad x, the second-order
+// adjoint A ld = cd - Ad l (Gauss-Newton: A ld = W xd), then every output in one contraction
+// (k_b_edge_form2). The linear objective against the handle's matrix keeps nx_batch_gradient's
+// one adjoint column per call. Status arrays: 4 x n_cols (forward, adjoint, tangent, second
+// adjoint); Gauss-Newton leaves the adjoint quarter as it was.
+int batch_hvp_run(nx_network* h, int32_t n_cols, const double* edge_R, const double* edge_bc,
+                  const double* edge_f, const double* f_const, double rtol, int32_t kind,
+                  int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
+                  const double* obs_d, const double* dir_R, const double* dir_bc,
+                  const double* dir_f, int32_t gauss_newton, double* value, double* grad_R,
+                  double* grad_bc, double* grad_f, double* hess_R, double* hess_bc,
+                  double* hess_f, int32_t* iters, double* relres, int32_t* converged) {
+  const bool ens = edge_R != nullptr;
+  const bool gn = gauss_newton != 0;
+  const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (n_cols < 1) return fail(NX_ERR_ARG, "n_cols must be >= 1");
+  if (!edge_bc || !value || !hess_R) return fail(NX_ERR_ARG, "edge_bc / value / hess_R is NULL");
+  if (n_obs < 1 || !obs_rows || !obs_w) return fail(NX_ERR_ARG, "at least one observed row");
+  if (kind != 0 && kind != 1) return fail(NX_ERR_ARG, "kind: 0 linear, 1 least squares");
+  if (kind == 1 && !obs_d) return fail(NX_ERR_ARG, "the least-squares objective needs obs_d");
+  if (!dir_R && !dir_bc && !dir_f)
+    return fail(NX_ERR_ARG, "a direction is needed: dir_R, dir_bc or dir_f");
+  if (gauss_newton != 0 && gauss_newton != 1) return fail(NX_ERR_ARG, "gauss_newton: 0 or 1");
+  if (gn && kind == 0)
+    return fail(NX_ERR_ARG, "the Gauss-Newton product needs the least-squares objective");
+  if (ens ? !ensemble_ok(h) : !batch_ok(h))
+    return fail(NX_ERR_STATE, ens ? "nx_ensemble_hvp: the batched ensemble does not apply to this "
+                                    "handle (nx_ensemble_supported)"
+                                  : "nx_batch_hvp: the batched direct solve does not apply to "
+                                    "this handle (nx_batch_supported)");
+  if (!h->have_lhs)
+    return fail(NX_ERR_STATE, ens ? "assemble the matrix before nx_ensemble_hvp"
+                                  : "assemble the matrix before nx_batch_hvp");
+  const int64_t n = h->n_own, E = h->E;
+  if (ens && ensemble_R_bad(edge_R, (int64_t)n_cols * E))
+    return fail(NX_ERR_ARG, "nx_ensemble_hvp: R must be finite and positive");
+  CHECK(batch_obs_rows_check(n, n_obs, obs_rows));
+  CHECK(set_device(h));
+  h->b_refined = h->b_fallback = 0;
+  h->b_launches = made_current + (!ens && h->dq_stale ? 1 : 0);
+  int chunk = 0;
+  CHECK(batch_workspace(h, n_cols, &chunk, true, ens, true));
+  h->b_chunk = chunk;
+  const BatchWs ws = batch_carve(h, h->bws_cap);
+  const BatchEns be = batch_ens(h, ws);
+  const BatchEns* ep = ens ? &be : nullptr;
+  if (!ens) CHECK(batch_make_current(h, ws));  // (an ensemble reads no dq of the handle's)
+  ObsDev od{};
+  CHECK(batch_obs_upload(h, n_obs, chunk, obs_rows, obs_w, &od));
+  const int64_t ld = ws.cols.ld;
+  const int slices = grid_of(n, kObsSpan);
+  std::vector<double> stats;
+  int32_t a_it = 1, a_cv = 1;
+  double a_rr = 0.0;
+  const bool one_adj = kind == 0 && !ens;  // (kind 0 is never Gauss-Newton)
+  if (one_adj) {  // the same adjoint column for every scenario: solved once per call
+    hipLaunchKernelGGL(k_b_obs, dim3(slices, 1), dim3(kObsThreads), 0, h->stream, nullptr, ld, n,
+                       0, n_obs, od.rows, od.w, nullptr, ws.C, nullptr);
+    HIPCALL(hipGetLastError());
+    h->b_launches += 1;
+    CHECK(batch_solve_cols(h, ws, 1, ws.C, ws.L, rtol, &a_it, &a_rr, &a_cv, stats));
+    CHECK(batch_zero_cols(h, ws.L, ld, 1, stats));
+  }
+  auto quarter = [&](int q, int c0, int32_t** it, double** rr, int32_t** cv) {
+    *it = iters ? iters + (int64_t)q * n_cols + c0 : nullptr;
+    *rr = relres ? relres + (int64_t)q * n_cols + c0 : nullptr;
+    *cv = converged ? converged + (int64_t)q * n_cols + c0 : nullptr;
+  };
+  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
+    const int nc = std::min(chunk, n_cols - c0);
+    int32_t *q_it, *q_cv;
+    double* q_rr;
+    // forward: A x = b
+    CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const, edge_R));
+    quarter(0, c0, &q_it, &q_rr, &q_cv);
+    CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.X, rtol, q_it, q_rr, q_cv, stats, ep));
+    CHECK(batch_zero_cols(h, ws.X, ld, nc, stats));  // b = 0: x = 0 exactly
+    if (kind == 1)
+      HIPCALL(hipMemcpyAsync(od.d, obs_d + (int64_t)c0 * n_obs, sizeof(double) * n_obs * nc,
+                             hipMemcpyHostToDevice, h->stream));
+    // adjoint: A l = c(x), and the objective
+    quarter(1, c0, &q_it, &q_rr, &q_cv);
+    if (gn || one_adj) {  // the objective alone
+      hipLaunchKernelGGL(k_b_obs, dim3(1, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n, kind,
+                         n_obs, od.rows, od.w, kind ? od.d : nullptr, nullptr, ws.gJ);
+      HIPCALL(hipGetLastError());
+      h->b_launches += 1;
+      if (one_adj)
+        for (int c = 0; c < nc; ++c) {
+          if (q_it) q_it[c] = a_it;
+          if (q_rr) q_rr[c] = a_rr;
+          if (q_cv) q_cv[c] = a_cv;
+        }
+    } else {
+      hipLaunchKernelGGL(k_b_obs, dim3(slices, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n,
+                         kind, n_obs, od.rows, od.w, kind ? od.d : nullptr, ws.C, ws.gJ);
+      HIPCALL(hipGetLastError());
+      h->b_launches += 1;
+      CHECK(batch_solve_cols(h, ws, nc, ws.C, ws.L, rtol, q_it, q_rr, q_cv, stats, ep));
+      CHECK(batch_zero_cols(h, ws.L, ld, nc, stats));
+    }
+    // tangent: A xd = bd - Ad x (ws.B, ws.bc, ws.ef are free: the forward solve is done)
+    if (dir_R)
+      HIPCALL(hipMemcpyAsync(ws.vR, dir_R + (int64_t)c0 * E, sizeof(double) * E * nc,
+                             hipMemcpyHostToDevice, h->stream));
+    else
+      HIPCALL(hipMemsetAsync(ws.vR, 0, sizeof(double) * E * nc, h->stream));
+    CHECK(batch_dir_rhs_chunk(h, ws, c0, nc, dir_bc, dir_f));
+    CHECK(batch_mass_apply(h, ws, nc, ws.X, ld, ws.B));
+    quarter(2, c0, &q_it, &q_rr, &q_cv);
+    CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.Xd, rtol, q_it, q_rr, q_cv, stats, ep));
+    CHECK(batch_zero_cols(h, ws.Xd, ld, nc, stats));
+    // second-order adjoint: A ld = cd - Ad l (ws.C is free: the adjoint solve is done)
+    hipLaunchKernelGGL(k_b_obs_dir, dim3(slices, nc), dim3(kObsThreads), 0, h->stream, ws.Xd, ld,
+                       n, kind, n_obs, od.rows, od.w, ws.C);
+    HIPCALL(hipGetLastError());
+    h->b_launches += 1;
+    if (!gn) CHECK(batch_mass_apply(h, ws, nc, ws.L, one_adj ? 0 : ld, ws.C));
+    quarter(3, c0, &q_it, &q_rr, &q_cv);
+    CHECK(batch_solve_cols(h, ws, nc, ws.C, ws.Ld, rtol, q_it, q_rr, q_cv, stats, ep));
+    CHECK(batch_zero_cols(h, ws.Ld, ld, nc, stats));
+    CHECK(batch_edge_form2(h, ws, nc, gn ? nullptr : ws.L, one_adj ? 0 : ld));
+    // the chunk's outputs straight into the caller's arrays (no staging, no host unpack)
+    auto out = [&](double* dst, const double* src, int64_t per) {
+      return dst ? hipMemcpyAsync(dst + (int64_t)c0 * per, src, sizeof(double) * per * nc,
+                                  hipMemcpyDeviceToHost, h->stream)
+                 : hipSuccess;
+    };
+    HIPCALL(out(value, ws.gJ, 1));
+    HIPCALL(out(hess_R, ws.HR, E));
+    HIPCALL(out(hess_f, ws.Hf, E));
+    HIPCALL(out(hess_bc, ws.Hbc, 2 * E));
+    if (!gn) {
+      HIPCALL(out(grad_R, ws.gR, E));
+      HIPCALL(out(grad_f, ws.gf, E));
+      HIPCALL(out(grad_bc, ws.gbc, 2 * E));
+    }
     HIPCALL(hipStreamSynchronize(h->stream));
   }
   return NX_OK;
@@ -13850,6 +14398,32 @@ NX_API int nx_ensemble_gradient(nx_network_t* h, int32_t n_cols, const double* e
   return batch_gradient_run(h, n_cols, edge_R, edge_bc, edge_f, f_const, rtol, kind, n_obs,
                             obs_rows, obs_w, obs_d, value, grad_R, grad_bc, grad_f, iters, relres,
                             converged);
+}
+
+NX_API int nx_batch_hvp(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                        const double* edge_f, const double* f_const, double rtol, int32_t kind,
+                        int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
+                        const double* obs_d, const double* dir_R, const double* dir_bc,
+                        const double* dir_f, int32_t gauss_newton, double* value, double* grad_R,
+                        double* grad_bc, double* grad_f, double* hess_R, double* hess_bc,
+                        double* hess_f, int32_t* iters, double* relres, int32_t* converged) {
+  return batch_hvp_run(h, n_cols, nullptr, edge_bc, edge_f, f_const, rtol, kind, n_obs, obs_rows,
+                       obs_w, obs_d, dir_R, dir_bc, dir_f, gauss_newton, value, grad_R, grad_bc,
+                       grad_f, hess_R, hess_bc, hess_f, iters, relres, converged);
+}
+
+NX_API int nx_ensemble_hvp(nx_network_t* h, int32_t n_cols, const double* edge_R,
+                           const double* edge_bc, const double* edge_f, const double* f_const,
+                           double rtol, int32_t kind, int32_t n_obs, const int32_t* obs_rows,
+                           const double* obs_w, const double* obs_d, const double* dir_R,
+                           const double* dir_bc, const double* dir_f, int32_t gauss_newton,
+                           double* value, double* grad_R, double* grad_bc, double* grad_f,
+                           double* hess_R, double* hess_bc, double* hess_f, int32_t* iters,
+                           double* relres, int32_t* converged) {
+  if (!edge_R) return fail(NX_ERR_ARG, "edge_R is NULL");
+  return batch_hvp_run(h, n_cols, edge_R, edge_bc, edge_f, f_const, rtol, kind, n_obs, obs_rows,
+                       obs_w, obs_d, dir_R, dir_bc, dir_f, gauss_newton, value, grad_R, grad_bc,
+                       grad_f, hess_R, hess_bc, hess_f, iters, relres, converged);
 }
 
 NX_API int nx_get_solution(nx_network_t* h, double* xo) {

@@ -50,7 +50,7 @@ from . import _lib
 from .assembly import DeviceMatrix, DeviceVector, HydraulicNetworkAssembler
 from .timing import timed
 
-__all__ = ["Solver", "KSPInfo", "BatchResult", "GradientResult"]
+__all__ = ["Solver", "KSPInfo", "BatchResult", "GradientResult", "HessianVectorResult"]
 
 _DEFAULTS = {
     "ksp_type": "preonly",
@@ -143,6 +143,36 @@ class GradientResult:
         self.dR = dR
         self.df = df
         self.dp_bc = dp_bc
+        self.iterations = np.asarray(iterations)
+        self.residual_norms = np.asarray(residual_norms)
+        self.converged = np.asarray(converged, dtype=bool)
+        self.info = dict(info)
+
+    def __len__(self) -> int:
+        return self.value.shape[0]
+
+
+class HessianVectorResult:
+    """What :meth:`Solver.hessian_vector` returns: per scenario the objective, its gradient
+    and the product of its Hessian with the scenario's direction.
+
+    ``value``, ``dR``, ``df``, ``dp_bc``: as :class:`GradientResult` (the three derivatives are
+    None in Gauss-Newton mode); ``HdR``, ``Hdf``: ``(B, num_edges)`` in ``graph.edges()`` order
+    and ``Hdp_bc``: ``(B, num_nodes)``, zero off the boundary nodes -- the blocks of ``H v``
+    belonging to ``R``, ``f`` and the nodal boundary pressure; ``iterations``,
+    ``residual_norms``, ``converged``: ``(B, 4)`` each -- the forward, adjoint, tangent and
+    second-order adjoint solve -- or ``(B, 3)`` in Gauss-Newton mode (no adjoint); ``info``: the
+    dict of ``nx_get_batch_info``."""
+
+    def __init__(self, value, dR, df, dp_bc, HdR, Hdf, Hdp_bc, iterations, residual_norms,
+                 converged, info):
+        self.value = value
+        self.dR = dR
+        self.df = df
+        self.dp_bc = dp_bc
+        self.HdR = HdR
+        self.Hdf = Hdf
+        self.Hdp_bc = Hdp_bc
         self.iterations = np.asarray(iterations)
         self.residual_norms = np.asarray(residual_norms)
         self.converged = np.asarray(converged, dtype=bool)
@@ -445,19 +475,7 @@ class Solver:
             raise RuntimeError("compute_forms() must be called before gradient()")
         if R is None and not derivatives:
             raise NotImplementedError("derivatives=False needs R (the ensemble call)")
-        if getattr(asm, "_nranks", 1) > 1:
-            raise NotImplementedError("gradient runs on one rank")
-        if tuple(asm.degrees) != (1, 0):
-            raise NotImplementedError(
-                f"gradient needs the P1/DG0 discretisation, not degrees {tuple(asm.degrees)}")
-        if not self._direct:
-            raise NotImplementedError("gradient needs the direct solve (ksp_type='preonly'), "
-                                      "not MINRES")
-        if not self._pc:
-            raise NotImplementedError("gradient needs the tree decomposition (pc_type != 'none')")
-        if not self._pc_exact:
-            raise NotImplementedError("gradient needs the consistent mass (pc_mass='lumped' "
-                                      "is not exact)")
+        self._adjoint_supported("gradient")
         if R is None:
             edge_R = None
             edge_bc, edge_f, f_const = asm.scenario_coefficients(p_bc, f)
@@ -465,33 +483,9 @@ class Solver:
             edge_R, edge_bc, edge_f, f_const = asm.ensemble_coefficients(R, p_bc, f)
         B = edge_bc.shape[0]
         h = asm.handle
-        rows = np.asarray(rows)
-        if rows.ndim != 1 or rows.size < 1 or not np.issubdtype(rows.dtype, np.integer):
-            raise ValueError("rows must be a 1-D array of at least one integer index")
-        if rows.min() < 0 or rows.max() >= h.n_rows:
-            raise ValueError(f"rows must lie in [0, {h.n_rows})")
-        if np.unique(rows).size != rows.size:
-            raise ValueError("rows must be distinct")
-        w = np.ones(rows.size) if weights is None else np.asarray(weights, dtype=np.float64)
-        if w.shape != (rows.size,):
-            raise ValueError("weights must have one value per observed row")
-        if data is not None:
-            data = np.asarray(data, dtype=np.float64)
-            if data.shape == (rows.size,):
-                data = np.broadcast_to(data, (B, rows.size))
-            if data.shape != (B, rows.size):
-                raise ValueError(f"data must be ({B}, {rows.size}) or ({rows.size},)")
-        self._configure()
-        if not asm.lhs_current:  # the matrix of the last compute_forms (its R), values only
-            asm.assemble(assemble_lhs=True, assemble_rhs=False)
-        if not h.batch_supported():
-            raise NotImplementedError("gradient: the batched direct solve does not apply to this "
-                                      "handle (nx_batch_supported)")
-        dev_rows = asm.block_order_rows()[rows]
+        rows, w, data = self._observations(rows, weights, data, B)
+        dev_rows = self._adjoint_ready("gradient", rows, edge_R is not None)
         if edge_R is not None:
-            if not h.ensemble_supported():
-                raise NotImplementedError("gradient(R=...): the batched ensemble does not apply "
-                                          "to this handle (nx_ensemble_supported)")
             value, gR, gbc, gf, it, rr, conv = h.ensemble_gradient(
                 edge_R, edge_bc, edge_f, f_const, self._rtol, rows=dev_rows, weights=w,
                 data=data, derivatives=derivatives)
@@ -518,6 +512,126 @@ class Solver:
             bad = np.flatnonzero(~conv.all(axis=1))
             raise _lib.NxNotConverged(
                 f"gradient: columns {bad.tolist()} did not converge (relative residuals "
+                f"{rr[bad].tolist()} > rtol {self._rtol:.1e})")
+        return res
+
+    def _adjoint_supported(self, what: str) -> None:
+        """The options under which :meth:`gradient` and :meth:`hessian_vector` run."""
+        asm = self.assembler
+        if getattr(asm, "_nranks", 1) > 1:
+            raise NotImplementedError(f"{what} runs on one rank")
+        if tuple(asm.degrees) != (1, 0):
+            raise NotImplementedError(
+                f"{what} needs the P1/DG0 discretisation, not degrees {tuple(asm.degrees)}")
+        if not self._direct:
+            raise NotImplementedError(f"{what} needs the direct solve (ksp_type='preonly'), "
+                                      "not MINRES")
+        if not self._pc:
+            raise NotImplementedError(f"{what} needs the tree decomposition (pc_type != 'none')")
+        if not self._pc_exact:
+            raise NotImplementedError(f"{what} needs the consistent mass (pc_mass='lumped' "
+                                      "is not exact)")
+
+    def _observations(self, rows, weights, data, B: int):
+        """The observed rows, weights and data of B scenarios, checked and normalised."""
+        n = self.assembler.handle.n_rows
+        rows = np.asarray(rows)
+        if rows.ndim != 1 or rows.size < 1 or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError("rows must be a 1-D array of at least one integer index")
+        if rows.min() < 0 or rows.max() >= n:
+            raise ValueError(f"rows must lie in [0, {n})")
+        if np.unique(rows).size != rows.size:
+            raise ValueError("rows must be distinct")
+        w = np.ones(rows.size) if weights is None else np.asarray(weights, dtype=np.float64)
+        if w.shape != (rows.size,):
+            raise ValueError("weights must have one value per observed row")
+        if data is not None:
+            data = np.asarray(data, dtype=np.float64)
+            if data.shape == (rows.size,):
+                data = np.broadcast_to(data, (B, rows.size))
+            if data.shape != (B, rows.size):
+                raise ValueError(f"data must be ({B}, {rows.size}) or ({rows.size},)")
+        return rows, w, data
+
+    def _adjoint_ready(self, what: str, rows, ensemble: bool) -> np.ndarray:
+        """The handle configured, its matrix current and the batched path checked; returns the
+        observed rows as device rows."""
+        asm = self.assembler
+        h = asm.handle
+        self._configure()
+        if not asm.lhs_current:  # the matrix of the last compute_forms (its R), values only
+            asm.assemble(assemble_lhs=True, assemble_rhs=False)
+        if not h.batch_supported():
+            raise NotImplementedError(f"{what}: the batched direct solve does not apply to this "
+                                      "handle (nx_batch_supported)")
+        if ensemble and not h.ensemble_supported():
+            raise NotImplementedError(f"{what}(R=...): the batched ensemble does not apply "
+                                      "to this handle (nx_ensemble_supported)")
+        return asm.block_order_rows()[rows]
+
+    @timed("nxfx:Solver:hessian_vector")
+    def hessian_vector(self, p_bc, f=None, *, rows, weights=None, data=None, v_R=None,
+                       v_p_bc=None, v_f=None, R=None,
+                       gauss_newton: bool = False) -> "HessianVectorResult":
+        """Exact Hessian-vector products of :meth:`gradient`'s objective for B scenarios
+        (``nx_batch_hvp``: four batched direct solves -- forward, adjoint, tangent and
+        second-order adjoint -- and one contraction; no solution leaves the device).
+
+        ``p_bc`` / ``f`` / ``rows`` / ``weights`` / ``data`` / ``R``: as for :meth:`gradient`.
+        The direction of scenario j is ``(v_R[j], v_p_bc[j], v_f[j])``: ``v_R`` ``(B,
+        num_edges)`` or ``(num_edges,)`` in ``graph.edges()`` order (any sign), ``v_p_bc`` nodal
+        ``(B, num_nodes)`` or ``(num_nodes,)``, ``v_f`` ``(B, num_edges)``, ``(num_edges,)`` or
+        ``(B,)`` constants; a part left None is zero
+        (:func:`~networks_fenicsx_amd.assembly.hvp_directions`), all three None a
+        ``ValueError``. Returns a :class:`HessianVectorResult`: ``H v`` in the three blocks
+        ``HdR``, ``Hdf``, ``Hdp_bc`` and, from the same pass, the objective and the gradient
+        with :meth:`gradient`'s bits.
+
+        ``gauss_newton=True`` (least squares only: ``data`` None raises ``ValueError``): the
+        product with the positive semidefinite ``J^T W J`` of the observed values' Jacobian --
+        three solves, no adjoint, no gradient (``dR``, ``df``, ``dp_bc`` None).
+
+        It runs where :meth:`gradient` runs and raises ``NotImplementedError`` elsewhere; with
+        ``R`` on a forest only (``nx_ensemble_hvp``). The reference has no counterpart."""
+        if self._closed:
+            raise RuntimeError("the solver has been destroyed")
+        asm = self.assembler
+        if getattr(asm, "_coefficients", None) is None:
+            raise RuntimeError("compute_forms() must be called before hessian_vector()")
+        if gauss_newton and data is None:
+            raise ValueError("gauss_newton=True needs the least-squares objective (data)")
+        if v_R is None and v_p_bc is None and v_f is None:
+            raise ValueError("a direction is needed: v_R, v_p_bc or v_f")
+        self._adjoint_supported("hessian_vector")
+        if R is None:
+            edge_R = None
+            edge_bc, edge_f, f_const = asm.scenario_coefficients(p_bc, f)
+        else:
+            edge_R, edge_bc, edge_f, f_const = asm.ensemble_coefficients(R, p_bc, f)
+        B = edge_bc.shape[0]
+        h = asm.handle
+        dir_R, dir_bc, dir_f = asm.hvp_directions(B, v_R, v_p_bc, v_f)
+        rows, w, data = self._observations(rows, weights, data, B)
+        dev_rows = self._adjoint_ready("hessian_vector", rows, edge_R is not None)
+        value, gR, gbc, gf, hR, hbc, hf, it, rr, conv = h.batch_hvp(
+            edge_bc, edge_f, f_const, self._rtol, rows=dev_rows, weights=w, data=data,
+            dir_R=dir_R, dir_bc=dir_bc, dir_f=dir_f, edge_R=edge_R, gauss_newton=gauss_newton)
+        # the gathers of gradient(): edge slots -> graph.edges() order, flux end rows -> nodes
+        # (every output is copied out of the handle's page-locked buffer)
+        slot, node_idx, node_sign = asm.gradient_maps()
+
+        def edges(a):
+            return None if a is None else np.take(a, slot, axis=1)
+
+        def nodes(a):
+            return None if a is None else np.take(a.reshape(B, -1), node_idx, axis=1) * node_sign
+
+        res = HessianVectorResult(value.copy(), edges(gR), edges(gf), nodes(gbc), edges(hR),
+                                  edges(hf), nodes(hbc), it, rr, conv, h.batch_info())
+        if self._raise and not conv.all():
+            bad = np.flatnonzero(~conv.all(axis=1))
+            raise _lib.NxNotConverged(
+                f"hessian_vector: columns {bad.tolist()} did not converge (relative residuals "
                 f"{rr[bad].tolist()} > rtol {self._rtol:.1e})")
         return res
 
