@@ -16,6 +16,7 @@ from networks_fenicsx_amd.layout import build_local_problem
 from networks_fenicsx_amd.precond import build_tree_preconditioner
 from oracle import nx_cpu
 from oracle import nx_oracle as O
+from tree_shapes import block_errors
 
 
 def _setup(G, N, strategy, pbc):
@@ -77,6 +78,8 @@ def test_cpu_direct_matches_oracle(case):
     assert passes in (1, 2) and rr <= 1e-12, (passes, rr)
     x_ref = O.solve_reference(A, b)[perm]
     assert np.linalg.norm(st.x - x_ref) / np.linalg.norm(x_ref) <= 1e-10
+    # fluxes, pressures and multipliers each: the pressures carry the norm of x on these graphs
+    assert max(block_errors(st.x, x_ref, m.num_edges, N)) <= 1e-10
 
 
 def test_cpu_direct_medium_tree_analytic():

@@ -16,6 +16,7 @@ from cases import CASES
 from networks_fenicsx_amd import HydraulicNetworkAssembler, NetworkMesh, Solver
 from networks_fenicsx_amd import network_generation as ng
 from oracle import nx_oracle as O
+from tree_shapes import block_errors_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -45,6 +46,8 @@ def test_direct_solve_matches_oracle(case):
     x_ref = O.solve_reference(A, b)
     got = np.concatenate([f.x.array for f in sol])  # the reference's block order
     assert np.linalg.norm(got - x_ref) / np.linalg.norm(x_ref) <= SOL_TOL
+    # fluxes, pressures and multipliers each: the pressures carry the norm of x on these graphs
+    assert max(block_errors_oracle(got, x_ref, P.p_offset, P.lm_offset)) <= SOL_TOL
     xa = O.resistor_network_solution(P, pbc)
     assert np.linalg.norm(got - xa) / np.linalg.norm(xa) <= SOL_TOL
     assert solver.true_residual() <= 1e-12

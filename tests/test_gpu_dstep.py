@@ -17,6 +17,7 @@ from cases import CASES
 from networks_fenicsx_amd import HydraulicNetworkAssembler, NetworkMesh
 from networks_fenicsx_amd import network_generation as ng
 from oracle import nx_oracle as O
+from tree_shapes import block_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -54,6 +55,8 @@ def test_dstep_matches_oracle_and_launches(case, monkeypatch):
     np.testing.assert_array_equal(h.rhs(), bb)
     x_ref = O.solve_reference(A, b)[perm]
     assert np.linalg.norm(x1 - x_ref) / np.linalg.norm(x_ref) <= SOL_TOL
+    # fluxes, pressures and multipliers each: the pressures carry the norm of x on these graphs
+    assert max(block_errors(x1, x_ref, mesh.num_edges, mesh.N)) <= SOL_TOL
     true1 = h.true_residual()
     assert abs(rr - true1) <= 0.05 * true1 + 5e-16, (rr, true1)
     # the separate launches: the same x to its rounding (same formulas; the compiler forms
