@@ -530,8 +530,8 @@ int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
  * nx_batch_solve's bits.
  *
  * nx_ensemble_supported: *ok = 1 where nx_batch_supported says 1 on a forest (tree_exact, no
- * cycle correction set: that correction is per matrix, 2 n_cyc solves per column); elsewhere
- * the two calls below return NX_ERR_STATE.
+ * cycle correction set: that correction is per matrix, 2 n_cyc solves per column -- a handle
+ * opts in with nx_set_ensemble_cycles, below); elsewhere the calls below return NX_ERR_STATE.
  *
  * nx_ensemble_solve: n_cols scenarios.
  *   edge_R    n_cols x E, finite and positive (as nx_set_coefficients' edge_R, per scenario)
@@ -561,6 +561,48 @@ int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
  * Launches per chunk with S = 5: 1 + S + 1 + S + 1 = 13 (both kinds), 1 + S + 1 = 7 for the
  * objective alone, 6 more for each refinement pass.
  *
+ * Graphs with cycles (nx_set_ensemble_cycles; off by default). The handle's cycle correction
+ * (nx_set_cycles: Z = A_g^{-1} U and Cinv) belongs to the resident R, so the reference's one LU
+ * per matrix (solver.py:58-65, after compute_forms + assemble, assembly.py:165-262, 329-368)
+ * becomes a correction per scenario in the solve-again form, with m = 2 n_cyc, U the unit
+ * columns of the cycle chains' rows and C the +-1 couplings the tree solve drops (they do not
+ * depend on R):
+ *   K_j = C^{-1} + U^T A_g(R_j)^{-1} U      (m x m, symmetric, indefinite)
+ *   x_g = A_g(R_j)^{-1} b,  w = K_j^{-1} U^T x_g,  x = A_g(R_j)^{-1} (b - U w)
+ * Z_j is never stored: per chunk of nc scenarios, right after the set-up kernel, the nc m unit
+ * right-hand sides go through the batched sweeps in passes of as many columns as the workspace
+ * holds (64 on such a handle, even for fewer scenarios; a pass may straddle scenarios, each
+ * column with its scenario's lumped mass), only the rows of U are kept as K_j, and one workgroup
+ * per scenario factorises K_j in place (LU, partial pivoting; in LDS while m^2 + m doubles fit a
+ * workgroup's 160 KiB less 1 KiB, m <= 142, else in global memory -- the same operations, the
+ * same bits). Every solve of the chunk -- 1 / 2 / 4 for nx_ensemble_solve / _gradient / _hvp,
+ * refinement passes included -- then runs sweeps, k_e_cyc_w (w, and b - U w patched into the m
+ * entries of the input column), sweeps, k_e_cyc_restore (the m entries put back bit for bit).
+ * The results agree with nx_batch_solve at the same R to rounding, not bit for bit: the
+ * solve-again form is a different sum from Z w. A zero coupling or a zero / non-finite pivot
+ * flags the scenario: its columns get no correction, hold finite values and are reported
+ * converged = 0. The workspace of a handle that has opted in carries m^2 + 2 m + 2 more
+ * doubles per column behind everything else. Nothing of the handle is read but its pattern,
+ * +-1 values and decomposition, and nothing written: no lumped mass, no cycle correction of
+ * the handle's is built.
+ *
+ * nx_set_ensemble_cycles: handle state, enable = 0 / 1 (NX_ERR_ARG otherwise, and for a NULL
+ * handle); it survives nx_set_preconditioner and nx_set_cycles. With 1, nx_ensemble_supported
+ * also says 1 where nx_batch_supported does on a handle with 0 < n_cyc <= 512.
+ * nx_get_ensemble_cycles: the flag, the last ensemble call's unit solves (n_cols m) and the
+ * factor kernel's storage in its last chunk (0 none, 1 LDS, 2 global memory; NXHIP_ENS_CYC_LDS=0,
+ * read per call, forces 2: a test hook). Any output may be NULL.
+ *
+ * Launches with cycles (nx_get_batch_info). With T the tree solve's launches (3: up, top, down;
+ * 1 on a decomposition without jobs), W the workspace's columns (64 unless memory is short) and
+ * per chunk of nc scenarios P = ceil(nc m / W):
+ *   build per chunk   P (1 (k_e_cyc_unit) + T + 1 (k_e_cyc_extract)) + 1 (k_e_cyc_factor) = 5 P + 1
+ *   per solve         T + 1 (k_e_cyc_w) + T + 1 (k_e_cyc_restore) + 2 (residual, norms): S = 10
+ *   per refinement    S + 1 (update) = 11 in the chunk that has one
+ * so nx_ensemble_solve takes 1 + (5 P + 1) + 10 + 1 (gather) = 5 P + 13 per chunk,
+ * nx_ensemble_gradient 1 + (5 P + 1) + 2 S + 2 = 5 P + 24 (5 P + 13 for the objective alone), and
+ * nx_ensemble_hvp 4 S + 7 + (5 P + 1) = 5 P + 48 (3 S + 6 + 5 P + 1 = 5 P + 37 with gauss_newton).
+ *
  * nx_stash_solution: for a caller that loops nx_set_coefficients / nx_assemble / nx_solve over
  * scenarios on a handle that cannot take the calls above, and wants the handle back as it was.
  * restore = 0 saves x, tmp, the rhs and the published state of the last solve (a pending
@@ -581,6 +623,9 @@ int nx_ensemble_gradient(nx_network_t* h, int32_t n_cols, const double* edge_R,
                          double* grad_bc, double* grad_f, int32_t* iters, double* relres,
                          int32_t* converged);
 int nx_stash_solution(nx_network_t* h, int32_t restore);
+int nx_set_ensemble_cycles(nx_network_t* h, int32_t enable);
+int nx_get_ensemble_cycles(nx_network_t* h, int32_t* enabled, int32_t* unit_solves,
+                           int32_t* storage);
 
 /*
  * Hessian-vector products of nx_batch_gradient's objective: per scenario j the product H_j v_j

@@ -63,6 +63,8 @@ _SIGS = {
     "nx_ensemble_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd,
                                        _pd, _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
     "nx_stash_solution": (C.c_int, [_h, _i32]),
+    "nx_set_ensemble_cycles": (C.c_int, [_h, _i32]),
+    "nx_get_ensemble_cycles": (C.c_int, [_h, _pi32, _pi32, _pi32]),
     "nx_batch_hvp": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd, _pd,
                                _pd, _pd, _pd, _i32, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _pi32,
                                _pd, _pi32]),
@@ -513,6 +515,21 @@ class Handle:
         ok = C.c_int32(0)
         check(lib().nx_ensemble_supported(self.ptr, C.byref(ok)))
         return bool(ok.value)
+
+    def set_ensemble_cycles(self, enable: bool) -> None:
+        """``nx_set_ensemble_cycles``: let the ensemble calls take this handle's graph with
+        cycles (a cycle correction per scenario, up to 512 cycle chains). Handle state, off by
+        default."""
+        check(lib().nx_set_ensemble_cycles(self.ptr, 1 if enable else 0))
+
+    def ensemble_cycles_info(self) -> dict:
+        """``nx_get_ensemble_cycles``: ``enabled``, the last ensemble call's ``unit_solves``
+        (``n_cols * 2 n_cyc``) and the factor kernel's ``storage`` (0 none, 1 LDS, 2 global
+        memory)."""
+        v = [C.c_int32(0) for _ in range(3)]
+        check(lib().nx_get_ensemble_cycles(self.ptr, *[C.byref(x) for x in v]))
+        return {"enabled": bool(v[0].value), "unit_solves": int(v[1].value),
+                "storage": int(v[2].value)}
 
     def _ensemble_R(self, edge_R, B: int) -> np.ndarray:
         eR = np.ascontiguousarray(edge_R, dtype=np.float64)

@@ -42,7 +42,7 @@
 
 namespace {
 
-constexpr int kVersion = 1 * 10000 + 1 * 100 + 0;  // 1.1: nx_create_fe, nx_set_source
+constexpr int kVersion = 1 * 10000 + 2 * 100 + 0;  // 1.2: nx_set_ensemble_cycles (1.1: nx_create_fe, nx_set_source)
 constexpr int kBlock = 256;         // threads per block (4 wave64)
 constexpr int kRowsPerBlock = 256;  // SpMV: one row per thread
 constexpr int kLdsCap = 2048;       // SpMV: products staged per block (16 KiB)
@@ -3578,6 +3578,9 @@ struct BatchCols {
   // R nowhere else), or null: the handle's
   const double* dq;
   int64_t n_dq;
+  // the unit solves of an ensemble's cycle correction: workspace column c takes the lumped
+  // mass of scenario dq_map[c] (several unit columns per scenario), or null: of column c
+  const int* dq_map;
 };
 
 __device__ __forceinline__ int batch_col(const BatchCols& bc, int i) {
@@ -3594,7 +3597,7 @@ __device__ __forceinline__ PcArgs batch_col_args(const PcArgs& pa, const BatchCo
   p.slot_A = bc.slot_A + col * bc.n_slot;
   p.slot_B = bc.slot_B + col * bc.n_slot;
   p.slot_z = bc.slot_z + col * bc.n_slot;
-  if (bc.dq) p.dq = bc.dq + col * bc.n_dq;
+  if (bc.dq) p.dq = bc.dq + (bc.dq_map ? bc.dq_map[col] : col) * bc.n_dq;
   return p;
 }
 
@@ -8493,6 +8496,14 @@ struct nx_network {
   // mass and R (kept once an ensemble call has asked for them)
   bool bws_ens = false;
   bool bws_hvp = false;  // nx_batch_hvp asked: the tangent / second adjoint columns, direction, outputs
+  // nx_set_ensemble_cycles: the ensemble calls take this handle's graph with cycles (a cycle
+  // correction per scenario); whether the workspace carries its part; the last ensemble call's
+  // unit solves and the factor kernel's storage (0 none, 1 LDS, 2 global memory); the current
+  // chunk's failed factorisations (host copy of the flags)
+  bool ens_cyc = false;
+  bool bws_ecyc = false;
+  int ecyc_unit = 0, ecyc_storage = 0;
+  std::vector<int> ecyc_failed;
   void* gobs = nullptr;
   size_t gobs_bytes = 0;
   // nx_stash_solution: x | tmp | rhs (3 n_col) and the published state (a BatchSaved, malloc'ed)
@@ -13384,6 +13395,215 @@ __global__ __launch_bounds__(kBlock) void k_b_cyc_fix(double* __restrict__ X, in
   X[col * ld + i] -= s;
 }
 
+// ---- ensembles on graphs with cycles (nx_set_ensemble_cycles). The handle's
+// Z and Cinv belong to the resident R, so every scenario j gets a correction of its own in the
+// solve-again form:
+//   K_j = C^{-1} + U^T A_g(R_j)^{-1} U          (m x m, symmetric, indefinite)
+//   x_g = A_g(R_j)^{-1} b,  w = K_j^{-1} U^T x_g,  x = A_g(R_j)^{-1} (b - U w)
+// Z_j = A_g(R_j)^{-1} U is never stored: its nc m columns go through the batched sweeps in
+// passes of as many columns as the workspace holds, and only its rows `rows` are kept, as
+// K_j (row-major, m^2 doubles per scenario), then factorised in place (LU, partial pivoting).
+constexpr int kEnsCycMax = 512;           // n_cyc <= this for ensembles (m = 1024: 8 MB per K_j)
+constexpr int kEnsFacThreads = 1024;      // k_e_cyc_factor's workgroup
+constexpr int kEnsCycLdsBytes = 160 * 1024 - 1024;  // K_j and a row in LDS up to this (m <= 142)
+
+// The unit right-hand sides of one pass (the buffer zeroed before): workspace column c serves
+// the pair g0 + c = s m + u -- scenario s (its lumped mass: map[c] = s), unit row u.
+__global__ __launch_bounds__(256) void k_e_cyc_unit(double* __restrict__ Bu, int64_t ld,
+                                                    const int* __restrict__ rows, int m, int g0,
+                                                    int ncols, int* __restrict__ map) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= ncols) return;
+  const int g = g0 + c;
+  map[c] = g / m;
+  Bu[c * ld + rows[g % m]] = 1.0;
+}
+
+// Column u of K_s from the pass's solutions: K_s[r][u] = Z[rows[r], c].
+__global__ __launch_bounds__(256) void k_e_cyc_extract(const double* __restrict__ Z, int64_t ld,
+                                                       const int* __restrict__ rows, int m,
+                                                       int g0, double* __restrict__ K) {
+  const int c = blockIdx.y;
+  const int g = g0 + c, s = g / m, u = g % m;
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= m) return;
+  K[(int64_t)s * m * m + (int64_t)r * m + u] = Z[c * ld + rows[r]];
+}
+
+// K_j += C^{-1} (1 / a_k on the two off-diagonals of pair k; a_k read from the assembled values
+// as k_cyc_cap reads it: a +-1 coupling, the same for every R), then P K_j = L U in place, one
+// workgroup per scenario. LDS: the matrix lives in dynamic LDS during the factorisation (the
+// same body, the same bits); otherwise in global memory. Either way the pivot row of a step is
+// staged in LDS (m doubles), so the trailing update reads one stream from the matrix. A zero coupling, or a zero or
+// non-finite pivot, sets the scenario's flag: its columns get no correction and are reported
+// unconverged.
+template <bool LDS>
+__global__ __launch_bounds__(kEnsFacThreads) void k_e_cyc_factor(Csr A,
+                                                                 const int* __restrict__ rows,
+                                                                 int m, double* __restrict__ Kall,
+                                                                 int* __restrict__ pivall,
+                                                                 int* __restrict__ flag) {
+  extern __shared__ double sRow[];  // the pivot row (m), then the matrix (LDS: m^2)
+  double* sK = sRow + m;
+  __shared__ double sVal[kEnsFacThreads / 64];
+  __shared__ int sIdx[kEnsFacThreads / 64];
+  __shared__ int sPiv, sBad;
+  constexpr int T = kEnsFacThreads;
+  const int tid = threadIdx.x, col = blockIdx.x;
+  double* Kg = Kall + (int64_t)col * m * m;
+  int* piv = pivall + (int64_t)col * m;
+  if (tid == 0) sBad = 0;
+  __syncthreads();
+  for (int k = tid; 2 * k < m; k += T) {
+    const int q = rows[2 * k], lam = rows[2 * k + 1];
+    double a = 0.0;
+    for (int p = A.rowptr[q]; p < A.rowptr[q + 1]; ++p)
+      if (A.col[p] == lam) a = A.val[p];
+    const double ia = 1.0 / a;
+    if (a == 0.0 || !isfinite(ia)) {
+      sBad = 1;  // (several threads may store the same 1: read after the barrier only)
+    } else {
+      Kg[(int64_t)(2 * k) * m + 2 * k + 1] += ia;
+      Kg[(int64_t)(2 * k + 1) * m + 2 * k] += ia;
+    }
+  }
+  __syncthreads();
+  if (LDS) {
+    for (int i = tid; i < m * m; i += T) sK[i] = Kg[i];
+    __syncthreads();
+  }
+  double* K = LDS ? sK : Kg;
+  for (int k = 0; k < m && !sBad; ++k) {
+    // the pivot: the largest |K[i][k]|, i >= k, the lowest such i (a NaN counts as infinite)
+    double best = -1.0;
+    int bi = m;
+    for (int i = k + tid; i < m; i += T) {
+      double v = fabs(K[(int64_t)i * m + k]);
+      if (!(v == v)) v = INFINITY;
+      if (v > best) {
+        best = v;
+        bi = i;
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const double ov = __shfl_down(best, off, 64);
+      const int oi = __shfl_down(bi, off, 64);
+      if (ov > best || (ov == best && oi < bi)) {
+        best = ov;
+        bi = oi;
+      }
+    }
+    if ((tid & 63) == 0) {
+      sVal[tid >> 6] = best;
+      sIdx[tid >> 6] = bi;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < T / 64; ++w)
+        if (sVal[w] > best || (sVal[w] == best && sIdx[w] < bi)) {
+          best = sVal[w];
+          bi = sIdx[w];
+        }
+      if (!(best > 0.0) || !isfinite(best) || bi >= m) {
+        sBad = 1;
+      } else {
+        sPiv = bi;
+        piv[k] = bi;
+      }
+    }
+    __syncthreads();
+    if (sBad) break;
+    const int p = sPiv;
+    // rows k and p change places; the new row k is staged in LDS for the update
+    for (int j = tid; j < m; j += T) {
+      const double a = K[(int64_t)k * m + j], b = K[(int64_t)p * m + j];
+      if (p != k) {
+        K[(int64_t)k * m + j] = b;
+        K[(int64_t)p * m + j] = a;
+      }
+      sRow[j] = b;
+    }
+    __syncthreads();
+    const double pv = sRow[k];
+    // the multipliers and the trailing block: a wave per row, its lanes along the row (the
+    // row's multiplier is read by every lane, then lane 0 stores it: the wave barrier keeps
+    // the store behind the wave's loads)
+    for (int i = k + 1 + (tid >> 6); i < m; i += T / 64) {
+      double* Ki = K + (int64_t)i * m;
+      const double l = Ki[k] / pv;
+#pragma unroll 4
+      for (int j = k + 1 + (tid & 63); j < m; j += 64) Ki[j] -= l * sRow[j];
+      __builtin_amdgcn_wave_barrier();
+      if ((tid & 63) == 0) Ki[k] = l;
+    }
+    __syncthreads();
+  }
+  const int bad = sBad;
+  if (LDS && !bad)
+    for (int i = tid; i < m * m; i += T) Kg[i] = sK[i];
+  if (tid == 0) flag[col] = bad;
+}
+
+// Per listed column: w = K_j^{-1} U^T x_g with the column's factors (U^T x_g in dynamic LDS, m
+// doubles, as k_b_cyc_w; the row swaps, the unit lower and the upper substitution, one entry per
+// thread and step), then the second right-hand side b - U w patched into the input column in
+// place: its m entries are saved first (save, m per column) and k_e_cyc_restore puts them
+// back bit for bit after the second sweep. A flagged scenario: w = 0.
+__global__ __launch_bounds__(256) void k_e_cyc_w(const double* __restrict__ X,
+                                                 double* __restrict__ Bin, int64_t ld,
+                                                 const int* __restrict__ list,
+                                                 const int* __restrict__ rows, int m,
+                                                 const double* __restrict__ Kall,
+                                                 const int* __restrict__ pivall,
+                                                 const int* __restrict__ flag,
+                                                 double* __restrict__ save) {
+  extern __shared__ double g[];
+  const int col = list ? list[blockIdx.x] : blockIdx.x;
+  const int tid = threadIdx.x;
+  const double* K = Kall + (int64_t)col * m * m;
+  const int* piv = pivall + (int64_t)col * m;
+  double* b = Bin + col * ld;
+  double* sv = save + (int64_t)col * m;
+  for (int i = tid; i < m; i += 256) {
+    g[i] = X[col * ld + rows[i]];
+    sv[i] = b[rows[i]];
+  }
+  __syncthreads();
+  if (flag[col]) return;
+  if (tid == 0)
+    for (int k = 0; k < m; ++k) {
+      const int p = piv[k];
+      if (p != k) {
+        const double t = g[k];
+        g[k] = g[p];
+        g[p] = t;
+      }
+    }
+  __syncthreads();
+  for (int k = 0; k < m; ++k) {  // L y = P g (unit diagonal)
+    const double gk = g[k];
+    for (int i = k + 1 + tid; i < m; i += 256) g[i] -= K[(int64_t)i * m + k] * gk;
+    __syncthreads();
+  }
+  for (int k = m - 1; k >= 0; --k) {  // U w = y
+    if (tid == 0) g[k] /= K[(int64_t)k * m + k];
+    __syncthreads();
+    const double gk = g[k];
+    for (int i = tid; i < k; i += 256) g[i] -= K[(int64_t)i * m + k] * gk;
+    __syncthreads();
+  }
+  for (int i = tid; i < m; i += 256) b[rows[i]] = sv[i] - g[i];
+}
+
+__global__ __launch_bounds__(256) void k_e_cyc_restore(double* __restrict__ Bin, int64_t ld,
+                                                       const int* __restrict__ list,
+                                                       const int* __restrict__ rows, int m,
+                                                       const double* __restrict__ save) {
+  const int col = list ? list[blockIdx.y] : blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < m) Bin[col * ld + rows[i]] = save[(int64_t)col * m + i];
+}
+
 constexpr int kBatchChunkMax = 64;     // default chunk: columns per pass
 constexpr int kBatchChunkEnvMax = 4096;  // NXHIP_BATCH_CHUNK is clamped to this (grid.y)
 constexpr double kBatchMemShare = 0.25;  // of the free device memory, for the workspace
@@ -13403,20 +13623,32 @@ struct BatchWs {
   double *Xd, *Ld;        // nx_batch_hvp (bws_hvp): tangent and second-order adjoint, cap x ld
   double *vR;             // the direction's v_R, cap x E (v_bc / v_f reuse bc / ef)
   double *HR, *Hf, *Hbc;  // and its outputs: cap x E, cap x E, cap x 2 E
+  // ensembles on a graph with cycles (bws_ecyc): K_j and its factors (cap x m^2), the patched
+  // entries of the input column (cap x m), the pivots (cap x m), the failure flags and the
+  // unit solves' column -> scenario map (cap each)
+  double *eK, *esave;
+  int *epiv, *eflag, *emap;
   int* list;              // cap
   int nblk;
 };
 
-size_t batch_col_doubles(const nx_network* h, bool grad, bool ens, bool hvp) {
+// The per-column part of an ensemble's cycle correction (nothing above kEnsCycMax: such a
+// handle takes no ensemble).
+int64_t batch_ecyc_doubles(const nx_network* h, bool ecyc) {
+  const int64_t m = 2 * (int64_t)h->n_cyc;
+  return ecyc && h->n_cyc > 0 && h->n_cyc <= kEnsCycMax ? m * m + 2 * m + 2 : 0;
+}
+size_t batch_col_doubles(const nx_network* h, bool grad, bool ens, bool hvp, bool ecyc) {
   const int64_t E = h->E, S = std::max<int64_t>(h->pc_slots, 1), m = 2 * (int64_t)h->n_cyc;
   const int nblk = grid_of(h->n_own, kBlock);
   const int64_t g = grad ? 2 * h->n_col + 4 * E + 1 : 0;  // X stays resident beside C and L
   const int64_t en = ens ? E * (int64_t)(h->N + 1) + E : 0;  // the column's own dq and R
   const int64_t hv = hvp ? 2 * h->n_col + 5 * E : 0;  // Xd, Ld; v_R, HR, Hf, Hbc
-  return (size_t)(4 * h->n_col + 3 * E + 5 * S + 3 * E + 1 + 2 * nblk + 2 + m + g + en + hv);
+  return (size_t)(4 * h->n_col + 3 * E + 5 * S + 3 * E + 1 + 2 * nblk + 2 + m + g + en + hv +
+                  batch_ecyc_doubles(h, ecyc));
 }
-size_t batch_bytes(const nx_network* h, int cap, bool grad, bool ens, bool hvp) {
-  return 8 * (batch_col_doubles(h, grad, ens, hvp) * (size_t)cap + (size_t)(3 * h->n_col)) +
+size_t batch_bytes(const nx_network* h, int cap, bool grad, bool ens, bool hvp, bool ecyc) {
+  return 8 * (batch_col_doubles(h, grad, ens, hvp, ecyc) * (size_t)cap + (size_t)(3 * h->n_col)) +
          sizeof(int) * (size_t)cap + 64;
 }
 BatchWs batch_carve(const nx_network* h, int cap) {
@@ -13473,6 +13705,13 @@ BatchWs batch_carve(const nx_network* h, int cap) {
     w.Hf = take(cap * E);
     w.Hbc = take(cap * 2 * E);
   }
+  if (batch_ecyc_doubles(h, h->bws_ecyc) > 0) {  // (behind everything the earlier calls use)
+    w.eK = take(cap * m * m);
+    w.esave = take(cap * m);
+    w.epiv = reinterpret_cast<int*>(take(cap * m));
+    w.eflag = reinterpret_cast<int*>(take(cap));
+    w.emap = reinterpret_cast<int*>(take(cap));
+  }
   w.list = reinterpret_cast<int*>(p);
   return w;
 }
@@ -13488,10 +13727,17 @@ bool batch_ok(const nx_network* h) {
 // size follows the decomposition's slots and the cycle chains, which nx_set_preconditioner
 // and nx_set_cycles change after a workspace was allocated (nx_batch_rhs is legal before
 // either), so the allocated bytes are checked, not the column count alone.
-bool batch_fits(const nx_network* h, int chunk, bool grad, bool ens, bool hvp) {
+bool batch_fits(const nx_network* h, int chunk, bool grad, bool ens, bool hvp, bool ecyc) {
   return h->bws != nullptr && chunk <= h->bws_cap && (!grad || h->bws_grad) &&
-         (!ens || h->bws_ens) && (!hvp || h->bws_hvp) &&
-         batch_bytes(h, h->bws_cap, h->bws_grad, h->bws_ens, h->bws_hvp) <= h->bws_bytes;
+         (!ens || h->bws_ens) && (!hvp || h->bws_hvp) && (!ecyc || h->bws_ecyc) &&
+         batch_bytes(h, h->bws_cap, h->bws_grad, h->bws_ens, h->bws_hvp, h->bws_ecyc) <=
+             h->bws_bytes;
+}
+
+// Ensembles take this handle's graph with cycles (nx_set_ensemble_cycles): a correction per
+// scenario, up to kEnsCycMax cycle chains.
+bool ens_cyc_on(const nx_network* h) {
+  return h->ens_cyc && h->n_cyc > 0 && h->n_cyc <= kEnsCycMax;
 }
 
 // The chunk size of this call and a workspace that holds it: NXHIP_BATCH_CHUNK (read per
@@ -13501,35 +13747,44 @@ int batch_workspace(nx_network* h, int n_cols, int* chunk_out, bool grad = false
                     bool ens = false, bool hvp = false) {
   hvp = hvp || h->bws_hvp;
   grad = grad || hvp || h->bws_grad;  // (the Hessian-vector product implies the gradient's part)
+  // an ensemble with a cycle correction per scenario: its nc m unit solves go in passes of as
+  // many columns as the workspace holds, so it holds kBatchChunkMax even for fewer scenarios
+  const bool wide = ens && ens_cyc_on(h);
+  const bool ecyc = wide || h->bws_ecyc;
   ens = ens || h->bws_ens;
   int chunk = std::min(n_cols, kBatchChunkMax);
+  int cap = wide ? kBatchChunkMax : chunk;  // the workspace's columns (>= chunk)
   const char* e = std::getenv("NXHIP_BATCH_CHUNK");
   if (e != nullptr && std::atoi(e) > 0) {
     chunk = std::min(std::min(std::atoi(e), kBatchChunkEnvMax), n_cols);
-  } else if (!batch_fits(h, chunk, grad, ens, hvp)) {
+    cap = wide ? std::max(chunk, kBatchChunkMax) : chunk;
+  } else if (!batch_fits(h, cap, grad, ens, hvp, ecyc)) {
     size_t fr = 0, tot = 0;
     HIPCALL(hipMemGetInfo(&fr, &tot));
     const double room = kBatchMemShare * (double)fr;
-    while (chunk > 1 && (double)batch_bytes(h, chunk, grad, ens, hvp) > room) --chunk;
+    while (cap > 1 && (double)batch_bytes(h, cap, grad, ens, hvp, ecyc) > room) --cap;
+    chunk = std::min(chunk, cap);
   }
-  if (!batch_fits(h, chunk, grad, ens, hvp)) {
+  if (!batch_fits(h, cap, grad, ens, hvp, ecyc)) {
     HIPCALL(hipStreamSynchronize(h->stream));
     if (h->bws) (void)hipFree(h->bws);
     h->bws = nullptr;
     h->bws_cap = 0;
     h->bws_bytes = 0;
     for (;;) {
-      if (hipMalloc(&h->bws, batch_bytes(h, chunk, grad, ens, hvp)) == hipSuccess) break;
+      if (hipMalloc(&h->bws, batch_bytes(h, cap, grad, ens, hvp, ecyc)) == hipSuccess) break;
       (void)hipGetLastError();
       h->bws = nullptr;
-      if (chunk == 1) return fail(NX_ERR_HIP, "nx_batch_solve: no memory for one column's workspace");
-      chunk = std::max(1, chunk / 2);
+      if (cap == 1) return fail(NX_ERR_HIP, "nx_batch_solve: no memory for one column's workspace");
+      cap = std::max(1, cap / 2);
     }
-    h->bws_cap = chunk;
+    chunk = std::min(chunk, cap);
+    h->bws_cap = cap;
     h->bws_grad = grad;
     h->bws_ens = ens;
     h->bws_hvp = hvp;
-    h->bws_bytes = batch_bytes(h, chunk, grad, ens, hvp);
+    h->bws_ecyc = ecyc;
+    h->bws_bytes = batch_bytes(h, cap, grad, ens, hvp, ecyc);
   }
   *chunk_out = chunk;
   return NX_OK;
@@ -13544,14 +13799,19 @@ struct BatchEns {
   const double* dq;  // cap x n_dq
   int64_t n_dq;
   const double* R;   // cap x E
+  // the unit solves of the cycle correction's build (batch_ens_cyc_build): the tree solve
+  // alone, workspace column c with the lumped mass of scenario map[c]
+  const int* map;
+  bool raw;
 };
 BatchEns batch_ens(const nx_network* h, const BatchWs& ws) {
-  return BatchEns{ws.edq, h->E * (int64_t)(h->N + 1), ws.eR};
+  return BatchEns{ws.edq, h->E * (int64_t)(h->N + 1), ws.eR, nullptr, false};
 }
 
 // The chunk's inputs to the device and its right-hand sides into ws.B (one launch). edge_R
 // (host, n_cols x E; an ensemble): the chunk's R columns go to ws.eR as well, and the launch
 // writes every column's lumped mass beside its right-hand side (k_e_setup).
+int batch_ens_cyc_build(nx_network* h, const BatchWs& ws, int nc);
 int batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const double* edge_bc,
                     const double* edge_f, const double* f_const,
                     const double* edge_R = nullptr) {
@@ -13590,6 +13850,8 @@ int batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const doub
                        nc, ws.bc, ef, ef_ld, ws.fc, ws.B, ws.cols.ld);
   HIPCALL(hipGetLastError());
   h->b_launches += 1;
+  // an ensemble on a graph with cycles: the chunk's corrections, once, for all of its solves
+  if (edge_R && h->n_cyc > 0) CHECK(batch_ens_cyc_build(h, ws, nc));
   return NX_OK;
 }
 
@@ -13606,19 +13868,36 @@ void batch_sweeps_wc(nx_network* h, const BatchWs& ws, const int* list, int nc, 
   bc.list = list;
   bc.dq = ens ? ens->dq : nullptr;
   bc.n_dq = ens ? ens->n_dq : 0;
-  if (h->pc_jobs > 0) {
-    hipLaunchKernelGGL((k_b_up<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, h->stream, pa,
-                       bc, in);
+  bc.dq_map = ens ? ens->map : nullptr;
+  auto tree = [&]() {  // out = A_g^{-1} in
+    if (h->pc_jobs > 0) {
+      hipLaunchKernelGGL((k_b_up<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, h->stream,
+                         pa, bc, in);
+      h->b_launches += 1;
+    }
+    hipLaunchKernelGGL(k_b_top, dim3(nc), dim3(kTopThreads), 0, h->stream, pa, bc, in, out);
     h->b_launches += 1;
-  }
-  hipLaunchKernelGGL(k_b_top, dim3(nc), dim3(kTopThreads), 0, h->stream, pa, bc, in, out);
-  h->b_launches += 1;
-  if (h->pc_jobs > 0) {
-    hipLaunchKernelGGL((k_b_down<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, h->stream,
-                       pa, bc, in, out);
+    if (h->pc_jobs > 0) {
+      hipLaunchKernelGGL((k_b_down<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, h->stream,
+                         pa, bc, in, out);
+      h->b_launches += 1;
+    }
+  };
+  tree();
+  if (h->n_cyc > 0 && ens) {
+    // the column's own correction (the handle's Z / Cinv belong to the resident R): w from the
+    // column's factors, the input patched to b - U w, the tree solve again, the input put back
+    if (ens->raw) return;
+    const int m = 2 * h->n_cyc;
+    double* inw = const_cast<double*>(in);
+    hipLaunchKernelGGL(k_e_cyc_w, dim3(nc), dim3(256), sizeof(double) * m, h->stream, out, inw,
+                       bc.ld, list, h->d_cyc_rows, m, ws.eK, ws.epiv, ws.eflag, ws.esave);
     h->b_launches += 1;
-  }
-  if (h->n_cyc > 0) {
+    tree();
+    hipLaunchKernelGGL(k_e_cyc_restore, dim3(grid_of(m, 256), nc), dim3(256), 0, h->stream, inw,
+                       bc.ld, list, h->d_cyc_rows, m, ws.esave);
+    h->b_launches += 1;
+  } else if (h->n_cyc > 0) {
     const int m = 2 * h->n_cyc;
     hipLaunchKernelGGL(k_b_cyc_w, dim3(grid_of(m, 256), nc), dim3(256), sizeof(double) * m,
                        h->stream, out, bc.ld, list, h->d_cyc_rows, m, h->cyc_cinv, ws.cw);
@@ -13642,6 +13921,54 @@ int batch_sweeps(nx_network* h, const BatchWs& ws, const int* list, int nc, cons
     default: batch_sweeps_wc<64, 4>(h, ws, list, nc, in, out, ens); break;
   }
   HIPCALL(hipGetLastError());
+  return NX_OK;
+}
+
+// The cycle corrections of a chunk of nc scenarios (after k_e_setup has written their lumped
+// masses; ws.R / ws.D are free then and carry the unit vectors and their solutions): the
+// nc m unit solves in passes of the workspace's columns -- a pass may straddle scenarios, the
+// last one is partial -- each pass zero fill, k_e_cyc_unit, the tree solve, k_e_cyc_extract;
+// then one k_e_cyc_factor. All solves of the chunk share the factors. Launches: P (2 + T) + 1
+// with P = ceil(nc m / workspace columns) and T the tree solve's launches (3; 1 without jobs).
+int batch_ens_cyc_build(nx_network* h, const BatchWs& ws, int nc) {
+  const int m = 2 * h->n_cyc, W = h->bws_cap;
+  const int64_t ld = ws.cols.ld;
+  const int total = nc * m;
+  BatchEns be = batch_ens(h, ws);
+  be.map = ws.emap;
+  be.raw = true;
+  for (int g0 = 0; g0 < total; g0 += W) {
+    const int ncp = std::min(W, total - g0);
+    HIPCALL(hipMemsetAsync(ws.R, 0, sizeof(double) * ld * ncp, h->stream));
+    hipLaunchKernelGGL(k_e_cyc_unit, dim3(grid_of(ncp, 256)), dim3(256), 0, h->stream, ws.R, ld,
+                       h->d_cyc_rows, m, g0, ncp, ws.emap);
+    h->b_launches += 1;
+    CHECK(batch_sweeps(h, ws, nullptr, ncp, ws.R, ws.D, &be));
+    hipLaunchKernelGGL(k_e_cyc_extract, dim3(grid_of(m, 256), ncp), dim3(256), 0, h->stream, ws.D,
+                       ld, h->d_cyc_rows, m, g0, ws.eK);
+    h->b_launches += 1;
+  }
+  const size_t rb = sizeof(double) * (size_t)m;  // the staged pivot row
+  const size_t kb = rb + sizeof(double) * (size_t)m * m;
+  const char* e = std::getenv("NXHIP_ENS_CYC_LDS");  // (test hook: 0 forces global memory)
+  const bool lds = kb <= (size_t)kEnsCycLdsBytes && !(e != nullptr && std::atoi(e) == 0);
+  if (lds) {
+    // (once per thread and kernel: opt_in_lds keeps the list of what it has opted in)
+    opt_in_lds(reinterpret_cast<const void*>(&k_e_cyc_factor<true>), kEnsCycLdsBytes);
+    hipLaunchKernelGGL(k_e_cyc_factor<true>, dim3(nc), dim3(kEnsFacThreads), kb, h->stream,
+                       csr_of(h), h->d_cyc_rows, m, ws.eK, ws.epiv, ws.eflag);
+  } else {
+    hipLaunchKernelGGL(k_e_cyc_factor<false>, dim3(nc), dim3(kEnsFacThreads), rb, h->stream,
+                       csr_of(h), h->d_cyc_rows, m, ws.eK, ws.epiv, ws.eflag);
+  }
+  HIPCALL(hipGetLastError());
+  h->b_launches += 1;
+  h->ecyc_unit += total;
+  h->ecyc_storage = lds ? 1 : 2;
+  // (read after the first residual's synchronisation: batch_solve_cols)
+  h->ecyc_failed.assign((size_t)h->bws_cap, 0);
+  HIPCALL(hipMemcpyAsync(h->ecyc_failed.data(), ws.eflag, sizeof(int) * nc, hipMemcpyDeviceToHost,
+                         h->stream));
   return NX_OK;
 }
 
@@ -13750,6 +14077,12 @@ int batch_solve_cols(nx_network* h, const BatchWs& ws, int nc, const double* Bv,
     if (iters) iters[c] = 1;
     if (relres) relres[c] = r;
     if (converged) converged[c] = (bb == 0.0 || r <= rtol) ? 1 : 0;
+    if (ens && h->n_cyc > 0 && h->ecyc_failed[(size_t)c]) {
+      // no factors for this scenario's cycle correction: the column is the tree solve's
+      // (finite), reported unconverged whatever its residual, and not refined
+      if (converged) converged[c] = 0;
+      continue;
+    }
     if (bb > 0.0 && !(r <= rtol)) redo.push_back(c);
   }
   if (!redo.empty()) {  // one refinement pass over the failing columns only: x += A^{-1} r
@@ -13926,9 +14259,12 @@ bool ensemble_R_bad(const double* edge_R, int64_t count) {
   return false;
 }
 
-// Where the ensemble calls apply: the batched kernels on a forest (the cycle correction is
-// per matrix: 2 n_cyc solves per column).
-bool ensemble_ok(const nx_network* h) { return batch_ok(h) && h->tree_exact && h->n_cyc == 0; }
+// Where the ensemble calls apply: the batched kernels on a forest, or on a graph with cycles
+// whose handle has opted in (nx_set_ensemble_cycles: the correction is per matrix, 2 n_cyc unit
+// solves and a factorisation per scenario, batch_ens_cyc_build).
+bool ensemble_ok(const nx_network* h) {
+  return batch_ok(h) && ((h->tree_exact && h->n_cyc == 0) || ens_cyc_on(h));
+}
 
 // The observed rows of a gradient / Hessian-vector call: in range and distinct.
 int batch_obs_rows_check(int64_t n, int32_t n_obs, const int32_t* obs_rows) {
@@ -14000,6 +14336,7 @@ int batch_gradient_run(nx_network* h, int32_t n_cols, const double* edge_R, cons
   CHECK(batch_obs_rows_check(n, n_obs, obs_rows));
   CHECK(set_device(h));
   h->b_refined = h->b_fallback = 0;
+  if (ens) h->ecyc_unit = h->ecyc_storage = 0;
   h->b_launches = made_current + (!ens && h->dq_stale ? 1 : 0);
   int chunk = 0;
   CHECK(batch_workspace(h, n_cols, &chunk, true, ens));
@@ -14189,6 +14526,7 @@ int batch_hvp_run(nx_network* h, int32_t n_cols, const double* edge_R, const dou
   CHECK(batch_obs_rows_check(n, n_obs, obs_rows));
   CHECK(set_device(h));
   h->b_refined = h->b_fallback = 0;
+  if (ens) h->ecyc_unit = h->ecyc_storage = 0;
   h->b_launches = made_current + (!ens && h->dq_stale ? 1 : 0);
   int chunk = 0;
   CHECK(batch_workspace(h, n_cols, &chunk, true, ens, true));
@@ -14312,6 +14650,22 @@ NX_API int nx_ensemble_supported(nx_network_t* h, int32_t* ok) {
   return NX_OK;
 }
 
+NX_API int nx_set_ensemble_cycles(nx_network_t* h, int32_t enable) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (enable != 0 && enable != 1) return fail(NX_ERR_ARG, "enable: 0 or 1");
+  h->ens_cyc = enable != 0;
+  return NX_OK;
+}
+
+NX_API int nx_get_ensemble_cycles(nx_network_t* h, int32_t* enabled, int32_t* unit_solves,
+                                  int32_t* storage) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (enabled) *enabled = h->ens_cyc ? 1 : 0;
+  if (unit_solves) *unit_solves = h->ecyc_unit;
+  if (storage) *storage = h->ecyc_storage;
+  return NX_OK;
+}
+
 NX_API int nx_ensemble_solve(nx_network_t* h, int32_t n_cols, const double* edge_R,
                              const double* edge_bc, const double* edge_f, const double* f_const,
                              double rtol, int32_t order, double* out, int32_t* iters,
@@ -14323,7 +14677,8 @@ NX_API int nx_ensemble_solve(nx_network_t* h, int32_t n_cols, const double* edge
   if (!ensemble_ok(h)) {
     if (batch_ok(h) && h->n_cyc > 0)
       return fail(NX_ERR_STATE, "nx_ensemble_solve: a graph with cycles (the correction is per "
-                                "matrix); loop over nx_set_coefficients / nx_solve");
+                                "matrix: nx_set_ensemble_cycles, up to 512 cycle chains); loop "
+                                "over nx_set_coefficients / nx_solve");
     return fail(NX_ERR_STATE, "nx_ensemble_solve: the batched ensemble does not apply to this "
                               "handle (nx_ensemble_supported)");
   }
@@ -14333,6 +14688,7 @@ NX_API int nx_ensemble_solve(nx_network_t* h, int32_t n_cols, const double* edge
     return fail(NX_ERR_ARG, "nx_ensemble_solve: R must be finite and positive");
   CHECK(set_device(h));
   h->b_refined = h->b_fallback = 0;
+  h->ecyc_unit = h->ecyc_storage = 0;
   h->b_launches = made_current;  // (the handle's lumped mass is not read: no ensure_dq)
   int chunk = 0;
   CHECK(batch_workspace(h, n_cols, &chunk, false, true));

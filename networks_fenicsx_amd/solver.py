@@ -198,6 +198,16 @@ class Solver:
         petsc_options_prefix: options prefix (kept for API compatibility)
         petsc_options: dictionary of PETSc-style options (see module docstring)
         kind: matrix kind (None, "mpi" or "nest"); recorded, storage is device CSR
+        ensemble_cycles: let :meth:`solve_ensemble`, :meth:`gradient` and
+            :meth:`hessian_vector` with ``R=`` take the batched path on a graph with cycles
+            (``nx_set_ensemble_cycles``: a cycle correction per scenario, up to 512 cycle
+            chains). ``None`` reads ``NXHIP_ENS_CYCLES`` (``"1"`` on; off when unset). Off, these
+            calls behave as before on such a graph: the per-scenario loop, or
+            ``NotImplementedError``. The batched results agree with the one-matrix path to
+            rounding, not bit for bit (the correction solves again instead of storing
+            ``A_g^{-1} U``). Measured against the per-scenario loop: 1.5 to
+            37 x faster at 240 to 506 cycle chains and B = 1 to 64, except B = 1 at 506 cycle
+            chains, where the one-workgroup factorisation makes it 0.80 x the loop.
     """
 
     def __init__(
@@ -206,8 +216,13 @@ class Solver:
         petsc_options_prefix: str = "NetworkSolver_",
         petsc_options: dict | None = None,
         kind: str | typing.Sequence[typing.Sequence[str]] | None = None,
+        *,
+        ensemble_cycles: bool | None = None,
     ):
         self._assembler = assembler
+        if ensemble_cycles is None:
+            ensemble_cycles = os.environ.get("NXHIP_ENS_CYCLES", "") == "1"
+        self._ens_cycles = bool(ensemble_cycles)
         opts = dict(_DEFAULTS if petsc_options is None else petsc_options)
         clean = {}
         for k, v in opts.items():
@@ -289,6 +304,8 @@ class Solver:
             h.set_pc_exact(self._pc_exact)
         self.assembler.set_direct(self._direct and (self.assembler.preconditioned
                                                     or self.assembler.fe_direct_available))
+        # (handle state, set on every call: two solvers on one assembler each get their own)
+        h.set_ensemble_cycles(self._ens_cycles)
 
     @timed("nxfx:Solver:solve_many")
     def solve_many(self, p_bc, f=None) -> "BatchResult":
@@ -370,14 +387,16 @@ class Solver:
         ``p_bc``: None (the boundary data of the last ``compute_forms`` on every scenario) or B
         items as :meth:`solve_many` takes them; ``f``: as for :meth:`solve_many`.
 
-        Where ``nx_ensemble_supported`` holds (P1/DG0, one rank, the direct solve, a forest)
+        Where ``nx_ensemble_supported`` holds (P1/DG0, one rank, the direct solve; a forest, or
+        with ``ensemble_cycles=True`` a graph with up to 512 cycle chains: a cycle correction
+        per scenario, ``2 n_cyc`` batched unit solves and one factorisation each)
         the scenarios go through ``nx_ensemble_solve`` in one batched pass
         (``path == "batched"``): a matrix per column, none of them assembled. The matrix of the
         last ``compute_forms`` is assembled first if it is not current (the residual reads its
         R-independent entries). A scenario the batched pass reports unconverged is solved again
         by the sequential path and counted in ``info["fallback"]``.
 
-        Otherwise -- a graph with cycles, general degrees, ``ksp_type="minres"``,
+        Otherwise -- a graph with cycles without ``ensemble_cycles``, general degrees, ``ksp_type="minres"``,
         ``pc_type="none"``, the lumped mass, or ``NXHIP_BATCH=0`` -- the per-scenario loop runs
         (``"sequential"``): the scenario's coefficients are uploaded, R included, then assembly,
         solve, gather. Afterwards the coefficients of the last ``compute_forms`` are put back,
@@ -463,7 +482,8 @@ class Solver:
 
         ``R`` (``(B, num_edges)`` or ``(B,)`` constants, as :meth:`solve_ensemble`): scenario j
         is evaluated at ``R[j]`` instead of the last ``compute_forms``' R
-        (``nx_ensemble_gradient``; a forest only, elsewhere ``NotImplementedError``), and
+        (``nx_ensemble_gradient``; a forest, or a graph with cycles under
+        ``ensemble_cycles=True``, elsewhere ``NotImplementedError``), and
         ``p_bc`` may be None (the last ``compute_forms``' boundary data).
         ``derivatives=False`` (with ``R``): the objective values alone -- the forward solves,
         no adjoint; ``dR``, ``df`` and ``dp_bc`` are None and ``iterations``,
@@ -592,7 +612,8 @@ class Solver:
         three solves, no adjoint, no gradient (``dR``, ``df``, ``dp_bc`` None).
 
         It runs where :meth:`gradient` runs and raises ``NotImplementedError`` elsewhere; with
-        ``R`` on a forest only (``nx_ensemble_hvp``). The reference has no counterpart."""
+        ``R`` on a forest, or on a graph with cycles under ``ensemble_cycles=True``
+        (``nx_ensemble_hvp``). The reference has no counterpart."""
         if self._closed:
             raise RuntimeError("the solver has been destroyed")
         asm = self.assembler
