@@ -471,6 +471,65 @@ int nx_get_batch_info(nx_network_t* h, int32_t* launches, int32_t* refined, int3
                       int32_t* chunk);
 
 /*
+ * nx_batch_solve for flux degree k >= 2 with DG0 pressure: many boundary / source scenarios
+ * against the current matrix of a (k, 0) handle in one batched pass of its condensed direct
+ * solve (nx_fe_set_direct). The reference answers one scenario per KSP solve
+ * (solver.py:107-135) and would loop compute_forms + assemble + solve; here the per-cell
+ * condensation, the auxiliary P1/DG0 tree sweeps and the expansion get a column dimension.
+ *
+ * nx_fe_batch_supported: *ok = 1 when nx_fe_batch_solve takes the batched kernels on this
+ * handle, else 0: an nx_create_fe handle with pressure degree 0 and an auxiliary handle
+ * attached (nx_fe_set_direct), one rank, not in a group, no ghosts, nx_set_solver(h, 1, 1), and
+ * the auxiliary handle with the exact preconditioner, the LDS sweeps, and tree_exact or a cycle
+ * correction. Continuous-pressure and P1/DG0 handles give 0 (and nx_batch_supported stays 0
+ * for every nx_create_fe handle).
+ *
+ * nx_fe_batch_solve: n_cols scenarios; edge_bc / edge_f / f_const / rtol / order / out /
+ * iters / relres / converged as nx_batch_solve, out = n_cols x n_rows of the (k, 0) handle;
+ * maxit caps the MINRES of a column's single-column fallback. NX_ERR_STATE where
+ * nx_fe_batch_supported says 0, where the matrix has not been assembled for the resident
+ * coefficients, or order != 0 without an output map; NX_ERR_ARG as nx_batch_solve (and
+ * maxit < 1). A pending deferred assembly is flushed first.
+ * Per chunk (the chunk rule is nx_batch_solve's; the workspace is the (k, 0) columns' plus the
+ * auxiliary system's, allocated on first use, freed by nx_destroy and when nx_fe_set_direct
+ * detaches; per column 4 n_rows + 2 n_aux + 3 E + 5 slots + 2 n_cyc doubles and the inputs):
+ *   k_fe_b_rhs        every column's rhs from the rhs gather tables, k_assemble_fe's terms in
+ *                     its order: bit-equal to nx_assemble's rhs of that scenario
+ *   k_fe_b_condense   b_v - C b_i on the vertex rows, pressure / multiplier rows copied, into
+ *                     the auxiliary columns; the auxiliary lumped mass (a + b) R h once per call
+ *   k_b_up / k_b_top / k_b_down with the auxiliary handle's decomposition, on this handle's
+ *                     stream; with cycles k_b_cyc_w / k_b_cyc_fix with the auxiliary Z / Cinv,
+ *                     built first (fe_cyc_build) where the matrix is new
+ *   k_fe_b_expand     the (k, 0) solution; added in a refinement pass
+ *   k_b_res / k_b_norms   the true residual against this handle's CSR
+ *   k_b_gather        when order != 0, then one copy per chunk
+ * Per column the policy is nx_batch_solve's: one refinement pass over the list of columns above
+ * rtol, then the handle's single-column route (fe_solve_direct, then MINRES capped at maxit)
+ * for a column still above it -- where that route ends unconverged with a residual no better
+ * than the refined column's (its MINRES is unpreconditioned and starts from zero), the refined
+ * column stands, with its residual and converged = 0; b = 0 gives x = 0, relres = 0,
+ * converged = 1. A column's bits do
+ * not depend on the other columns, its position, n_cols or the chunk size. The handle's
+ * coefficients, rhs, x, tmp, published state and snapshots are left as they were.
+ *
+ * Launches (nx_get_batch_info reports the last nx_fe_batch_solve as it does nx_batch_solve's):
+ * per chunk 9 on a forest -- rhs, condense, up, top, down, expand, residual, norms, gather -- 7
+ * where the decomposition has no subtree jobs (no up / down), 11 / 9 with cycles; 8 / 6 / 10 / 8
+ * with order = 0 (no gather). A chunk with a refinement pass adds 7 (5 without jobs), 9 (7)
+ * with cycles. What the call had to make current first is counted too: 1 for a flushed
+ * assembly and the whole build of the cycle correction.
+ *
+ * nx_fe_batch_rhs (test hook): k_fe_b_rhs alone; out = n_cols x n_rows, device layout.
+ */
+int nx_fe_batch_supported(nx_network_t* h, int32_t* ok);
+int nx_fe_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                      const double* edge_f, const double* f_const, double rtol, int32_t maxit,
+                      int32_t order, double* out, int32_t* iters, double* relres,
+                      int32_t* converged);
+int nx_fe_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc, const double* edge_f,
+                    const double* f_const, double* out);
+
+/*
  * Adjoint gradients of an observed-row objective with respect to every edge's R, every
  * boundary value and every edge's source, for n_cols scenarios, in two batched direct solves;
  * no solution leaves the device (the reference has no counterpart). Per scenario j over the

@@ -8515,6 +8515,12 @@ struct nx_network {
   bool cpc_failed = false;   // a singular capacitance matrix: the solves run MINRES
   int cpc_builds = 0;
   bool cpc_last = false;  // the last fe_cp_solve applied the correction
+  // nx_fe_batch_solve on a (k, 0) handle: bws holds this handle's columns; fe_bws the
+  // auxiliary system's (condensed rhs, solution, the sweeps' scratch, the cycle correction's
+  // w; fe_batch_carve), owned here: freed in nx_destroy and when nx_fe_set_direct detaches
+  void* fe_bws = nullptr;
+  int fe_bws_cap = 0;
+  size_t fe_bws_bytes = 0;
 };
 
 struct nx_group {
@@ -11027,6 +11033,7 @@ NX_API int nx_destroy(nx_network_t* h) {
   for (void* p : h->pc_bufs)
     if (p) (void)hipFree(p);
   if (h->bws) (void)hipFree(h->bws);
+  if (h->fe_bws) (void)hipFree(h->fe_bws);
   if (h->gobs) (void)hipFree(h->gobs);
   if (h->stash) (void)hipFree(h->stash);
   std::free(h->stash_state);
@@ -13812,13 +13819,13 @@ BatchEns batch_ens(const nx_network* h, const BatchWs& ws) {
 // (host, n_cols x E; an ensemble): the chunk's R columns go to ws.eR as well, and the launch
 // writes every column's lumped mass beside its right-hand side (k_e_setup).
 int batch_ens_cyc_build(nx_network* h, const BatchWs& ws, int nc);
-int batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const double* edge_bc,
-                    const double* edge_f, const double* f_const,
-                    const double* edge_R = nullptr) {
+// The chunk's boundary values and sources to the device (ws.bc, ws.ef / ws.fc). A column's
+// edge_f wins over its f_const; with neither the handle's source serves every column. *ef /
+// *ef_ld: what the rhs kernel reads as the per-edge source (null: ws.fc).
+int batch_inputs(nx_network* h, const BatchWs& ws, int c0, int nc, const double* edge_bc,
+                 const double* edge_f, const double* f_const, const double** ef_out,
+                 int64_t* ef_ld_out) {
   const int64_t E = h->E;
-  if (edge_R)
-    HIPCALL(hipMemcpyAsync(ws.eR, edge_R + (int64_t)c0 * E, sizeof(double) * E * nc,
-                           hipMemcpyHostToDevice, h->stream));
   HIPCALL(hipMemcpyAsync(ws.bc, edge_bc + (int64_t)c0 * 2 * E, sizeof(double) * 2 * E * nc,
                          hipMemcpyHostToDevice, h->stream));
   const double* ef = nullptr;
@@ -13839,6 +13846,20 @@ int batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const doub
                            h->stream));
     HIPCALL(hipStreamSynchronize(h->stream));  // (fc leaves scope)
   }
+  *ef_out = ef;
+  *ef_ld_out = ef_ld;
+  return NX_OK;
+}
+int batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const double* edge_bc,
+                    const double* edge_f, const double* f_const,
+                    const double* edge_R = nullptr) {
+  const int64_t E = h->E;
+  if (edge_R)
+    HIPCALL(hipMemcpyAsync(ws.eR, edge_R + (int64_t)c0 * E, sizeof(double) * E * nc,
+                           hipMemcpyHostToDevice, h->stream));
+  const double* ef = nullptr;
+  int64_t ef_ld = 0;
+  CHECK(batch_inputs(h, ws, c0, nc, edge_bc, edge_f, f_const, &ef, &ef_ld));
   const int64_t nthr = E * (int64_t)(h->N + 1) + h->B;
   const EdgeArgs ea{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N};
   if (edge_R)
@@ -14039,9 +14060,13 @@ int batch_restore(nx_network* h, const BatchWs& ws, const BatchSaved& s, bool wi
 // refinement, then MINRES): the column's assembled rhs (ws.B) stands in for the handle's,
 // which is put back with its x, tmp and published state (no assembly runs, so the handle's
 // coefficients are not involved). The solution goes to Xv's column (Bv / Xv: ws.B / ws.X, or
-// the adjoint's ws.C / ws.L).
+// the adjoint's ws.C / ws.L). have >= 0 (nx_fe_batch_solve, whose route ends in a capped,
+// unpreconditioned MINRES): the relative residual the column already has -- a single-column
+// solve that ends unconverged and no better than that leaves the column as it is, and
+// *relres = have.
 int batch_fallback(nx_network* h, const BatchWs& ws, const double* Bv, double* Xv, int wcol,
-                   double rtol, int32_t* it, double* relres, int32_t* conv) {
+                   double rtol, int32_t* it, double* relres, int32_t* conv,
+                   int32_t maxit = 50000, double have = -1.0) {
   const int64_t n = h->n_col;
   BatchSaved sv{};
   CHECK(batch_save(h, ws, &sv, true));
@@ -14049,8 +14074,10 @@ int batch_fallback(nx_network* h, const BatchWs& ws, const double* Bv, double* X
                          h->stream));
   h->have_rhs = true;
   nx_network* hs[1] = {h};
-  const int rc = solve_team(Team{hs, 1, nullptr}, rtol, 50000, 4, it, relres, conv);
-  if (rc == NX_OK)
+  const int rc = solve_team(Team{hs, 1, nullptr}, rtol, maxit, 4, it, relres, conv);
+  if (rc == NX_OK && have >= 0.0 && !*conv && !(*relres < have))
+    *relres = have;
+  else if (rc == NX_OK)
     HIPCALL(hipMemcpyAsync(Xv + wcol * n, h->x, sizeof(double) * n, hipMemcpyDeviceToDevice,
                            h->stream));
   CHECK(batch_restore(h, ws, sv, true));
@@ -14233,6 +14260,551 @@ NX_API int nx_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc
     CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.X, rtol, iters ? iters + c0 : nullptr,
                            relres ? relres + c0 : nullptr, converged ? converged + c0 : nullptr,
                            stats));
+    const double* src = ws.X;
+    if (order != 0) {
+      hipLaunchKernelGGL(k_b_gather, dim3(grid_of(n, kBlock), nc), dim3(kBlock), 0, h->stream, ws.X,
+                         ld, h->out_idx, n, ws.D);
+      HIPCALL(hipGetLastError());
+      h->b_launches += 1;
+      src = ws.D;
+    }
+    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * n, src, sizeof(double) * n * nc,
+                           hipMemcpyDeviceToHost, h->stream));
+    HIPCALL(hipStreamSynchronize(h->stream));
+    for (int c = 0; c < nc; ++c)  // b = 0: x = 0 exactly (no division by ||b||)
+      if (stats[2 * c + 1] == 0.0) std::fill_n(out + (int64_t)(c0 + c) * n, n, 0.0);
+  }
+  return NX_OK;
+}
+
+// ---- nx_fe_batch_solve: nx_batch_solve for a (k, 0) handle solved through its auxiliary
+// P1/DG0 system (nx_fe_set_direct). Per chunk: k_fe_b_rhs, k_fe_b_condense, the batched
+// sweeps with the auxiliary handle's PcArgs and a per-column scratch of its own (and its cycle
+// correction), k_fe_b_expand, then k_b_res / k_b_norms against this handle's CSR. Everything
+// runs on this handle's stream. The columns of this handle live in its bws (batch_carve), the
+// auxiliary system's in fe_bws.
+namespace {
+
+// ---- k_fe_condense, k_fe_expand and the rhs of k_assemble_fe with a column dimension
+// (nx_fe_batch_solve). One thread per row / vertex / cell as in the single-column kernels: it
+// loads what does not depend on the column once (its term list, row maps, R h, constants) and
+// walks the chunk's columns in tiles of kBatchTile, as k_b_res does, so a tile's loads are
+// independent and the maps are read once per tile, not once per column. Column c of a vector
+// starts at c * ld (the (k, 0) workspace) or c * lda (the auxiliary one); list: the columns a
+// launch serves (a refinement pass), or null: 0 .. ncols - 1. Every column takes the
+// single-column expression in its operation order, no contraction: its bits are the single
+// kernel's on the same inputs, whatever else is in the tile.
+struct FeTile {
+  int64_t col[kBatchTile];
+};
+__device__ __forceinline__ FeTile fe_tile(const int* __restrict__ list, int c0, int nt) {
+  FeTile t;
+#pragma unroll
+  for (int k = 0; k < kBatchTile; ++k) t.col[k] = k < nt ? (list ? list[c0 + k] : c0 + k) : 0;
+  return t;
+}
+
+// Every column's right-hand side in the (k, 0) layout from the rhs gather tables: fe_term's
+// terms (the column's source and boundary values in place of the handle's) summed from 0.0
+// left to right as k_assemble_fe sums them -- bit-equal to nx_assemble's rhs of that
+// scenario. edge_bc: column c at c * 2 E; edge_f: at c * ef_ld (0: one source for all), or
+// null: the constant f_const[c].
+__global__ __launch_bounds__(kBlock) void k_fe_b_rhs(FeArgs a, int ncols,
+                                                     const double* __restrict__ edge_bc,
+                                                     const double* __restrict__ edge_f,
+                                                     int64_t ef_ld,
+                                                     const double* __restrict__ f_const,
+                                                     double* __restrict__ out, int64_t ld) {
+#pragma clang fp contract(off)
+  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (row >= a.n_rows) return;
+  const int p0 = a.b_ptr[row], p1 = a.b_ptr[row + 1];
+  const int64_t bc_ld = 2 * a.n_edges;
+  for (int c0 = 0; c0 < ncols; c0 += kBatchTile) {
+    const int nt = min(kBatchTile, ncols - c0);
+    double acc[kBatchTile];
+#pragma unroll
+    for (int k = 0; k < kBatchTile; ++k) acc[k] = 0.0;
+    for (int p = p0; p < p1; ++p) {
+      const int idx = a.b_idx[p], ent = a.b_ent[p];
+      const int kind = a.kind[ent];
+      const double v = a.tval[ent];
+      double hc = 0.0, Rh = 0.0;
+      if (kind == kFeMass || kind == kFeSource) {
+        hc = a.cellh ? a.cellh[idx] : fe_cell_h(a.edge_x, idx, a.N);
+        if (kind == kFeMass) Rh = a.edge_R[idx / a.N] * hc;
+      }
+      const int64_t e = idx / a.N;
+#pragma unroll
+      for (int k = 0; k < kBatchTile; ++k)
+        if (k < nt) {
+          const int64_t c = c0 + k;
+          double t;
+          if (kind == kFeSource)
+            t = ((edge_f ? edge_f[c * ef_ld + e] : f_const[c]) * hc) * v;
+          else if (kind == kFeBc)
+            t = edge_bc[c * bc_ld + idx] * v;
+          else if (kind == kFeMass)
+            t = Rh * v;
+          else
+            t = v;
+          acc[k] += t;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kBatchTile; ++k)
+      if (k < nt) out[(c0 + k) * ld + row] = acc[k];
+  }
+}
+
+// k_fe_condense on the listed columns: b_v - C b_i on the vertex rows, the pressure and
+// multiplier rows copied, into the auxiliary workspace's columns; dq_aux (the first chunk of a
+// call, else null): the auxiliary lumped mass (a + b) R h, once -- the resident R alone.
+__global__ __launch_bounds__(kBlock) void k_fe_b_condense(FeCond c, const double* __restrict__ B,
+                                                          int64_t ld, double* __restrict__ Ba,
+                                                          int64_t lda,
+                                                          const int* __restrict__ list, int ncols,
+                                                          double* __restrict__ dq_aux) {
+#pragma clang fp contract(off)
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int N = c.N, km = c.km;
+  const int64_t nv = c.E * (N + 1), np = c.E * N;
+  if (t >= nv + np + c.nl) return;
+  if (t >= nv) {  // a pressure or multiplier row: copied
+    const int64_t src = t < nv + np ? c.pfe[t - nv] : c.lfe[t - nv - np];
+    const int64_t dst = t < nv + np ? c.paux[t - nv] : c.laux[t - nv - np];
+    for (int c0 = 0; c0 < ncols; c0 += kBatchTile) {
+      const int nt = min(kBatchTile, ncols - c0);
+      const FeTile tl = fe_tile(list, c0, nt);
+      double v[kBatchTile];
+#pragma unroll
+      for (int k = 0; k < kBatchTile; ++k)
+        if (k < nt) v[k] = B[tl.col[k] * ld + src];
+#pragma unroll
+      for (int k = 0; k < kBatchTile; ++k)
+        if (k < nt) Ba[tl.col[k] * lda + dst] = v[k];
+    }
+    return;
+  }
+  const int64_t e = t / (N + 1);
+  const int g = (int)(t - e * (N + 1));
+  const int64_t vsrc = c.vfe[t], vdst = c.vaux[t];
+  const int64_t cl = e * N + g - 1, cr = e * N + g;  // the cells on the left (g > 0), right (g < N)
+  if (dq_aux) {
+    const double R = c.edge_R[e];
+    double d = 0.0;
+    if (g > 0) d = c.ab * (R * c.cellh[cl]);
+    if (g < N) d += c.ab * (R * c.cellh[cr]);
+    dq_aux[(int64_t)c.slot[e] * (N + 1) + g] = d;
+  }
+  for (int c0 = 0; c0 < ncols; c0 += kBatchTile) {
+    const int nt = min(kBatchTile, ncols - c0);
+    const FeTile tl = fe_tile(list, c0, nt);
+    double bv[kBatchTile];
+#pragma unroll
+    for (int k = 0; k < kBatchTile; ++k) bv[k] = k < nt ? B[tl.col[k] * ld + vsrc] : 0.0;
+    if (g > 0)  // this vertex is the left cell's right one (C row 1)
+      for (int i = 0; i < km; ++i) {
+        const double ci = c.cst[km + i];
+        const int64_t r = c.ife[cl * km + i];
+#pragma unroll
+        for (int k = 0; k < kBatchTile; ++k)
+          if (k < nt) bv[k] -= ci * B[tl.col[k] * ld + r];
+      }
+    if (g < N)  // the right cell's left vertex (C row 0)
+      for (int i = 0; i < km; ++i) {
+        const double ci = c.cst[i];
+        const int64_t r = c.ife[cr * km + i];
+#pragma unroll
+        for (int k = 0; k < kBatchTile; ++k)
+          if (k < nt) bv[k] -= ci * B[tl.col[k] * ld + r];
+      }
+#pragma unroll
+    for (int k = 0; k < kBatchTile; ++k)
+      if (k < nt) Ba[tl.col[k] * lda + vdst] = bv[k];
+  }
+}
+
+// k_fe_expand on the listed columns: vertex, pressure and multiplier values copied from the
+// auxiliary solution, the interior fluxes x_i = Mii b_i / (R h) - K x_v; accum: added (the
+// refinement pass's update, B the residual).
+__global__ __launch_bounds__(kBlock) void k_fe_b_expand(FeCond c, const double* __restrict__ Xa,
+                                                        int64_t lda, const double* __restrict__ B,
+                                                        double* __restrict__ X, int64_t ld,
+                                                        const int* __restrict__ list, int ncols,
+                                                        int accum) {
+#pragma clang fp contract(off)
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int N = c.N, km = c.km;
+  const int64_t nv = c.E * (N + 1), np = c.E * N, n0 = nv + np + c.nl;
+  if (t >= n0 + np) return;
+  if (t < n0) {  // a vertex, pressure or multiplier row: copied
+    int64_t dst, src;
+    if (t < nv) {
+      dst = c.vfe[t];
+      src = c.vaux[t];
+    } else if (t < nv + np) {
+      dst = c.pfe[t - nv];
+      src = c.paux[t - nv];
+    } else {
+      dst = c.lfe[t - nv - np];
+      src = c.laux[t - nv - np];
+    }
+    for (int c0 = 0; c0 < ncols; c0 += kBatchTile) {
+      const int nt = min(kBatchTile, ncols - c0);
+      const FeTile tl = fe_tile(list, c0, nt);
+      double v[kBatchTile];
+#pragma unroll
+      for (int k = 0; k < kBatchTile; ++k)
+        if (k < nt) {
+          v[k] = Xa[tl.col[k] * lda + src];
+          if (accum) v[k] = X[tl.col[k] * ld + dst] + v[k];
+        }
+#pragma unroll
+      for (int k = 0; k < kBatchTile; ++k)
+        if (k < nt) X[tl.col[k] * ld + dst] = v[k];
+    }
+    return;
+  }
+  const int64_t cell = t - n0, e = cell / N;
+  const int g = (int)(cell - e * N);
+  const double Rh = c.edge_R[e] * c.cellh[cell];
+  const int64_t il = c.vaux[e * (N + 1) + g], ir = c.vaux[e * (N + 1) + g + 1];
+  const double* K = c.cst + 2 * km;
+  const double* Mii = c.cst + 4 * km;
+  for (int c0 = 0; c0 < ncols; c0 += kBatchTile) {
+    const int nt = min(kBatchTile, ncols - c0);
+    const FeTile tl = fe_tile(list, c0, nt);
+    double xl[kBatchTile], xr[kBatchTile];
+#pragma unroll
+    for (int k = 0; k < kBatchTile; ++k) {
+      xl[k] = k < nt ? Xa[tl.col[k] * lda + il] : 0.0;
+      xr[k] = k < nt ? Xa[tl.col[k] * lda + ir] : 0.0;
+    }
+    for (int j = 0; j < km; ++j) {
+      double s[kBatchTile];
+#pragma unroll
+      for (int k = 0; k < kBatchTile; ++k) s[k] = 0.0;
+      for (int i = 0; i < km; ++i) {
+        const double mji = Mii[j * km + i];
+        const int64_t r = c.ife[cell * km + i];
+#pragma unroll
+        for (int k = 0; k < kBatchTile; ++k)
+          if (k < nt) s[k] += mji * B[tl.col[k] * ld + r];
+      }
+      const double k0 = K[2 * j], k1 = K[2 * j + 1];
+      const int64_t r = c.ife[cell * km + j];
+#pragma unroll
+      for (int k = 0; k < kBatchTile; ++k)
+        if (k < nt) {
+          const double xi = s[k] / Rh - k0 * xl[k] - k1 * xr[k];
+          double* xp = X + tl.col[k] * ld + r;
+          *xp = accum ? *xp + xi : xi;
+        }
+    }
+  }
+}
+
+
+// The auxiliary handle can serve batched columns: batch_ok's conditions but for cond_mass
+// (direct_local refuses an auxiliary handle: its CSR is not the system its sweeps invert,
+// which is why the residual here is the (k, 0) handle's).
+bool fe_aux_batch_ok(const nx_network* a) {
+  return a && !a->fe && a->cond_mass && !proc_rank(a) && a->group == nullptr && a->nranks == 1 &&
+         a->n_ghost == 0 && a->pc && a->pc_lds && a->pa.exact && a->E > 0 &&
+         (a->tree_exact || a->n_cyc > 0);
+}
+bool fe_batch_ok(const nx_network* h) {
+  return h && h->fe && !h->fe_cp && h->fe_aux != nullptr && h->fe_k >= 2 && !proc_rank(h) &&
+         h->group == nullptr && h->nranks == 1 && h->n_ghost == 0 && h->solver == 1 &&
+         h->tree_exact && fe_aux_batch_ok(h->fe_aux);
+}
+
+struct FeAuxWs {
+  double *B, *X;   // cap x lda: the condensed rhs and the auxiliary solution
+  BatchCols cols;  // the sweeps' per-column scratch
+  double* cw;      // the cycle correction's w, cap x m
+};
+size_t fe_aux_col_doubles(const nx_network* a) {
+  const int64_t S = std::max<int64_t>(a->pc_slots, 1);
+  return (size_t)(2 * a->n_col + 3 * a->E + 5 * S + 2 * (int64_t)a->n_cyc);
+}
+size_t fe_aux_bytes(const nx_network* a, int cap) {
+  return 8 * fe_aux_col_doubles(a) * (size_t)cap + 64;
+}
+FeAuxWs fe_batch_carve(const nx_network* h, int cap) {
+  const nx_network* a = h->fe_aux;
+  const int64_t E = a->E, S = std::max<int64_t>(a->pc_slots, 1), m = 2 * (int64_t)a->n_cyc;
+  FeAuxWs w{};
+  double* p = static_cast<double*>(h->fe_bws);
+  auto take = [&](int64_t n) {
+    double* q = p;
+    p += n;
+    return q;
+  };
+  w.B = take(cap * a->n_col);
+  w.X = take(cap * a->n_col);
+  w.cols.list = nullptr;
+  w.cols.ld = a->n_col;
+  w.cols.n_chain = E;
+  w.cols.n_slot = S;
+  w.cols.chain_T = take(cap * E);
+  w.cols.chain_It = take(cap * E);
+  w.cols.chain_Ib = take(cap * E);
+  w.cols.slot_D = take(cap * S);
+  w.cols.slot_J = take(cap * S);
+  w.cols.slot_A = take(cap * S);
+  w.cols.slot_B = take(cap * S);
+  w.cols.slot_z = take(cap * S);
+  w.cw = take(cap * m);
+  return w;
+}
+// (the allocated bytes are checked, as in batch_fits: the auxiliary decomposition's slots and
+// cycle chains may have changed since the allocation)
+bool fe_batch_fits(const nx_network* h, int cap) {
+  return batch_fits(h, cap, false, false, false, false) && h->fe_bws != nullptr &&
+         cap <= h->fe_bws_cap && fe_aux_bytes(h->fe_aux, h->fe_bws_cap) <= h->fe_bws_bytes &&
+         h->fe_bws_cap == h->bws_cap;
+}
+void fe_batch_free(nx_network* h) {
+  if (h->bws) (void)hipFree(h->bws);
+  if (h->fe_bws) (void)hipFree(h->fe_bws);
+  h->bws = h->fe_bws = nullptr;
+  h->bws_cap = h->fe_bws_cap = 0;
+  h->bws_bytes = h->fe_bws_bytes = 0;
+}
+
+// batch_workspace's rule for the two parts together: NXHIP_BATCH_CHUNK (read per call) or the
+// largest chunk of <= kBatchChunkMax whose two parts fit kBatchMemShare of the free device
+// memory; a failed allocation of either part halves it down to 1.
+int fe_batch_workspace(nx_network* h, int n_cols, int* chunk_out) {
+  const nx_network* a = h->fe_aux;
+  auto bytes = [&](int cap) {
+    return batch_bytes(h, cap, false, false, false, false) + fe_aux_bytes(a, cap);
+  };
+  int chunk = std::min(n_cols, kBatchChunkMax);
+  const char* e = std::getenv("NXHIP_BATCH_CHUNK");
+  if (e != nullptr && std::atoi(e) > 0) {
+    chunk = std::min(std::min(std::atoi(e), kBatchChunkEnvMax), n_cols);
+  } else if (!fe_batch_fits(h, chunk)) {
+    size_t fr = 0, tot = 0;
+    HIPCALL(hipMemGetInfo(&fr, &tot));
+    const double room = kBatchMemShare * (double)fr;
+    while (chunk > 1 && (double)bytes(chunk) > room) --chunk;
+  }
+  if (!fe_batch_fits(h, chunk)) {
+    HIPCALL(hipStreamSynchronize(h->stream));
+    fe_batch_free(h);
+    int cap = chunk;
+    for (;;) {
+      const bool ok1 = hipMalloc(&h->bws, batch_bytes(h, cap, false, false, false, false)) ==
+                       hipSuccess;
+      const bool ok2 = ok1 && hipMalloc(&h->fe_bws, fe_aux_bytes(a, cap)) == hipSuccess;
+      if (ok2) break;
+      (void)hipGetLastError();
+      if (ok1) (void)hipFree(h->bws);
+      h->bws = h->fe_bws = nullptr;
+      if (cap == 1)
+        return fail(NX_ERR_HIP, "nx_fe_batch_solve: no memory for one column's workspace");
+      cap = std::max(1, cap / 2);
+    }
+    chunk = std::min(chunk, cap);
+    h->bws_cap = h->fe_bws_cap = cap;
+    h->bws_grad = h->bws_ens = h->bws_hvp = h->bws_ecyc = false;
+    h->bws_bytes = batch_bytes(h, cap, false, false, false, false);
+    h->fe_bws_bytes = fe_aux_bytes(a, cap);
+  }
+  *chunk_out = chunk;
+  return NX_OK;
+}
+
+FeCond fe_cond_of(const nx_network* h) {
+  return FeCond{h->edge_x, h->edge_R, h->N, h->fe_k - 1, h->E, h->fe_slot, h->fe_vfe,
+                h->fe_vaux, h->fe_ife, h->fe_pfe, h->fe_paux, h->fe_lfe, h->fe_laux, h->fe_nl,
+                h->fe_cst, h->fe_ab, h->fe_cellh};
+}
+
+// The chunk's inputs to the device and its right-hand sides into ws.B (one launch).
+int fe_batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const double* edge_bc,
+                       const double* edge_f, const double* f_const) {
+  const double* ef = nullptr;
+  int64_t ef_ld = 0;
+  CHECK(batch_inputs(h, ws, c0, nc, edge_bc, edge_f, f_const, &ef, &ef_ld));
+  const FeArgs fa{h->edge_x, h->edge_R, h->edge_bc, h->f, h->edge_f, h->N, h->fe_kind,
+                  h->fe_tval, h->fe_aptr, h->fe_aidx, h->fe_aent, h->fe_bptr, h->fe_bidx,
+                  h->fe_bent, h->nnz, h->n_own, h->val, h->rhs, 0, 1, h->E, h->fe_cellh};
+  hipLaunchKernelGGL(k_fe_b_rhs, dim3(grid_of(h->n_own, kBlock)), dim3(kBlock), 0, h->stream, fa,
+                     nc, ws.bc, ef, ef_ld, ws.fc, ws.B, ws.cols.ld);
+  HIPCALL(hipGetLastError());
+  h->b_launches += 1;
+  return NX_OK;
+}
+
+// The kernel launches of one fe_cyc_build: per column of Z the unit right-hand side, the
+// refinement form's k_cyc_w and the auxiliary sweeps (launch_direct_wc returns after them on
+// an auxiliary handle), then k_cyc_cap_p1 and cyc_invert.
+int fe_cyc_build_launches(const nx_network* a) {
+  const int m = 2 * a->n_cyc;
+  const int sweeps = (a->pc_jobs > 0 ? 2 : 0) + (top_down_on(a) ? 0 : 1);
+  return m * (2 + sweeps) + 1 + (1 + 2 * m + 1);
+}
+
+// X (+)= A^{-1} Bv on nc columns (list: which, device; null: the first nc): condense, the
+// auxiliary sweeps with the cycle correction, expand. The auxiliary handle lends its PcArgs,
+// decomposition and Z / Cinv; its stream is this handle's for the launches. dq (first pass of
+// a call): the auxiliary lumped mass is written by the condensation, and the correction is
+// built after it where the matrix is new (fe_cyc_build reads that lumped mass).
+int fe_batch_apply(nx_network* h, const BatchWs& ws, const FeAuxWs& wa, const int* list, int nc,
+                   const double* Bv, double* Xv, int accum, bool dq) {
+  nx_network* a = h->fe_aux;
+  const FeCond c = fe_cond_of(h);
+  const int64_t np = h->E * (int64_t)h->N, n0 = h->E * (int64_t)(h->N + 1) + np + h->fe_nl;
+  hipLaunchKernelGGL(k_fe_b_condense, dim3(grid_of(n0, kBlock)), dim3(kBlock), 0, h->stream, c,
+                     Bv, ws.cols.ld, wa.B, wa.cols.ld, list, nc, dq ? a->dq : nullptr);
+  HIPCALL(hipGetLastError());
+  h->b_launches += 1;
+  if (dq && a->n_cyc > 0 && a->cyc_version != h->lhs_version) {
+    CHECK(fe_cyc_build(h, a));
+    h->b_launches += fe_cyc_build_launches(a);
+  }
+  {
+    BatchWs aw{};
+    aw.cols = wa.cols;
+    aw.cw = wa.cw;
+    const hipStream_t as = a->stream;
+    const int before = a->b_launches;
+    a->stream = h->stream;
+    a->b_launches = 0;
+    const int rc = batch_sweeps(a, aw, list, nc, wa.B, wa.X);
+    h->b_launches += a->b_launches;
+    a->b_launches = before;
+    a->stream = as;
+    CHECK(rc);
+  }
+  hipLaunchKernelGGL(k_fe_b_expand, dim3(grid_of(n0 + np, kBlock)), dim3(kBlock), 0, h->stream, c,
+                     wa.X, wa.cols.ld, Bv, Xv, ws.cols.ld, list, nc, accum);
+  HIPCALL(hipGetLastError());
+  h->b_launches += 1;
+  return NX_OK;
+}
+
+// batch_solve_cols' per-column policy on the first nc workspace columns of a (k, 0) handle.
+int fe_batch_solve_cols(nx_network* h, const BatchWs& ws, const FeAuxWs& wa, int nc, double rtol,
+                        int32_t maxit, bool first, int32_t* iters, double* relres,
+                        int32_t* converged, std::vector<double>& stats) {
+  const int cap = h->bws_cap;
+  std::vector<int> redo, fall;
+  CHECK(fe_batch_apply(h, ws, wa, nullptr, nc, ws.B, ws.X, 0, first));
+  CHECK(batch_residual(h, ws, ws.X, ws.B, nullptr, nc, stats, cap));
+  for (int c = 0; c < nc; ++c) {
+    const double bb = stats[2 * c + 1];
+    const double r = batch_relres(stats[2 * c], bb);
+    if (iters) iters[c] = 1;
+    if (relres) relres[c] = r;
+    if (converged) converged[c] = (bb == 0.0 || r <= rtol) ? 1 : 0;
+    if (bb > 0.0 && !(r <= rtol)) redo.push_back(c);
+  }
+  if (!redo.empty()) {  // one refinement pass over the failing columns only: x += A^{-1} r
+    const int nr = (int)redo.size();
+    HIPCALL(hipMemcpyAsync(ws.list, redo.data(), sizeof(int) * nr, hipMemcpyHostToDevice,
+                           h->stream));
+    CHECK(fe_batch_apply(h, ws, wa, ws.list, nr, ws.R, ws.X, 1, false));
+    CHECK(batch_residual(h, ws, ws.X, ws.B, ws.list, nr, stats, cap));
+    h->b_refined += nr;
+    for (int c : redo) {
+      const double r = batch_relres(stats[2 * c], stats[2 * c + 1]);
+      if (iters) iters[c] = 2;
+      if (relres) relres[c] = r;
+      if (converged) converged[c] = r <= rtol ? 1 : 0;
+      if (!(r <= rtol)) fall.push_back(c);
+    }
+  }
+  // still above rtol: the single-column route (fe_solve_direct, then MINRES capped at maxit);
+  // where that ends unconverged and no better, the refined column stands (batch_fallback)
+  for (int c : fall) {
+    int32_t it = 0, cv = 0;
+    double r = 0.0;
+    const double have = batch_relres(stats[2 * c], stats[2 * c + 1]);
+    CHECK(batch_fallback(h, ws, ws.B, ws.X, c, rtol, &it, &r, &cv, maxit, have));
+    h->b_fallback += 1;
+    if (iters) iters[c] = it;
+    if (relres) relres[c] = r;
+    if (converged) converged[c] = cv;
+  }
+  return NX_OK;
+}
+
+int fe_batch_state(nx_network* h, const char* who) {
+  if (!fe_batch_ok(h))
+    return fail(NX_ERR_STATE, std::string(who) + ": the batched condensed solve does not apply "
+                                                 "to this handle (nx_fe_batch_supported)");
+  return NX_OK;
+}
+
+}  // namespace
+
+NX_API int nx_fe_batch_supported(nx_network_t* h, int32_t* ok) {
+  if (!h || !ok) return fail(NX_ERR_ARG, "null argument");
+  *ok = fe_batch_ok(h) ? 1 : 0;
+  return NX_OK;
+}
+
+NX_API int nx_fe_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                           const double* edge_f, const double* f_const, double* out) {
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  CHECK(batch_check_args(h, n_cols, edge_bc, out));
+  CHECK(fe_batch_state(h, "nx_fe_batch_rhs"));
+  CHECK(set_device(h));
+  int chunk = 0;
+  CHECK(fe_batch_workspace(h, n_cols, &chunk));
+  const BatchWs ws = batch_carve(h, h->bws_cap);
+  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
+    const int nc = std::min(chunk, n_cols - c0);
+    CHECK(fe_batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
+    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * h->n_own, ws.B, sizeof(double) * h->n_own * nc,
+                           hipMemcpyDeviceToHost, h->stream));
+    HIPCALL(hipStreamSynchronize(h->stream));
+  }
+  return NX_OK;
+}
+
+NX_API int nx_fe_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                             const double* edge_f, const double* f_const, double rtol,
+                             int32_t maxit, int32_t order, double* out, int32_t* iters,
+                             double* relres, int32_t* converged) {
+  // (a flushed assembly is counted in the call's launches, as in nx_batch_solve)
+  const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  CHECK(batch_check_args(h, n_cols, edge_bc, out));
+  if (maxit < 1) return fail(NX_ERR_ARG, "maxit must be >= 1");
+  CHECK(fe_batch_state(h, "nx_fe_batch_solve"));
+  if (!h->have_lhs || h->asm_coef_version != h->coef_version)
+    return fail(NX_ERR_STATE, "nx_fe_batch_solve: assemble the matrix for the resident "
+                              "coefficients first");
+  if (order != 0 && !h->out_idx) return fail(NX_ERR_STATE, "nx_set_output_map first");
+  CHECK(set_device(h));
+  nx_network* a = h->fe_aux;
+  const bool apend = a->pend_lhs || a->pend_rhs;
+  CHECK(flush_assembly(a));
+  if (apend) {  // (the auxiliary handle's own assembly ran on its stream)
+    HIPCALL(hipEventRecord(h->fe_ev[1], a->stream));
+    HIPCALL(hipStreamWaitEvent(h->stream, h->fe_ev[1], 0));
+  }
+  h->b_refined = h->b_fallback = 0;
+  h->b_launches = made_current;
+  int chunk = 0;
+  CHECK(fe_batch_workspace(h, n_cols, &chunk));
+  h->b_chunk = chunk;
+  const BatchWs ws = batch_carve(h, h->bws_cap);
+  const FeAuxWs wa = fe_batch_carve(h, h->fe_bws_cap);
+  const int64_t n = h->n_own, ld = ws.cols.ld;
+  std::vector<double> stats;
+  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
+    const int nc = std::min(chunk, n_cols - c0);
+    CHECK(fe_batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
+    CHECK(fe_batch_solve_cols(h, ws, wa, nc, rtol, maxit, c0 == 0,
+                              iters ? iters + c0 : nullptr, relres ? relres + c0 : nullptr,
+                              converged ? converged + c0 : nullptr, stats));
     const double* src = ws.X;
     if (order != 0) {
       hipLaunchKernelGGL(k_b_gather, dim3(grid_of(n, kBlock), nc), dim3(kBlock), 0, h->stream, ws.X,
@@ -16371,6 +16943,16 @@ NX_API int nx_fe_set_direct(nx_network_t* h, nx_network_t* aux, int32_t k, int64
   if (h->fe_cst) HIPCALL(hipFree(h->fe_cst));
   h->fe_cst = nullptr;
   h->fe_aux = nullptr;
+  // nx_fe_batch_solve's workspace goes with the attachment (both parts: a new auxiliary
+  // handle may size its columns differently)
+  if (h->fe_bws) HIPCALL(hipFree(h->fe_bws));
+  h->fe_bws = nullptr;
+  h->fe_bws_cap = 0;
+  h->fe_bws_bytes = 0;
+  if (h->bws) HIPCALL(hipFree(h->bws));
+  h->bws = nullptr;
+  h->bws_cap = 0;
+  h->bws_bytes = 0;
   if (aux == nullptr) return NX_OK;
   if (k < 2 || k > 16) return fail(NX_ERR_ARG, "flux degree k in 2..16");
   if (!slot || !v_fe || !v_aux || !i_fe || !p_fe || !p_aux || (n_lm > 0 && (!l_fe || !l_aux)) ||

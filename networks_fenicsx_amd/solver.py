@@ -208,6 +208,12 @@ class Solver:
             ``A_g^{-1} U``). Measured against the per-scenario loop: 1.5 to
             37 x faster at 240 to 506 cycle chains and B = 1 to 64, except B = 1 at 506 cycle
             chains, where the one-workgroup factorisation makes it 0.80 x the loop.
+        batch_degrees: let :meth:`solve_many` (and ``terminal_conductance``) take the batched
+            path for flux degree k >= 2 with DG0 pressure (``nx_fe_batch_solve``: the per-cell
+            condensation, the auxiliary tree sweeps and the expansion with a column dimension).
+            ``None`` reads ``NXHIP_FE_BATCH`` (``"1"`` on; off when unset). Off, these degrees
+            take the per-scenario loop, whose columns are bit-equal to single solves; the
+            batched columns agree with them to rounding.
     """
 
     def __init__(
@@ -218,8 +224,12 @@ class Solver:
         kind: str | typing.Sequence[typing.Sequence[str]] | None = None,
         *,
         ensemble_cycles: bool | None = None,
+        batch_degrees: bool | None = None,
     ):
         self._assembler = assembler
+        if batch_degrees is None:
+            batch_degrees = os.environ.get("NXHIP_FE_BATCH", "") == "1"
+        self._fe_batch = bool(batch_degrees)
         if ensemble_cycles is None:
             ensemble_cycles = os.environ.get("NXHIP_ENS_CYCLES", "") == "1"
         self._ens_cycles = bool(ensemble_cycles)
@@ -317,7 +327,9 @@ class Solver:
 
         Where the handle supports it (``nx_batch_supported``: P1/DG0, one rank, the direct
         solve) the scenarios go through ``nx_batch_solve`` in one batched pass
-        (``path == "batched"``). Otherwise -- general degrees, ``ksp_type="minres"``,
+        (``path == "batched"``); with ``batch_degrees`` so do flux degrees k >= 2 with DG0
+        pressure where ``nx_fe_batch_supported`` holds (``nx_fe_batch_solve``: the condensed
+        direct solve with a column dimension). Otherwise -- general degrees, ``ksp_type="minres"``,
         ``pc_type="none"``, the lumped mass, the global-memory sweeps, or ``NXHIP_BATCH=0`` --
         the per-scenario loop runs (``"sequential"``): the rhs coefficients alone are set (R
         is never uploaded again), then rhs assembly, solve, gather; afterwards the coefficients
@@ -344,8 +356,17 @@ class Solver:
         want = os.environ.get("NXHIP_BATCH", "")
         worth = want == "1" or not (B == 1 and h.n_rows > BATCH_SINGLE_MAX_ROWS)
         batched = want != "0" and worth and h.batch_supported()
+        # (k, 0), k >= 2, with batch_degrees: the condensed direct solve's batched pass
+        fe_batched = (not batched and self._fe_batch and want != "0" and worth and self._direct
+                      and len(asm.degrees) == 2 and asm.degrees[0] >= 2 and asm.degrees[1] == 0
+                      and h.fe_batch_supported())
         if batched:
             x, it, rr, conv = h.batch_solve(edge_bc, edge_f, f_const, self._rtol, blocks=True)
+            info = h.batch_info()
+        elif fe_batched:
+            batched = True
+            x, it, rr, conv = h.fe_batch_solve(edge_bc, edge_f, f_const, self._rtol,
+                                               self._maxit, blocks=True)
             info = h.batch_info()
         else:
             x = h.batch_output(B)  # page-locked and reused, as the batched path's
