@@ -34,6 +34,7 @@
 #include <cstring>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nxhip.h"
@@ -8187,6 +8188,18 @@ struct HostComm {
   std::string name;
 };
 
+// What a batched workspace holds beside the plain solve's columns (batch_layout): the
+// gradient's adjoint columns and outputs, an ensemble's lumped mass and R per column, the
+// Hessian-vector product's columns, an ensemble's cycle correction per scenario. A part stays
+// once a call has asked for it.
+struct BatchParts {
+  enum : unsigned { kGrad = 1, kEns = 2, kHvp = 4, kEcyc = 8 };
+  unsigned bits = 0;
+  bool has(unsigned part) const { return (bits & part) != 0; }
+  bool contains(BatchParts o) const { return (bits & o.bits) == o.bits; }
+  BatchParts operator|(BatchParts o) const { return BatchParts{bits | o.bits}; }
+};
+
 struct nx_network {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -8484,26 +8497,22 @@ struct nx_network {
   // residual and the sweep's values (2 cp_nn each)
   double *cpc_se0 = nullptr, *cpc_rho = nullptr, *cpc_xd = nullptr;
   // nx_batch_solve: the column workspace (one allocation for bws_cap columns, carved by
-  // batch_carve; allocated on first use, freed in nx_destroy) and the last call's figures
+  // batch_carve; allocated on first use, freed in nx_destroy), the parts it carries beside the
+  // plain solve's (what the gradient, ensemble and Hessian-vector calls have asked for so far),
+  // and the last call's figures
   void* bws = nullptr;
   int bws_cap = 0;
   size_t bws_bytes = 0;
+  BatchParts bws_parts;
   int b_launches = 0, b_refined = 0, b_fallback = 0, b_chunk = 0;
-  // nx_batch_gradient: whether the workspace carries the adjoint columns (kept once a
-  // gradient call asked for them), and the observation list's device copy (rows | w | data)
-  bool bws_grad = false;
-  // nx_ensemble_solve / nx_ensemble_gradient: whether it carries every column's own lumped
-  // mass and R (kept once an ensemble call has asked for them)
-  bool bws_ens = false;
-  bool bws_hvp = false;  // nx_batch_hvp asked: the tangent / second adjoint columns, direction, outputs
   // nx_set_ensemble_cycles: the ensemble calls take this handle's graph with cycles (a cycle
-  // correction per scenario); whether the workspace carries its part; the last ensemble call's
-  // unit solves and the factor kernel's storage (0 none, 1 LDS, 2 global memory); the current
-  // chunk's failed factorisations (host copy of the flags)
+  // correction per scenario); the last ensemble call's unit solves and the factor kernel's
+  // storage (0 none, 1 LDS, 2 global memory); the current chunk's failed factorisations (host
+  // copy of the flags)
   bool ens_cyc = false;
-  bool bws_ecyc = false;
   int ecyc_unit = 0, ecyc_storage = 0;
   std::vector<int> ecyc_failed;
+  // nx_batch_gradient: the observation list's device copy (rows | w | data)
   void* gobs = nullptr;
   size_t gobs_bytes = 0;
   // nx_stash_solution: x | tmp | rhs (3 n_col) and the published state (a BatchSaved, malloc'ed)
@@ -8517,7 +8526,7 @@ struct nx_network {
   bool cpc_last = false;  // the last fe_cp_solve applied the correction
   // nx_fe_batch_solve on a (k, 0) handle: bws holds this handle's columns; fe_bws the
   // auxiliary system's (condensed rhs, solution, the sweeps' scratch, the cycle correction's
-  // w; fe_batch_carve), owned here: freed in nx_destroy and when nx_fe_set_direct detaches
+  // w; fe_aux_layout), owned here: freed in nx_destroy and when nx_fe_set_direct detaches
   void* fe_bws = nullptr;
   int fe_bws_cap = 0;
   size_t fe_bws_bytes = 0;
@@ -13615,7 +13624,8 @@ constexpr int kBatchChunkMax = 64;     // default chunk: columns per pass
 constexpr int kBatchChunkEnvMax = 4096;  // NXHIP_BATCH_CHUNK is clamped to this (grid.y)
 constexpr double kBatchMemShare = 0.25;  // of the free device memory, for the workspace
 
-// The workspace of `cap` columns, carved from one allocation (doubles first, then ints).
+// The workspace of `cap` columns, carved from one allocation (doubles first, then ints;
+// batch_layout).
 struct BatchWs {
   double *B, *X, *R, *D;  // cap x ld each: rhs, solution, residual, correction / output
   BatchCols cols;         // the sweeps' per-column scratch
@@ -13624,103 +13634,111 @@ struct BatchWs {
   double* cw;             // cycle correction: w (cap x m)
   double* save;           // the handle's x | tmp | rhs while a build of the cycle correction
                           // or a fallback solve borrows them (3 n_col)
-  double *C, *L;          // nx_batch_gradient (bws_grad): adjoint rhs and solution, cap x ld
+  double *C, *L;          // nx_batch_gradient (kGrad): adjoint rhs and solution, cap x ld
   double *gJ, *gR, *gf, *gbc;  // and its outputs: cap, cap x E, cap x E, cap x 2 E
-  double *edq, *eR;       // ensembles (bws_ens): the column's lumped mass and R, cap x E (N + 1), cap x E
-  double *Xd, *Ld;        // nx_batch_hvp (bws_hvp): tangent and second-order adjoint, cap x ld
+  double *edq, *eR;       // ensembles (kEns): the column's lumped mass and R, cap x E (N + 1), cap x E
+  double *Xd, *Ld;        // nx_batch_hvp (kHvp): tangent and second-order adjoint, cap x ld
   double *vR;             // the direction's v_R, cap x E (v_bc / v_f reuse bc / ef)
   double *HR, *Hf, *Hbc;  // and its outputs: cap x E, cap x E, cap x 2 E
-  // ensembles on a graph with cycles (bws_ecyc): K_j and its factors (cap x m^2), the patched
+  // ensembles on a graph with cycles (kEcyc): K_j and its factors (cap x m^2), the patched
   // entries of the input column (cap x m), the pivots (cap x m), the failure flags and the
   // unit solves' column -> scenario map (cap each)
   double *eK, *esave;
   int *epiv, *eflag, *emap;
   int* list;              // cap
   int nblk;
+  size_t bytes;           // of the whole layout
 };
 
-// The per-column part of an ensemble's cycle correction (nothing above kEnsCycMax: such a
-// handle takes no ensemble).
-int64_t batch_ecyc_doubles(const nx_network* h, bool ecyc) {
-  const int64_t m = 2 * (int64_t)h->n_cyc;
-  return ecyc && h->n_cyc > 0 && h->n_cyc <= kEnsCycMax ? m * m + 2 * m + 2 : 0;
+// One walk over a workspace's fields, in two modes: counting (base null: the pointers it
+// hands out are null and only `off` matters) and carving from a base pointer.
+struct WsWalk {
+  double* base;
+  int64_t off = 0;  // doubles so far
+  double* take(int64_t n) {
+    double* q = base ? base + off : nullptr;
+    off += n;
+    return q;
+  }
+  int* take_int(int64_t n) { return reinterpret_cast<int*>(take(n)); }  // (a double per int)
+};
+
+// The sweeps' per-column scratch of `cap` columns: three chain arrays, five slot arrays.
+BatchCols batch_cols_walk(WsWalk& k, int cap, int64_t ld, int64_t E, int64_t S) {
+  BatchCols c{};
+  c.list = nullptr;
+  c.ld = ld;
+  c.n_chain = E;
+  c.n_slot = S;
+  c.chain_T = k.take(cap * E);
+  c.chain_It = k.take(cap * E);
+  c.chain_Ib = k.take(cap * E);
+  c.slot_D = k.take(cap * S);
+  c.slot_J = k.take(cap * S);
+  c.slot_A = k.take(cap * S);
+  c.slot_B = k.take(cap * S);
+  c.slot_z = k.take(cap * S);
+  return c;
 }
-size_t batch_col_doubles(const nx_network* h, bool grad, bool ens, bool hvp, bool ecyc) {
-  const int64_t E = h->E, S = std::max<int64_t>(h->pc_slots, 1), m = 2 * (int64_t)h->n_cyc;
-  const int nblk = grid_of(h->n_own, kBlock);
-  const int64_t g = grad ? 2 * h->n_col + 4 * E + 1 : 0;  // X stays resident beside C and L
-  const int64_t en = ens ? E * (int64_t)(h->N + 1) + E : 0;  // the column's own dq and R
-  const int64_t hv = hvp ? 2 * h->n_col + 5 * E : 0;  // Xd, Ld; v_R, HR, Hf, Hbc
-  return (size_t)(4 * h->n_col + 3 * E + 5 * S + 3 * E + 1 + 2 * nblk + 2 + m + g + en + hv +
-                  batch_ecyc_doubles(h, ecyc));
-}
-size_t batch_bytes(const nx_network* h, int cap, bool grad, bool ens, bool hvp, bool ecyc) {
-  return 8 * (batch_col_doubles(h, grad, ens, hvp, ecyc) * (size_t)cap + (size_t)(3 * h->n_col)) +
-         sizeof(int) * (size_t)cap + 64;
-}
-BatchWs batch_carve(const nx_network* h, int cap) {
+
+// The workspace's layout, written once: every field of `cap` columns with `parts`, in order
+// (a part that is added later goes behind what the earlier calls use, so that keeps its place;
+// the ints last). base null: the size alone (ws.bytes), every pointer null.
+BatchWs batch_layout(const nx_network* h, int cap, BatchParts parts, void* base) {
   const int64_t E = h->E, S = std::max<int64_t>(h->pc_slots, 1), m = 2 * (int64_t)h->n_cyc;
   const int64_t ld = h->n_col;
   BatchWs w{};
-  double* p = static_cast<double*>(h->bws);
-  auto take = [&](int64_t n) {
-    double* q = p;
-    p += n;
-    return q;
-  };
+  WsWalk k{static_cast<double*>(base)};
   w.nblk = grid_of(h->n_own, kBlock);
-  w.B = take(cap * ld);
-  w.X = take(cap * ld);
-  w.R = take(cap * ld);
-  w.D = take(cap * ld);
-  w.cols.list = nullptr;
-  w.cols.ld = ld;
-  w.cols.n_chain = E;
-  w.cols.n_slot = S;
-  w.cols.chain_T = take(cap * E);
-  w.cols.chain_It = take(cap * E);
-  w.cols.chain_Ib = take(cap * E);
-  w.cols.slot_D = take(cap * S);
-  w.cols.slot_J = take(cap * S);
-  w.cols.slot_A = take(cap * S);
-  w.cols.slot_B = take(cap * S);
-  w.cols.slot_z = take(cap * S);
-  w.bc = take(cap * 2 * E);
-  w.ef = take(cap * E);
-  w.fc = take(cap);
-  w.part = take((int64_t)cap * 2 * w.nblk);
-  w.stats = take(cap * 2);
-  w.cw = take(cap * m);
-  w.save = take(3 * ld);
-  if (h->bws_grad) {
-    w.C = take(cap * ld);
-    w.L = take(cap * ld);
-    w.gJ = take(cap);
-    w.gR = take(cap * E);
-    w.gf = take(cap * E);
-    w.gbc = take(cap * 2 * E);
+  w.B = k.take(cap * ld);
+  w.X = k.take(cap * ld);
+  w.R = k.take(cap * ld);
+  w.D = k.take(cap * ld);
+  w.cols = batch_cols_walk(k, cap, ld, E, S);
+  w.bc = k.take(cap * 2 * E);
+  w.ef = k.take(cap * E);
+  w.fc = k.take(cap);
+  w.part = k.take((int64_t)cap * 2 * w.nblk);
+  w.stats = k.take(cap * 2);
+  w.cw = k.take(cap * m);
+  w.save = k.take(3 * ld);
+  if (parts.has(BatchParts::kGrad)) {  // (X stays resident beside C and L)
+    w.C = k.take(cap * ld);
+    w.L = k.take(cap * ld);
+    w.gJ = k.take(cap);
+    w.gR = k.take(cap * E);
+    w.gf = k.take(cap * E);
+    w.gbc = k.take(cap * 2 * E);
   }
-  if (h->bws_ens) {
-    w.edq = take(cap * E * (int64_t)(h->N + 1));
-    w.eR = take(cap * E);
+  if (parts.has(BatchParts::kEns)) {
+    w.edq = k.take(cap * E * (int64_t)(h->N + 1));
+    w.eR = k.take(cap * E);
   }
-  if (h->bws_hvp) {  // (last: what came before keeps its place)
-    w.Xd = take(cap * ld);
-    w.Ld = take(cap * ld);
-    w.vR = take(cap * E);
-    w.HR = take(cap * E);
-    w.Hf = take(cap * E);
-    w.Hbc = take(cap * 2 * E);
+  if (parts.has(BatchParts::kHvp)) {
+    w.Xd = k.take(cap * ld);
+    w.Ld = k.take(cap * ld);
+    w.vR = k.take(cap * E);
+    w.HR = k.take(cap * E);
+    w.Hf = k.take(cap * E);
+    w.Hbc = k.take(cap * 2 * E);
   }
-  if (batch_ecyc_doubles(h, h->bws_ecyc) > 0) {  // (behind everything the earlier calls use)
-    w.eK = take(cap * m * m);
-    w.esave = take(cap * m);
-    w.epiv = reinterpret_cast<int*>(take(cap * m));
-    w.eflag = reinterpret_cast<int*>(take(cap));
-    w.emap = reinterpret_cast<int*>(take(cap));
+  // (nothing above kEnsCycMax: such a handle takes no ensemble)
+  if (parts.has(BatchParts::kEcyc) && h->n_cyc > 0 && h->n_cyc <= kEnsCycMax) {
+    w.eK = k.take(cap * m * m);
+    w.esave = k.take(cap * m);
+    w.epiv = k.take_int(cap * m);
+    w.eflag = k.take_int(cap);
+    w.emap = k.take_int(cap);
   }
-  w.list = reinterpret_cast<int*>(p);
+  w.list = reinterpret_cast<int*>(k.take(0));
+  w.bytes = 8 * (size_t)k.off + sizeof(int) * (size_t)cap + 64;
   return w;
+}
+size_t batch_bytes(const nx_network* h, int cap, BatchParts parts) {
+  return batch_layout(h, cap, parts, nullptr).bytes;
+}
+BatchWs batch_carve(const nx_network* h) {
+  return batch_layout(h, h->bws_cap, h->bws_parts, h->bws);
 }
 
 // One rank, P1/DG0, the direct solve's LDS sweeps exact on this handle (a forest, or the
@@ -13734,11 +13752,9 @@ bool batch_ok(const nx_network* h) {
 // size follows the decomposition's slots and the cycle chains, which nx_set_preconditioner
 // and nx_set_cycles change after a workspace was allocated (nx_batch_rhs is legal before
 // either), so the allocated bytes are checked, not the column count alone.
-bool batch_fits(const nx_network* h, int chunk, bool grad, bool ens, bool hvp, bool ecyc) {
-  return h->bws != nullptr && chunk <= h->bws_cap && (!grad || h->bws_grad) &&
-         (!ens || h->bws_ens) && (!hvp || h->bws_hvp) && (!ecyc || h->bws_ecyc) &&
-         batch_bytes(h, h->bws_cap, h->bws_grad, h->bws_ens, h->bws_hvp, h->bws_ecyc) <=
-             h->bws_bytes;
+bool batch_fits(const nx_network* h, int chunk, BatchParts parts) {
+  return h->bws != nullptr && chunk <= h->bws_cap && h->bws_parts.contains(parts) &&
+         batch_bytes(h, h->bws_cap, h->bws_parts) <= h->bws_bytes;
 }
 
 // Ensembles take this handle's graph with cycles (nx_set_ensemble_cycles): a correction per
@@ -13747,54 +13763,74 @@ bool ens_cyc_on(const nx_network* h) {
   return h->ens_cyc && h->n_cyc > 0 && h->n_cyc <= kEnsCycMax;
 }
 
-// The chunk size of this call and a workspace that holds it: NXHIP_BATCH_CHUNK (read per
-// call) or the largest of <= kBatchChunkMax whose workspace fits kBatchMemShare of the free
-// device memory; a failed allocation halves it down to 1.
-int batch_workspace(nx_network* h, int n_cols, int* chunk_out, bool grad = false,
-                    bool ens = false, bool hvp = false) {
-  hvp = hvp || h->bws_hvp;
-  grad = grad || hvp || h->bws_grad;  // (the Hessian-vector product implies the gradient's part)
-  // an ensemble with a cycle correction per scenario: its nc m unit solves go in passes of as
-  // many columns as the workspace holds, so it holds kBatchChunkMax even for fewer scenarios
-  const bool wide = ens && ens_cyc_on(h);
-  const bool ecyc = wide || h->bws_ecyc;
-  ens = ens || h->bws_ens;
+// The chunk size of a call and a workspace that holds it: NXHIP_BATCH_CHUNK (read per call)
+// or the largest of <= kBatchChunkMax whose workspace fits kBatchMemShare of the free device
+// memory; a failed allocation halves it down to 1. wide: the workspace holds kBatchChunkMax
+// columns even for fewer scenarios. The workspace is the caller's: fits(cap) -- what is
+// allocated serves cap columns; bytes(cap); release(); alloc(cap) -- true when every part was
+// allocated and recorded on the handle (a part it did allocate is freed again otherwise).
+template <class Fits, class Bytes, class Release, class Alloc>
+int batch_chunk_rule(nx_network* h, int n_cols, bool wide, const char* who, Fits fits,
+                     Bytes bytes, Release release, Alloc alloc, int* chunk_out) {
   int chunk = std::min(n_cols, kBatchChunkMax);
   int cap = wide ? kBatchChunkMax : chunk;  // the workspace's columns (>= chunk)
   const char* e = std::getenv("NXHIP_BATCH_CHUNK");
   if (e != nullptr && std::atoi(e) > 0) {
     chunk = std::min(std::min(std::atoi(e), kBatchChunkEnvMax), n_cols);
     cap = wide ? std::max(chunk, kBatchChunkMax) : chunk;
-  } else if (!batch_fits(h, cap, grad, ens, hvp, ecyc)) {
+  } else if (!fits(cap)) {
     size_t fr = 0, tot = 0;
     HIPCALL(hipMemGetInfo(&fr, &tot));
     const double room = kBatchMemShare * (double)fr;
-    while (cap > 1 && (double)batch_bytes(h, cap, grad, ens, hvp, ecyc) > room) --cap;
+    while (cap > 1 && (double)bytes(cap) > room) --cap;
     chunk = std::min(chunk, cap);
   }
-  if (!batch_fits(h, cap, grad, ens, hvp, ecyc)) {
+  if (!fits(cap)) {
     HIPCALL(hipStreamSynchronize(h->stream));
-    if (h->bws) (void)hipFree(h->bws);
-    h->bws = nullptr;
-    h->bws_cap = 0;
-    h->bws_bytes = 0;
-    for (;;) {
-      if (hipMalloc(&h->bws, batch_bytes(h, cap, grad, ens, hvp, ecyc)) == hipSuccess) break;
+    release();
+    while (!alloc(cap)) {
       (void)hipGetLastError();
-      h->bws = nullptr;
-      if (cap == 1) return fail(NX_ERR_HIP, "nx_batch_solve: no memory for one column's workspace");
+      if (cap == 1)
+        return fail(NX_ERR_HIP, std::string(who) + ": no memory for one column's workspace");
       cap = std::max(1, cap / 2);
     }
     chunk = std::min(chunk, cap);
-    h->bws_cap = cap;
-    h->bws_grad = grad;
-    h->bws_ens = ens;
-    h->bws_hvp = hvp;
-    h->bws_ecyc = ecyc;
-    h->bws_bytes = batch_bytes(h, cap, grad, ens, hvp, ecyc);
   }
   *chunk_out = chunk;
   return NX_OK;
+}
+
+void batch_free(nx_network* h) {
+  if (h->bws) (void)hipFree(h->bws);
+  h->bws = nullptr;
+  h->bws_cap = 0;
+  h->bws_bytes = 0;
+}
+bool batch_alloc(nx_network* h, int cap, BatchParts parts) {
+  const size_t bytes = batch_bytes(h, cap, parts);
+  if (hipMalloc(&h->bws, bytes) != hipSuccess) {
+    h->bws = nullptr;
+    return false;
+  }
+  h->bws_cap = cap;
+  h->bws_parts = parts;
+  h->bws_bytes = bytes;
+  return true;
+}
+
+// A P1/DG0 handle's workspace for this call: what the call asks for beside what the workspace
+// already carries (the Hessian-vector product implies the gradient's part). An ensemble with a
+// cycle correction per scenario: its nc m unit solves go in passes of as many columns as the
+// workspace holds, so it holds kBatchChunkMax even for fewer scenarios.
+int batch_workspace(nx_network* h, int n_cols, int* chunk_out, BatchParts ask = BatchParts{}) {
+  const bool wide = ask.has(BatchParts::kEns) && ens_cyc_on(h);
+  if (ask.has(BatchParts::kHvp)) ask.bits |= BatchParts::kGrad;
+  if (wide) ask.bits |= BatchParts::kEcyc;
+  const BatchParts parts = ask | h->bws_parts;
+  return batch_chunk_rule(
+      h, n_cols, wide, "nx_batch_solve", [&](int cap) { return batch_fits(h, cap, parts); },
+      [&](int cap) { return batch_bytes(h, cap, parts); }, [&]() { batch_free(h); },
+      [&](int cap) { return batch_alloc(h, cap, parts); }, chunk_out);
 }
 
 // An ensemble's columns (nx_ensemble_solve): every workspace column solves its own matrix
@@ -13876,32 +13912,50 @@ int batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const doub
   return NX_OK;
 }
 
+// What the sweeps take: the handle whose decomposition (PcArgs, jobs, cycle rows, Z / Cinv)
+// they run on, read only; the stream and the launch counter of the call (another handle's where
+// an auxiliary decomposition is lent: fe_batch_apply); the per-column scratch; the cycle
+// correction's scratch (w; an ensemble's factors, pivots, flags and patched entries).
+struct SweepCtx {
+  const nx_network* d;
+  hipStream_t stream;
+  int* launches;
+  BatchCols cols;
+  double* cw;
+  double *eK, *esave;
+  int *epiv, *eflag;
+};
+SweepCtx sweep_ctx(nx_network* h, const BatchWs& ws) {
+  return SweepCtx{h, h->stream, &h->b_launches, ws.cols, ws.cw, ws.eK, ws.esave, ws.epiv, ws.eflag};
+}
+
 // out = A^{-1} in on nc columns (list: which, device; null: the first nc): the up, top and
 // down sweeps, then the cycle correction.
 template <int W, int CPL>
-void batch_sweeps_wc(nx_network* h, const BatchWs& ws, const int* list, int nc, const double* in,
-                     double* out, const BatchEns* ens) {
+void batch_sweeps_wc(const SweepCtx& sc, const int* list, int nc, const double* in, double* out,
+                     const BatchEns* ens) {
+  const nx_network* h = sc.d;
   PcArgs pa = h->pa;
   pa.accum = 0;
   pa.fres = 0;
   pa.topdown = 0;
-  BatchCols bc = ws.cols;
+  BatchCols bc = sc.cols;
   bc.list = list;
   bc.dq = ens ? ens->dq : nullptr;
   bc.n_dq = ens ? ens->n_dq : 0;
   bc.dq_map = ens ? ens->map : nullptr;
   auto tree = [&]() {  // out = A_g^{-1} in
     if (h->pc_jobs > 0) {
-      hipLaunchKernelGGL((k_b_up<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, h->stream,
+      hipLaunchKernelGGL((k_b_up<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, sc.stream,
                          pa, bc, in);
-      h->b_launches += 1;
+      *sc.launches += 1;
     }
-    hipLaunchKernelGGL(k_b_top, dim3(nc), dim3(kTopThreads), 0, h->stream, pa, bc, in, out);
-    h->b_launches += 1;
+    hipLaunchKernelGGL(k_b_top, dim3(nc), dim3(kTopThreads), 0, sc.stream, pa, bc, in, out);
+    *sc.launches += 1;
     if (h->pc_jobs > 0) {
-      hipLaunchKernelGGL((k_b_down<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, h->stream,
+      hipLaunchKernelGGL((k_b_down<W, CPL>), dim3(h->pc_jobs, nc), dim3(kPcThreads), 0, sc.stream,
                          pa, bc, in, out);
-      h->b_launches += 1;
+      *sc.launches += 1;
     }
   };
   tree();
@@ -13911,35 +13965,35 @@ void batch_sweeps_wc(nx_network* h, const BatchWs& ws, const int* list, int nc, 
     if (ens->raw) return;
     const int m = 2 * h->n_cyc;
     double* inw = const_cast<double*>(in);
-    hipLaunchKernelGGL(k_e_cyc_w, dim3(nc), dim3(256), sizeof(double) * m, h->stream, out, inw,
-                       bc.ld, list, h->d_cyc_rows, m, ws.eK, ws.epiv, ws.eflag, ws.esave);
-    h->b_launches += 1;
+    hipLaunchKernelGGL(k_e_cyc_w, dim3(nc), dim3(256), sizeof(double) * m, sc.stream, out, inw,
+                       bc.ld, list, h->d_cyc_rows, m, sc.eK, sc.epiv, sc.eflag, sc.esave);
+    *sc.launches += 1;
     tree();
-    hipLaunchKernelGGL(k_e_cyc_restore, dim3(grid_of(m, 256), nc), dim3(256), 0, h->stream, inw,
-                       bc.ld, list, h->d_cyc_rows, m, ws.esave);
-    h->b_launches += 1;
+    hipLaunchKernelGGL(k_e_cyc_restore, dim3(grid_of(m, 256), nc), dim3(256), 0, sc.stream, inw,
+                       bc.ld, list, h->d_cyc_rows, m, sc.esave);
+    *sc.launches += 1;
   } else if (h->n_cyc > 0) {
     const int m = 2 * h->n_cyc;
     hipLaunchKernelGGL(k_b_cyc_w, dim3(grid_of(m, 256), nc), dim3(256), sizeof(double) * m,
-                       h->stream, out, bc.ld, list, h->d_cyc_rows, m, h->cyc_cinv, ws.cw);
+                       sc.stream, out, bc.ld, list, h->d_cyc_rows, m, h->cyc_cinv, sc.cw);
     hipLaunchKernelGGL(k_b_cyc_fix, dim3(grid_of(h->n_own, kBlock), nc), dim3(kBlock), 0,
-                       h->stream, out, bc.ld, list, h->cyc_z, h->n_col, ws.cw, m, h->n_own);
-    h->b_launches += 2;
+                       sc.stream, out, bc.ld, list, h->cyc_z, h->n_col, sc.cw, m, h->n_own);
+    *sc.launches += 2;
   }
 }
-int batch_sweeps(nx_network* h, const BatchWs& ws, const int* list, int nc, const double* in,
-                 double* out, const BatchEns* ens = nullptr) {
-  switch (h->pc_variant) {
-    case 0: batch_sweeps_wc<16, 1>(h, ws, list, nc, in, out, ens); break;
-    case 1: batch_sweeps_wc<16, 2>(h, ws, list, nc, in, out, ens); break;
-    case 2: batch_sweeps_wc<16, 4>(h, ws, list, nc, in, out, ens); break;
-    case 3: batch_sweeps_wc<64, 2>(h, ws, list, nc, in, out, ens); break;
-    case 5: batch_sweeps_wc<8, 2>(h, ws, list, nc, in, out, ens); break;
-    case 6: batch_sweeps_wc<4, 4>(h, ws, list, nc, in, out, ens); break;
-    case 7: batch_sweeps_wc<8, 4>(h, ws, list, nc, in, out, ens); break;
-    case 8: batch_sweeps_wc<64, 8>(h, ws, list, nc, in, out, ens); break;
-    case 9: batch_sweeps_wc<64, 16>(h, ws, list, nc, in, out, ens); break;
-    default: batch_sweeps_wc<64, 4>(h, ws, list, nc, in, out, ens); break;
+int batch_sweeps(const SweepCtx& sc, const int* list, int nc, const double* in, double* out,
+                 const BatchEns* ens = nullptr) {
+  switch (sc.d->pc_variant) {
+    case 0: batch_sweeps_wc<16, 1>(sc, list, nc, in, out, ens); break;
+    case 1: batch_sweeps_wc<16, 2>(sc, list, nc, in, out, ens); break;
+    case 2: batch_sweeps_wc<16, 4>(sc, list, nc, in, out, ens); break;
+    case 3: batch_sweeps_wc<64, 2>(sc, list, nc, in, out, ens); break;
+    case 5: batch_sweeps_wc<8, 2>(sc, list, nc, in, out, ens); break;
+    case 6: batch_sweeps_wc<4, 4>(sc, list, nc, in, out, ens); break;
+    case 7: batch_sweeps_wc<8, 4>(sc, list, nc, in, out, ens); break;
+    case 8: batch_sweeps_wc<64, 8>(sc, list, nc, in, out, ens); break;
+    case 9: batch_sweeps_wc<64, 16>(sc, list, nc, in, out, ens); break;
+    default: batch_sweeps_wc<64, 4>(sc, list, nc, in, out, ens); break;
   }
   HIPCALL(hipGetLastError());
   return NX_OK;
@@ -13964,7 +14018,7 @@ int batch_ens_cyc_build(nx_network* h, const BatchWs& ws, int nc) {
     hipLaunchKernelGGL(k_e_cyc_unit, dim3(grid_of(ncp, 256)), dim3(256), 0, h->stream, ws.R, ld,
                        h->d_cyc_rows, m, g0, ncp, ws.emap);
     h->b_launches += 1;
-    CHECK(batch_sweeps(h, ws, nullptr, ncp, ws.R, ws.D, &be));
+    CHECK(batch_sweeps(sweep_ctx(h, ws), nullptr, ncp, ws.R, ws.D, &be));
     hipLaunchKernelGGL(k_e_cyc_extract, dim3(grid_of(m, 256), ncp), dim3(256), 0, h->stream, ws.D,
                        ld, h->d_cyc_rows, m, g0, ws.eK);
     h->b_launches += 1;
@@ -14084,30 +14138,53 @@ int batch_fallback(nx_network* h, const BatchWs& ws, const double* Bv, double* X
   return rc;
 }
 
-// The per-column policy on the first nc workspace columns, Xv = A^{-1} Bv: the sweeps, the
+// A call's status arrays (any may be null), from some column on.
+struct BatchStatus {
+  int32_t* iters;
+  double* relres;
+  int32_t* converged;
+  BatchStatus at(int64_t c0) const {
+    return BatchStatus{iters ? iters + c0 : nullptr, relres ? relres + c0 : nullptr,
+                       converged ? converged + c0 : nullptr};
+  }
+  void set(int c, int32_t it, double rr, int32_t cv) const {
+    if (iters) iters[c] = it;
+    if (relres) relres[c] = rr;
+    if (converged) converged[c] = cv;
+  }
+};
+
+// What a column still above rtol after the refinement pass gets: nothing (an ensemble: the
+// single-column path solves the handle's matrix, not the column's), the single-column path, or
+// that path capped at maxit, the refined column kept where it ends unconverged and no better.
+struct BatchFallback {
+  enum Mode { kNone, kPlain, kKeep } mode;
+  int32_t maxit;
+};
+
+// The per-column policy on the first nc workspace columns, Xv = A^{-1} Bv: the operator, the
 // true residual, one refinement pass over the list of columns above rtol, the single-column
-// path for a column still above it. iters / relres / converged: this chunk's entries (any
-// may be null). stats (host) keeps ||r||^2 | ||b||^2 per column: a column with ||b|| = 0 is
-// reported converged and its caller writes the exact zero. ens: every column against its own
-// matrix, and no single-column path (BatchEns): such a column stays converged = 0, 2 iterations.
+// path for a column still above it (fb). The operator is the caller's: solve(nc) -- Xv =
+// A^{-1} Bv on the first nc columns; refine(list, nr) -- Xv += A^{-1} ws.R on the listed ones.
+// st: this chunk's status entries. stats (host) keeps ||r||^2 | ||b||^2 per column: a column
+// with ||b|| = 0 is reported converged and its caller writes the exact zero. ens: the residual
+// against every column's own matrix (BatchEns).
+template <class Solve, class Refine>
 int batch_solve_cols(nx_network* h, const BatchWs& ws, int nc, const double* Bv, double* Xv,
-                     double rtol, int32_t* iters, double* relres, int32_t* converged,
-                     std::vector<double>& stats, const BatchEns* ens = nullptr) {
+                     double rtol, BatchStatus st, std::vector<double>& stats, Solve solve,
+                     Refine refine, BatchFallback fb, const BatchEns* ens = nullptr) {
   const int cap = h->bws_cap;
-  const int64_t n = h->n_own, ld = ws.cols.ld;
   std::vector<int> redo, fall;
-  CHECK(batch_sweeps(h, ws, nullptr, nc, Bv, Xv, ens));
+  CHECK(solve(nc));
   CHECK(batch_residual(h, ws, Xv, Bv, nullptr, nc, stats, cap, ens));
   for (int c = 0; c < nc; ++c) {
     const double rr = stats[2 * c], bb = stats[2 * c + 1];
     const double r = batch_relres(rr, bb);
-    if (iters) iters[c] = 1;
-    if (relres) relres[c] = r;
-    if (converged) converged[c] = (bb == 0.0 || r <= rtol) ? 1 : 0;
+    st.set(c, 1, r, (bb == 0.0 || r <= rtol) ? 1 : 0);
     if (ens && h->n_cyc > 0 && h->ecyc_failed[(size_t)c]) {
       // no factors for this scenario's cycle correction: the column is the tree solve's
       // (finite), reported unconverged whatever its residual, and not refined
-      if (converged) converged[c] = 0;
+      if (st.converged) st.converged[c] = 0;
       continue;
     }
     if (bb > 0.0 && !(r <= rtol)) redo.push_back(c);
@@ -14116,30 +14193,44 @@ int batch_solve_cols(nx_network* h, const BatchWs& ws, int nc, const double* Bv,
     const int nr = (int)redo.size();
     HIPCALL(hipMemcpyAsync(ws.list, redo.data(), sizeof(int) * nr, hipMemcpyHostToDevice,
                            h->stream));
-    CHECK(batch_sweeps(h, ws, ws.list, nr, ws.R, ws.D, ens));
-    hipLaunchKernelGGL(k_b_add, dim3(grid_of(n, kBlock), nr), dim3(kBlock), 0, h->stream, Xv,
-                       ws.D, ld, ws.list, n);
-    h->b_launches += 1;
+    CHECK(refine(ws.list, nr));
     CHECK(batch_residual(h, ws, Xv, Bv, ws.list, nr, stats, cap, ens));
     h->b_refined += nr;
     for (int c : redo) {
       const double r = batch_relres(stats[2 * c], stats[2 * c + 1]);
-      if (iters) iters[c] = 2;
-      if (relres) relres[c] = r;
-      if (converged) converged[c] = r <= rtol ? 1 : 0;
-      if (!(r <= rtol) && !ens) fall.push_back(c);
+      st.set(c, 2, r, r <= rtol ? 1 : 0);
+      if (!(r <= rtol) && fb.mode != BatchFallback::kNone) fall.push_back(c);
     }
   }
   for (int c : fall) {  // still above rtol: the single-column path (with its MINRES)
     int32_t it = 0, cv = 0;
     double r = 0.0;
-    CHECK(batch_fallback(h, ws, Bv, Xv, c, rtol, &it, &r, &cv));
+    const double have =
+        fb.mode == BatchFallback::kKeep ? batch_relres(stats[2 * c], stats[2 * c + 1]) : -1.0;
+    CHECK(batch_fallback(h, ws, Bv, Xv, c, rtol, &it, &r, &cv, fb.maxit, have));
     h->b_fallback += 1;
-    if (iters) iters[c] = it;
-    if (relres) relres[c] = r;
-    if (converged) converged[c] = cv;
+    st.set(c, it, r, cv);
   }
   return NX_OK;
+}
+
+// The policy with a P1/DG0 handle's own sweeps (the refinement's correction through ws.D). An
+// ensemble's column still above rtol stays converged = 0, 2 iterations.
+int batch_solve_p1(nx_network* h, const BatchWs& ws, int nc, const double* Bv, double* Xv,
+                   double rtol, BatchStatus st, std::vector<double>& stats,
+                   const BatchEns* ens = nullptr) {
+  const SweepCtx sc = sweep_ctx(h, ws);
+  return batch_solve_cols(
+      h, ws, nc, Bv, Xv, rtol, st, stats,
+      [&](int ncs) { return batch_sweeps(sc, nullptr, ncs, Bv, Xv, ens); },
+      [&](const int* list, int nr) {
+        CHECK(batch_sweeps(sc, list, nr, ws.R, ws.D, ens));
+        hipLaunchKernelGGL(k_b_add, dim3(grid_of(h->n_own, kBlock), nr), dim3(kBlock), 0,
+                           h->stream, Xv, ws.D, ws.cols.ld, list, h->n_own);
+        h->b_launches += 1;
+        return (int)NX_OK;
+      },
+      BatchFallback{ens ? BatchFallback::kNone : BatchFallback::kPlain, 50000}, ens);
 }
 
 // What the sweeps read besides the right-hand side, current for the handle's matrix: the
@@ -14168,28 +14259,76 @@ int batch_zero_cols(nx_network* h, double* Xv, int64_t ld, int nc,
   return NX_OK;
 }
 
-int batch_edge_form(nx_network* h, const BatchWs& ws, int nc, int64_t l_ld) {
+// One launch of an edge-kernel family on nc columns: a 16- or 32-lane segment per edge where N
+// allows it, a wave per edge otherwise.
+template <class Args, void (*Seg16)(Args), void (*Seg32)(Args), void (*Wave)(Args)>
+int batch_edge_launch(nx_network* h, int nc, const Args& a) {
   const int64_t E = h->E;
-  const FormArgs fa{EdgeArgs{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N}, ws.X, ws.L,
-                    ws.cols.ld, l_ld, ws.gR, ws.gf, ws.gbc};
   constexpr int wpb = kBlock / 64;
   if (h->N < 16)
-    hipLaunchKernelGGL(k_b_edge_form_seg<16>, dim3(grid_of(E, wpb * 4), nc), dim3(kBlock), 0,
-                       h->stream, fa);
+    hipLaunchKernelGGL(Seg16, dim3(grid_of(E, wpb * 4), nc), dim3(kBlock), 0, h->stream, a);
   else if (h->N < 32)
-    hipLaunchKernelGGL(k_b_edge_form_seg<32>, dim3(grid_of(E, wpb * 2), nc), dim3(kBlock), 0,
-                       h->stream, fa);
+    hipLaunchKernelGGL(Seg32, dim3(grid_of(E, wpb * 2), nc), dim3(kBlock), 0, h->stream, a);
   else
-    hipLaunchKernelGGL(k_b_edge_form, dim3(grid_of(E, wpb), nc), dim3(kBlock), 0, h->stream, fa);
+    hipLaunchKernelGGL(Wave, dim3(grid_of(E, wpb), nc), dim3(kBlock), 0, h->stream, a);
   HIPCALL(hipGetLastError());
   h->b_launches += 1;
   return NX_OK;
+}
+
+int batch_edge_form(nx_network* h, const BatchWs& ws, int nc, int64_t l_ld) {
+  const FormArgs fa{EdgeArgs{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N}, ws.X, ws.L,
+                    ws.cols.ld, l_ld, ws.gR, ws.gf, ws.gbc};
+  return batch_edge_launch<FormArgs, k_b_edge_form_seg<16>, k_b_edge_form_seg<32>,
+                           k_b_edge_form>(h, nc, fa);
 }
 
 int batch_check_args(nx_network* h, int32_t n_cols, const double* edge_bc, const double* out) {
   if (!h) return fail(NX_ERR_ARG, "null handle");
   if (n_cols < 1) return fail(NX_ERR_ARG, "n_cols must be >= 1");
   if (!edge_bc || !out) return fail(NX_ERR_ARG, "edge_bc / out is NULL");
+  return NX_OK;
+}
+
+// A deferred assembly that the call is about to flush: counted in the call's launches, so a
+// caller sees that nothing current is rebuilt.
+int batch_pending(const nx_network* h) {
+  return (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+}
+
+// The chunks of a call: rhs(c0, nc) writes the chunk's right-hand sides into ws.B, then
+// solve(c0, nc, stats) its solutions into ws.X (stats: batch_solve_cols'; nullptr for solve:
+// the right-hand sides are the output). The chunk goes to `out` (n_cols x n_own): gathered
+// through the output map where order != 0 (ws.D), one copy and one synchronisation per
+// chunk, and a solution whose right-hand side was zero is written as the exact zero.
+template <class Rhs, class Solve>
+int batch_chunks(nx_network* h, const BatchWs& ws, int n_cols, int chunk, int order, double* out,
+                 Rhs rhs, Solve solve) {
+  constexpr bool solves = !std::is_same<Solve, std::nullptr_t>::value;
+  const int64_t n = h->n_own, ld = ws.cols.ld;
+  std::vector<double> stats;
+  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
+    const int nc = std::min(chunk, n_cols - c0);
+    CHECK(rhs(c0, nc));
+    const double* src = ws.B;
+    if constexpr (solves) {
+      CHECK(solve(c0, nc, stats));
+      src = ws.X;
+      if (order != 0) {
+        hipLaunchKernelGGL(k_b_gather, dim3(grid_of(n, kBlock), nc), dim3(kBlock), 0, h->stream,
+                           ws.X, ld, h->out_idx, n, ws.D);
+        HIPCALL(hipGetLastError());
+        h->b_launches += 1;
+        src = ws.D;
+      }
+    }
+    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * n, src, sizeof(double) * n * nc,
+                           hipMemcpyDeviceToHost, h->stream));
+    HIPCALL(hipStreamSynchronize(h->stream));
+    if constexpr (solves)
+      for (int c = 0; c < nc; ++c)  // b = 0: x = 0 exactly (no division by ||b||)
+        if (stats[2 * c + 1] == 0.0) std::fill_n(out + (int64_t)(c0 + c) * n, n, 0.0);
+  }
   return NX_OK;
 }
 
@@ -14220,15 +14359,11 @@ NX_API int nx_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc,
   CHECK(set_device(h));
   int chunk = 0;
   CHECK(batch_workspace(h, n_cols, &chunk));
-  const BatchWs ws = batch_carve(h, h->bws_cap);
-  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
-    const int nc = std::min(chunk, n_cols - c0);
-    CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
-    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * h->n_own, ws.B, sizeof(double) * h->n_own * nc,
-                           hipMemcpyDeviceToHost, h->stream));
-    HIPCALL(hipStreamSynchronize(h->stream));
-  }
-  return NX_OK;
+  const BatchWs ws = batch_carve(h);
+  return batch_chunks(
+      h, ws, n_cols, chunk, 0, out,
+      [&](int c0, int nc) { return batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const); },
+      nullptr);
 }
 
 NX_API int nx_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc,
@@ -14236,7 +14371,7 @@ NX_API int nx_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc
                           double* out, int32_t* iters, double* relres, int32_t* converged) {
   // (what the call makes current first is counted in its launches: a pending assembly, the
   // lumped mass, the cycle correction -- a caller sees that nothing current is rebuilt)
-  const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+  const int made_current = batch_pending(h);
   CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
   CHECK(batch_check_args(h, n_cols, edge_bc, out));
   if (!batch_ok(h))
@@ -14250,31 +14385,15 @@ NX_API int nx_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc
   int chunk = 0;
   CHECK(batch_workspace(h, n_cols, &chunk));
   h->b_chunk = chunk;
-  const BatchWs ws = batch_carve(h, h->bws_cap);
+  const BatchWs ws = batch_carve(h);
   CHECK(batch_make_current(h, ws));
-  const int64_t n = h->n_own, ld = ws.cols.ld;
-  std::vector<double> stats;
-  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
-    const int nc = std::min(chunk, n_cols - c0);
-    CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
-    CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.X, rtol, iters ? iters + c0 : nullptr,
-                           relres ? relres + c0 : nullptr, converged ? converged + c0 : nullptr,
-                           stats));
-    const double* src = ws.X;
-    if (order != 0) {
-      hipLaunchKernelGGL(k_b_gather, dim3(grid_of(n, kBlock), nc), dim3(kBlock), 0, h->stream, ws.X,
-                         ld, h->out_idx, n, ws.D);
-      HIPCALL(hipGetLastError());
-      h->b_launches += 1;
-      src = ws.D;
-    }
-    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * n, src, sizeof(double) * n * nc,
-                           hipMemcpyDeviceToHost, h->stream));
-    HIPCALL(hipStreamSynchronize(h->stream));
-    for (int c = 0; c < nc; ++c)  // b = 0: x = 0 exactly (no division by ||b||)
-      if (stats[2 * c + 1] == 0.0) std::fill_n(out + (int64_t)(c0 + c) * n, n, 0.0);
-  }
-  return NX_OK;
+  const BatchStatus st{iters, relres, converged};
+  return batch_chunks(
+      h, ws, n_cols, chunk, order, out,
+      [&](int c0, int nc) { return batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const); },
+      [&](int c0, int nc, std::vector<double>& stats) {
+        return batch_solve_p1(h, ws, nc, ws.B, ws.X, rtol, st.at(c0), stats);
+      });
 }
 
 // ---- nx_fe_batch_solve: nx_batch_solve for a (k, 0) handle solved through its auxiliary
@@ -14524,98 +14643,56 @@ struct FeAuxWs {
   double *B, *X;   // cap x lda: the condensed rhs and the auxiliary solution
   BatchCols cols;  // the sweeps' per-column scratch
   double* cw;      // the cycle correction's w, cap x m
+  size_t bytes;    // of the whole layout
 };
-size_t fe_aux_col_doubles(const nx_network* a) {
-  const int64_t S = std::max<int64_t>(a->pc_slots, 1);
-  return (size_t)(2 * a->n_col + 3 * a->E + 5 * S + 2 * (int64_t)a->n_cyc);
-}
-size_t fe_aux_bytes(const nx_network* a, int cap) {
-  return 8 * fe_aux_col_doubles(a) * (size_t)cap + 64;
-}
-FeAuxWs fe_batch_carve(const nx_network* h, int cap) {
-  const nx_network* a = h->fe_aux;
+// The auxiliary workspace's layout (as batch_layout: base null gives the size alone).
+FeAuxWs fe_aux_layout(const nx_network* a, int cap, void* base) {
   const int64_t E = a->E, S = std::max<int64_t>(a->pc_slots, 1), m = 2 * (int64_t)a->n_cyc;
   FeAuxWs w{};
-  double* p = static_cast<double*>(h->fe_bws);
-  auto take = [&](int64_t n) {
-    double* q = p;
-    p += n;
-    return q;
-  };
-  w.B = take(cap * a->n_col);
-  w.X = take(cap * a->n_col);
-  w.cols.list = nullptr;
-  w.cols.ld = a->n_col;
-  w.cols.n_chain = E;
-  w.cols.n_slot = S;
-  w.cols.chain_T = take(cap * E);
-  w.cols.chain_It = take(cap * E);
-  w.cols.chain_Ib = take(cap * E);
-  w.cols.slot_D = take(cap * S);
-  w.cols.slot_J = take(cap * S);
-  w.cols.slot_A = take(cap * S);
-  w.cols.slot_B = take(cap * S);
-  w.cols.slot_z = take(cap * S);
-  w.cw = take(cap * m);
+  WsWalk k{static_cast<double*>(base)};
+  w.B = k.take(cap * a->n_col);
+  w.X = k.take(cap * a->n_col);
+  w.cols = batch_cols_walk(k, cap, a->n_col, E, S);
+  w.cw = k.take(cap * m);
+  w.bytes = 8 * (size_t)k.off + 64;
   return w;
 }
+size_t fe_aux_bytes(const nx_network* a, int cap) { return fe_aux_layout(a, cap, nullptr).bytes; }
 // (the allocated bytes are checked, as in batch_fits: the auxiliary decomposition's slots and
 // cycle chains may have changed since the allocation)
 bool fe_batch_fits(const nx_network* h, int cap) {
-  return batch_fits(h, cap, false, false, false, false) && h->fe_bws != nullptr &&
-         cap <= h->fe_bws_cap && fe_aux_bytes(h->fe_aux, h->fe_bws_cap) <= h->fe_bws_bytes &&
+  return batch_fits(h, cap, BatchParts{}) && h->fe_bws != nullptr && cap <= h->fe_bws_cap &&
+         fe_aux_bytes(h->fe_aux, h->fe_bws_cap) <= h->fe_bws_bytes &&
          h->fe_bws_cap == h->bws_cap;
 }
-void fe_batch_free(nx_network* h) {
-  if (h->bws) (void)hipFree(h->bws);
-  if (h->fe_bws) (void)hipFree(h->fe_bws);
-  h->bws = h->fe_bws = nullptr;
-  h->bws_cap = h->fe_bws_cap = 0;
-  h->bws_bytes = h->fe_bws_bytes = 0;
-}
 
-// batch_workspace's rule for the two parts together: NXHIP_BATCH_CHUNK (read per call) or the
-// largest chunk of <= kBatchChunkMax whose two parts fit kBatchMemShare of the free device
-// memory; a failed allocation of either part halves it down to 1.
+// batch_workspace for the two parts together (batch_chunk_rule: the chunk's two parts fit the
+// share of the free memory; a failed allocation of either part halves it).
 int fe_batch_workspace(nx_network* h, int n_cols, int* chunk_out) {
   const nx_network* a = h->fe_aux;
-  auto bytes = [&](int cap) {
-    return batch_bytes(h, cap, false, false, false, false) + fe_aux_bytes(a, cap);
+  auto release = [&]() {
+    batch_free(h);
+    if (h->fe_bws) (void)hipFree(h->fe_bws);
+    h->fe_bws = nullptr;
+    h->fe_bws_cap = 0;
+    h->fe_bws_bytes = 0;
   };
-  int chunk = std::min(n_cols, kBatchChunkMax);
-  const char* e = std::getenv("NXHIP_BATCH_CHUNK");
-  if (e != nullptr && std::atoi(e) > 0) {
-    chunk = std::min(std::min(std::atoi(e), kBatchChunkEnvMax), n_cols);
-  } else if (!fe_batch_fits(h, chunk)) {
-    size_t fr = 0, tot = 0;
-    HIPCALL(hipMemGetInfo(&fr, &tot));
-    const double room = kBatchMemShare * (double)fr;
-    while (chunk > 1 && (double)bytes(chunk) > room) --chunk;
-  }
-  if (!fe_batch_fits(h, chunk)) {
-    HIPCALL(hipStreamSynchronize(h->stream));
-    fe_batch_free(h);
-    int cap = chunk;
-    for (;;) {
-      const bool ok1 = hipMalloc(&h->bws, batch_bytes(h, cap, false, false, false, false)) ==
-                       hipSuccess;
-      const bool ok2 = ok1 && hipMalloc(&h->fe_bws, fe_aux_bytes(a, cap)) == hipSuccess;
-      if (ok2) break;
-      (void)hipGetLastError();
-      if (ok1) (void)hipFree(h->bws);
-      h->bws = h->fe_bws = nullptr;
-      if (cap == 1)
-        return fail(NX_ERR_HIP, "nx_fe_batch_solve: no memory for one column's workspace");
-      cap = std::max(1, cap / 2);
+  auto alloc = [&](int cap) {
+    if (!batch_alloc(h, cap, BatchParts{})) return false;
+    const size_t bytes = fe_aux_bytes(a, cap);
+    if (hipMalloc(&h->fe_bws, bytes) != hipSuccess) {
+      h->fe_bws = nullptr;
+      batch_free(h);
+      return false;
     }
-    chunk = std::min(chunk, cap);
-    h->bws_cap = h->fe_bws_cap = cap;
-    h->bws_grad = h->bws_ens = h->bws_hvp = h->bws_ecyc = false;
-    h->bws_bytes = batch_bytes(h, cap, false, false, false, false);
-    h->fe_bws_bytes = fe_aux_bytes(a, cap);
-  }
-  *chunk_out = chunk;
-  return NX_OK;
+    h->fe_bws_cap = cap;
+    h->fe_bws_bytes = bytes;
+    return true;
+  };
+  return batch_chunk_rule(
+      h, n_cols, false, "nx_fe_batch_solve", [&](int cap) { return fe_batch_fits(h, cap); },
+      [&](int cap) { return batch_bytes(h, cap, BatchParts{}) + fe_aux_bytes(a, cap); }, release,
+      alloc, chunk_out);
 }
 
 FeCond fe_cond_of(const nx_network* h) {
@@ -14656,81 +14733,25 @@ int fe_cyc_build_launches(const nx_network* a) {
 // built after it where the matrix is new (fe_cyc_build reads that lumped mass).
 int fe_batch_apply(nx_network* h, const BatchWs& ws, const FeAuxWs& wa, const int* list, int nc,
                    const double* Bv, double* Xv, int accum, bool dq) {
-  nx_network* a = h->fe_aux;
   const FeCond c = fe_cond_of(h);
   const int64_t np = h->E * (int64_t)h->N, n0 = h->E * (int64_t)(h->N + 1) + np + h->fe_nl;
   hipLaunchKernelGGL(k_fe_b_condense, dim3(grid_of(n0, kBlock)), dim3(kBlock), 0, h->stream, c,
-                     Bv, ws.cols.ld, wa.B, wa.cols.ld, list, nc, dq ? a->dq : nullptr);
+                     Bv, ws.cols.ld, wa.B, wa.cols.ld, list, nc, dq ? h->fe_aux->dq : nullptr);
   HIPCALL(hipGetLastError());
   h->b_launches += 1;
-  if (dq && a->n_cyc > 0 && a->cyc_version != h->lhs_version) {
-    CHECK(fe_cyc_build(h, a));
-    h->b_launches += fe_cyc_build_launches(a);
+  if (dq && h->fe_aux->n_cyc > 0 && h->fe_aux->cyc_version != h->lhs_version) {
+    // (the one place a batched call writes the auxiliary handle: its correction, per matrix)
+    CHECK(fe_cyc_build(h, h->fe_aux));
+    h->b_launches += fe_cyc_build_launches(h->fe_aux);
   }
-  {
-    BatchWs aw{};
-    aw.cols = wa.cols;
-    aw.cw = wa.cw;
-    const hipStream_t as = a->stream;
-    const int before = a->b_launches;
-    a->stream = h->stream;
-    a->b_launches = 0;
-    const int rc = batch_sweeps(a, aw, list, nc, wa.B, wa.X);
-    h->b_launches += a->b_launches;
-    a->b_launches = before;
-    a->stream = as;
-    CHECK(rc);
-  }
+  const nx_network* a = h->fe_aux;  // lent read-only: the sweeps run on this handle's stream
+  const SweepCtx sc{a, h->stream, &h->b_launches, wa.cols, wa.cw, nullptr, nullptr, nullptr,
+                    nullptr};
+  CHECK(batch_sweeps(sc, list, nc, wa.B, wa.X));
   hipLaunchKernelGGL(k_fe_b_expand, dim3(grid_of(n0 + np, kBlock)), dim3(kBlock), 0, h->stream, c,
                      wa.X, wa.cols.ld, Bv, Xv, ws.cols.ld, list, nc, accum);
   HIPCALL(hipGetLastError());
   h->b_launches += 1;
-  return NX_OK;
-}
-
-// batch_solve_cols' per-column policy on the first nc workspace columns of a (k, 0) handle.
-int fe_batch_solve_cols(nx_network* h, const BatchWs& ws, const FeAuxWs& wa, int nc, double rtol,
-                        int32_t maxit, bool first, int32_t* iters, double* relres,
-                        int32_t* converged, std::vector<double>& stats) {
-  const int cap = h->bws_cap;
-  std::vector<int> redo, fall;
-  CHECK(fe_batch_apply(h, ws, wa, nullptr, nc, ws.B, ws.X, 0, first));
-  CHECK(batch_residual(h, ws, ws.X, ws.B, nullptr, nc, stats, cap));
-  for (int c = 0; c < nc; ++c) {
-    const double bb = stats[2 * c + 1];
-    const double r = batch_relres(stats[2 * c], bb);
-    if (iters) iters[c] = 1;
-    if (relres) relres[c] = r;
-    if (converged) converged[c] = (bb == 0.0 || r <= rtol) ? 1 : 0;
-    if (bb > 0.0 && !(r <= rtol)) redo.push_back(c);
-  }
-  if (!redo.empty()) {  // one refinement pass over the failing columns only: x += A^{-1} r
-    const int nr = (int)redo.size();
-    HIPCALL(hipMemcpyAsync(ws.list, redo.data(), sizeof(int) * nr, hipMemcpyHostToDevice,
-                           h->stream));
-    CHECK(fe_batch_apply(h, ws, wa, ws.list, nr, ws.R, ws.X, 1, false));
-    CHECK(batch_residual(h, ws, ws.X, ws.B, ws.list, nr, stats, cap));
-    h->b_refined += nr;
-    for (int c : redo) {
-      const double r = batch_relres(stats[2 * c], stats[2 * c + 1]);
-      if (iters) iters[c] = 2;
-      if (relres) relres[c] = r;
-      if (converged) converged[c] = r <= rtol ? 1 : 0;
-      if (!(r <= rtol)) fall.push_back(c);
-    }
-  }
-  // still above rtol: the single-column route (fe_solve_direct, then MINRES capped at maxit);
-  // where that ends unconverged and no better, the refined column stands (batch_fallback)
-  for (int c : fall) {
-    int32_t it = 0, cv = 0;
-    double r = 0.0;
-    const double have = batch_relres(stats[2 * c], stats[2 * c + 1]);
-    CHECK(batch_fallback(h, ws, ws.B, ws.X, c, rtol, &it, &r, &cv, maxit, have));
-    h->b_fallback += 1;
-    if (iters) iters[c] = it;
-    if (relres) relres[c] = r;
-    if (converged) converged[c] = cv;
-  }
   return NX_OK;
 }
 
@@ -14757,15 +14778,11 @@ NX_API int nx_fe_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_b
   CHECK(set_device(h));
   int chunk = 0;
   CHECK(fe_batch_workspace(h, n_cols, &chunk));
-  const BatchWs ws = batch_carve(h, h->bws_cap);
-  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
-    const int nc = std::min(chunk, n_cols - c0);
-    CHECK(fe_batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
-    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * h->n_own, ws.B, sizeof(double) * h->n_own * nc,
-                           hipMemcpyDeviceToHost, h->stream));
-    HIPCALL(hipStreamSynchronize(h->stream));
-  }
-  return NX_OK;
+  const BatchWs ws = batch_carve(h);
+  return batch_chunks(
+      h, ws, n_cols, chunk, 0, out,
+      [&](int c0, int nc) { return fe_batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const); },
+      nullptr);
 }
 
 NX_API int nx_fe_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc,
@@ -14773,7 +14790,7 @@ NX_API int nx_fe_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge
                              int32_t maxit, int32_t order, double* out, int32_t* iters,
                              double* relres, int32_t* converged) {
   // (a flushed assembly is counted in the call's launches, as in nx_batch_solve)
-  const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+  const int made_current = batch_pending(h);
   CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
   CHECK(batch_check_args(h, n_cols, edge_bc, out));
   if (maxit < 1) return fail(NX_ERR_ARG, "maxit must be >= 1");
@@ -14795,31 +14812,25 @@ NX_API int nx_fe_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge
   int chunk = 0;
   CHECK(fe_batch_workspace(h, n_cols, &chunk));
   h->b_chunk = chunk;
-  const BatchWs ws = batch_carve(h, h->bws_cap);
-  const FeAuxWs wa = fe_batch_carve(h, h->fe_bws_cap);
-  const int64_t n = h->n_own, ld = ws.cols.ld;
-  std::vector<double> stats;
-  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
-    const int nc = std::min(chunk, n_cols - c0);
-    CHECK(fe_batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
-    CHECK(fe_batch_solve_cols(h, ws, wa, nc, rtol, maxit, c0 == 0,
-                              iters ? iters + c0 : nullptr, relres ? relres + c0 : nullptr,
-                              converged ? converged + c0 : nullptr, stats));
-    const double* src = ws.X;
-    if (order != 0) {
-      hipLaunchKernelGGL(k_b_gather, dim3(grid_of(n, kBlock), nc), dim3(kBlock), 0, h->stream, ws.X,
-                         ld, h->out_idx, n, ws.D);
-      HIPCALL(hipGetLastError());
-      h->b_launches += 1;
-      src = ws.D;
-    }
-    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * n, src, sizeof(double) * n * nc,
-                           hipMemcpyDeviceToHost, h->stream));
-    HIPCALL(hipStreamSynchronize(h->stream));
-    for (int c = 0; c < nc; ++c)  // b = 0: x = 0 exactly (no division by ||b||)
-      if (stats[2 * c + 1] == 0.0) std::fill_n(out + (int64_t)(c0 + c) * n, n, 0.0);
-  }
-  return NX_OK;
+  const BatchWs ws = batch_carve(h);
+  const FeAuxWs wa = fe_aux_layout(h->fe_aux, h->fe_bws_cap, h->fe_bws);
+  // the policy's operator: condense, the auxiliary sweeps, expand (the refinement accumulates
+  // into ws.X); the single-column route is fe_solve_direct, then MINRES capped at maxit, and
+  // where that ends unconverged and no better, the refined column stands
+  const BatchStatus st{iters, relres, converged};
+  return batch_chunks(
+      h, ws, n_cols, chunk, order, out,
+      [&](int c0, int nc) { return fe_batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const); },
+      [&](int c0, int nc, std::vector<double>& stats) {
+        return batch_solve_cols(
+            h, ws, nc, ws.B, ws.X, rtol, st.at(c0), stats,
+            // (the call's first pass writes the auxiliary lumped mass)
+            [&](int ncs) { return fe_batch_apply(h, ws, wa, nullptr, ncs, ws.B, ws.X, 0, c0 == 0); },
+            [&](const int* list, int nr) {
+              return fe_batch_apply(h, ws, wa, list, nr, ws.R, ws.X, 1, false);
+            },
+            BatchFallback{BatchFallback::kKeep, maxit});
+      });
 }
 
 namespace {
@@ -14876,6 +14887,109 @@ int batch_obs_upload(nx_network* h, int32_t n_obs, int chunk, const int32_t* obs
   return NX_OK;
 }
 
+// What nx_batch_gradient and nx_batch_hvp (and their ensemble forms) share: the call's set-up
+// (batch_adjoint_begin) and the two steps every solve of theirs is made of.
+struct AdjointRun {
+  nx_network* h;
+  double rtol;
+  int32_t n_obs;
+  BatchWs ws;
+  bool ens;  // every scenario against its own matrix (be)
+  BatchEns be;
+  ObsDev od;
+  int chunk;
+  // the linear objective against the handle's matrix: the same adjoint column (ws.L, column 0)
+  // for every scenario, solved once per call, and its status
+  bool one_adj;
+  int32_t a_it = 1, a_cv = 1;
+  double a_rr = 0.0;
+  std::vector<double> stats;
+  // Xv = A^{-1} Bv on nc columns by the per-column policy; b = 0: x = 0 exactly
+  int solve(int nc, const double* Bv, double* Xv, BatchStatus st) {
+    CHECK(batch_solve_p1(h, ws, nc, Bv, Xv, rtol, st, stats, ens ? &be : nullptr));
+    return batch_zero_cols(h, Xv, ws.cols.ld, nc, stats);
+  }
+  // k_b_obs on nc columns of X: the objective into J and / or the adjoint's right-hand side
+  // into C (either may be null; C: one block per slice of rows)
+  int observe(int nc, const double* X, int32_t kind, double* Cv, double* J) {
+    const int64_t n = h->n_own;
+    hipLaunchKernelGGL(k_b_obs, dim3(Cv ? grid_of(n, kObsSpan) : 1, nc), dim3(kObsThreads), 0,
+                       h->stream, X, ws.cols.ld, n, kind, n_obs, od.rows, od.w,
+                       kind ? od.d : nullptr, Cv, J);
+    HIPCALL(hipGetLastError());
+    h->b_launches += 1;
+    return NX_OK;
+  }
+  // the chunk's observed data to the device (least squares)
+  int upload_data(const double* obs_d, int c0, int nc) {
+    HIPCALL(hipMemcpyAsync(od.d, obs_d + (int64_t)c0 * n_obs, sizeof(double) * n_obs * nc,
+                           hipMemcpyHostToDevice, h->stream));
+    return NX_OK;
+  }
+  // the chunk's outputs straight into the caller's arrays (no staging, no host unpack)
+  hipError_t out(double* dst, const double* src, int64_t per, int c0, int nc) const {
+    return dst ? hipMemcpyAsync(dst + (int64_t)c0 * per, src, sizeof(double) * per * nc,
+                                hipMemcpyDeviceToHost, h->stream)
+               : hipSuccess;
+  }
+};
+
+// Their common argument checks (ptrs_ok / ptrs_msg: the call's own required pointers).
+int batch_adjoint_args(nx_network* h, int32_t n_cols, bool ptrs_ok, const char* ptrs_msg,
+                       int32_t kind, int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
+                       const double* obs_d) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (n_cols < 1) return fail(NX_ERR_ARG, "n_cols must be >= 1");
+  if (!ptrs_ok) return fail(NX_ERR_ARG, ptrs_msg);
+  if (n_obs < 1 || !obs_rows || !obs_w) return fail(NX_ERR_ARG, "at least one observed row");
+  if (kind != 0 && kind != 1) return fail(NX_ERR_ARG, "kind: 0 linear, 1 least squares");
+  if (kind == 1 && !obs_d) return fail(NX_ERR_ARG, "the least-squares objective needs obs_d");
+  return NX_OK;
+}
+
+// The state checks (who: the entry point, for the messages; edge_R: an ensemble), the counters,
+// the workspace with `ask`, what the sweeps read made current, the observation list uploaded,
+// and the one adjoint column where it serves every scenario. made_current: batch_pending before
+// the flush.
+int batch_adjoint_begin(nx_network* h, const std::string& who, int made_current, BatchParts ask,
+                        int32_t n_cols, const double* edge_R, double rtol, int32_t kind,
+                        int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
+                        AdjointRun* r) {
+  const bool ens = edge_R != nullptr;
+  if (ens ? !ensemble_ok(h) : !batch_ok(h))
+    return fail(NX_ERR_STATE,
+                who + (ens ? ": the batched ensemble does not apply to this handle "
+                             "(nx_ensemble_supported)"
+                           : ": the batched direct solve does not apply to this handle "
+                             "(nx_batch_supported)"));
+  if (!h->have_lhs) return fail(NX_ERR_STATE, "assemble the matrix before " + who);
+  const int64_t n = h->n_own;
+  if (ens && ensemble_R_bad(edge_R, (int64_t)n_cols * h->E))
+    return fail(NX_ERR_ARG, who + ": R must be finite and positive");
+  CHECK(batch_obs_rows_check(n, n_obs, obs_rows));
+  CHECK(set_device(h));
+  h->b_refined = h->b_fallback = 0;
+  if (ens) h->ecyc_unit = h->ecyc_storage = 0;
+  h->b_launches = made_current + (!ens && h->dq_stale ? 1 : 0);
+  if (ens) ask.bits |= BatchParts::kEns;
+  CHECK(batch_workspace(h, n_cols, &r->chunk, ask));
+  h->b_chunk = r->chunk;
+  r->h = h;
+  r->rtol = rtol;
+  r->n_obs = n_obs;
+  r->ws = batch_carve(h);
+  r->ens = ens;
+  r->be = batch_ens(h, r->ws);
+  if (!ens) CHECK(batch_make_current(h, r->ws));  // (an ensemble reads no dq of the handle's)
+  CHECK(batch_obs_upload(h, n_obs, r->chunk, obs_rows, obs_w, &r->od));
+  r->one_adj = kind == 0 && !ens;
+  if (r->one_adj) {
+    CHECK(r->observe(1, nullptr, 0, r->ws.C, nullptr));
+    CHECK(r->solve(1, r->ws.C, r->ws.L, BatchStatus{&r->a_it, &r->a_rr, &r->a_cv}));
+  }
+  return NX_OK;
+}
+
 // nx_batch_gradient (edge_R null: every scenario against the handle's matrix) and
 // nx_ensemble_gradient (edge_R: n_cols x E, every scenario against its own matrix; the adjoint
 // column is then per scenario for both kinds, and grad_R null means the objective alone).
@@ -14885,109 +14999,42 @@ int batch_gradient_run(nx_network* h, int32_t n_cols, const double* edge_R, cons
                        const double* obs_d, double* value, double* grad_R, double* grad_bc,
                        double* grad_f, int32_t* iters, double* relres, int32_t* converged) {
   const bool ens = edge_R != nullptr;
-  const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+  const int made_current = batch_pending(h);
   CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
-  if (!h) return fail(NX_ERR_ARG, "null handle");
-  if (n_cols < 1) return fail(NX_ERR_ARG, "n_cols must be >= 1");
-  if (!edge_bc || !value || (!ens && !grad_R))
-    return fail(NX_ERR_ARG, "edge_bc / value / grad_R is NULL");
-  if (n_obs < 1 || !obs_rows || !obs_w) return fail(NX_ERR_ARG, "at least one observed row");
-  if (kind != 0 && kind != 1) return fail(NX_ERR_ARG, "kind: 0 linear, 1 least squares");
-  if (kind == 1 && !obs_d) return fail(NX_ERR_ARG, "the least-squares objective needs obs_d");
-  if (ens ? !ensemble_ok(h) : !batch_ok(h))
-    return fail(NX_ERR_STATE, ens ? "nx_ensemble_gradient: the batched ensemble does not apply "
-                                    "to this handle (nx_ensemble_supported)"
-                                  : "nx_batch_gradient: the batched direct solve does not apply "
-                                    "to this handle (nx_batch_supported)");
-  if (!h->have_lhs)
-    return fail(NX_ERR_STATE, ens ? "assemble the matrix before nx_ensemble_gradient"
-                                  : "assemble the matrix before nx_batch_gradient");
-  const int64_t n = h->n_own, E = h->E;
-  if (ens && ensemble_R_bad(edge_R, (int64_t)n_cols * E))
-    return fail(NX_ERR_ARG, "nx_ensemble_gradient: R must be finite and positive");
-  CHECK(batch_obs_rows_check(n, n_obs, obs_rows));
-  CHECK(set_device(h));
-  h->b_refined = h->b_fallback = 0;
-  if (ens) h->ecyc_unit = h->ecyc_storage = 0;
-  h->b_launches = made_current + (!ens && h->dq_stale ? 1 : 0);
-  int chunk = 0;
-  CHECK(batch_workspace(h, n_cols, &chunk, true, ens));
-  h->b_chunk = chunk;
-  const BatchWs ws = batch_carve(h, h->bws_cap);
-  const BatchEns be = batch_ens(h, ws);
-  const BatchEns* ep = ens ? &be : nullptr;
-  if (!ens) CHECK(batch_make_current(h, ws));  // (an ensemble reads no dq of the handle's)
-  ObsDev od{};
-  CHECK(batch_obs_upload(h, n_obs, chunk, obs_rows, obs_w, &od));
-  int* d_rows = od.rows;
-  double *d_w = od.w, *d_d = od.d;
-  const int64_t ld = ws.cols.ld;
-  const int slices = grid_of(n, kObsSpan);
-  std::vector<double> stats;
-  int32_t a_it = 1, a_cv = 1;
-  double a_rr = 0.0;
-  const bool one_adj = kind == 0 && !ens;
-  if (one_adj) {  // the same adjoint column for every scenario: solved once per call
-    hipLaunchKernelGGL(k_b_obs, dim3(slices, 1), dim3(kObsThreads), 0, h->stream, nullptr, ld, n,
-                       0, n_obs, d_rows, d_w, nullptr, ws.C, nullptr);
-    HIPCALL(hipGetLastError());
-    h->b_launches += 1;
-    CHECK(batch_solve_cols(h, ws, 1, ws.C, ws.L, rtol, &a_it, &a_rr, &a_cv, stats));
-    CHECK(batch_zero_cols(h, ws.L, ld, 1, stats));
-  }
-  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
-    const int nc = std::min(chunk, n_cols - c0);
+  CHECK(batch_adjoint_args(h, n_cols, edge_bc && value && (ens || grad_R),
+                           "edge_bc / value / grad_R is NULL", kind, n_obs, obs_rows, obs_w,
+                           obs_d));
+  AdjointRun r;
+  CHECK(batch_adjoint_begin(h, ens ? "nx_ensemble_gradient" : "nx_batch_gradient", made_current,
+                            BatchParts{BatchParts::kGrad}, n_cols, edge_R, rtol, kind, n_obs,
+                            obs_rows, obs_w, &r));
+  const BatchWs& ws = r.ws;
+  const BatchStatus st{iters, relres, converged};
+  const int64_t E = h->E, ld = ws.cols.ld;
+  for (int c0 = 0; c0 < n_cols; c0 += r.chunk) {
+    const int nc = std::min(r.chunk, n_cols - c0);
     CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const, edge_R));
-    CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.X, rtol, iters ? iters + c0 : nullptr,
-                           relres ? relres + c0 : nullptr, converged ? converged + c0 : nullptr,
-                           stats, ep));
-    CHECK(batch_zero_cols(h, ws.X, ld, nc, stats));  // b = 0: x = 0 exactly
-    int32_t* a_iters = iters ? iters + n_cols + c0 : nullptr;
-    double* a_relres = relres ? relres + n_cols + c0 : nullptr;
-    int32_t* a_conv = converged ? converged + n_cols + c0 : nullptr;
-    if (kind == 1)
-      HIPCALL(hipMemcpyAsync(d_d, obs_d + (int64_t)c0 * n_obs, sizeof(double) * n_obs * nc,
-                             hipMemcpyHostToDevice, h->stream));
+    CHECK(r.solve(nc, ws.B, ws.X, st.at(c0)));
+    if (kind == 1) CHECK(r.upload_data(obs_d, c0, nc));
     if (!grad_R) {  // (an ensemble's) objective alone: no adjoint, n_cols doubles to the host
-      hipLaunchKernelGGL(k_b_obs, dim3(1, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n, kind,
-                         n_obs, d_rows, d_w, kind ? d_d : nullptr, nullptr, ws.gJ);
-      HIPCALL(hipGetLastError());
-      h->b_launches += 1;
-      HIPCALL(hipMemcpyAsync(value + c0, ws.gJ, sizeof(double) * nc, hipMemcpyDeviceToHost,
-                             h->stream));
+      CHECK(r.observe(nc, ws.X, kind, nullptr, ws.gJ));
+      HIPCALL(r.out(value, ws.gJ, 1, c0, nc));
       HIPCALL(hipStreamSynchronize(h->stream));
       continue;
     }
-    if (!one_adj) {
-      hipLaunchKernelGGL(k_b_obs, dim3(slices, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n,
-                         kind, n_obs, d_rows, d_w, kind ? d_d : nullptr, ws.C, ws.gJ);
-      HIPCALL(hipGetLastError());
-      h->b_launches += 1;
-      CHECK(batch_solve_cols(h, ws, nc, ws.C, ws.L, rtol, a_iters, a_relres, a_conv, stats, ep));
-      CHECK(batch_zero_cols(h, ws.L, ld, nc, stats));
+    const BatchStatus adj = st.at((int64_t)n_cols + c0);
+    if (!r.one_adj) {
+      CHECK(r.observe(nc, ws.X, kind, ws.C, ws.gJ));
+      CHECK(r.solve(nc, ws.C, ws.L, adj));
     } else {
-      hipLaunchKernelGGL(k_b_obs, dim3(1, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n, 0,
-                         n_obs, d_rows, d_w, nullptr, nullptr, ws.gJ);
-      HIPCALL(hipGetLastError());
-      h->b_launches += 1;
-      for (int c = 0; c < nc; ++c) {
-        if (a_iters) a_iters[c] = a_it;
-        if (a_relres) a_relres[c] = a_rr;
-        if (a_conv) a_conv[c] = a_cv;
-      }
+      CHECK(r.observe(nc, ws.X, 0, nullptr, ws.gJ));
+      for (int c = 0; c < nc; ++c) adj.set(c, r.a_it, r.a_rr, r.a_cv);
     }
-    CHECK(batch_edge_form(h, ws, nc, one_adj ? 0 : ld));
-    // the chunk's outputs straight into the caller's arrays (no staging, no host unpack)
-    HIPCALL(hipMemcpyAsync(value + c0, ws.gJ, sizeof(double) * nc, hipMemcpyDeviceToHost,
-                           h->stream));
-    HIPCALL(hipMemcpyAsync(grad_R + (int64_t)c0 * E, ws.gR, sizeof(double) * E * nc,
-                           hipMemcpyDeviceToHost, h->stream));
-    if (grad_f)
-      HIPCALL(hipMemcpyAsync(grad_f + (int64_t)c0 * E, ws.gf, sizeof(double) * E * nc,
-                             hipMemcpyDeviceToHost, h->stream));
-    if (grad_bc)
-      HIPCALL(hipMemcpyAsync(grad_bc + (int64_t)c0 * 2 * E, ws.gbc, sizeof(double) * 2 * E * nc,
-                             hipMemcpyDeviceToHost, h->stream));
+    CHECK(batch_edge_form(h, ws, nc, r.one_adj ? 0 : ld));
+    HIPCALL(r.out(value, ws.gJ, 1, c0, nc));
+    HIPCALL(r.out(grad_R, ws.gR, E, c0, nc));
+    HIPCALL(r.out(grad_f, ws.gf, E, c0, nc));
+    HIPCALL(r.out(grad_bc, ws.gbc, 2 * E, c0, nc));
     HIPCALL(hipStreamSynchronize(h->stream));
   }
   return NX_OK;
@@ -15020,39 +15067,17 @@ int batch_dir_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const 
 // Y -= (sum_e v_R[e] dA/dR_e) Z on nc columns (k_b_mass_apply*, one launch).
 int batch_mass_apply(nx_network* h, const BatchWs& ws, int nc, const double* Z, int64_t z_ld,
                      double* Y) {
-  const int64_t E = h->E;
   const MassArgs ma{EdgeArgs{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N}, Z, z_ld, ws.vR, Y,
                     ws.cols.ld};
-  constexpr int wpb = kBlock / 64;
-  if (h->N < 16)
-    hipLaunchKernelGGL(k_b_mass_apply_seg<16>, dim3(grid_of(E, wpb * 4), nc), dim3(kBlock), 0,
-                       h->stream, ma);
-  else if (h->N < 32)
-    hipLaunchKernelGGL(k_b_mass_apply_seg<32>, dim3(grid_of(E, wpb * 2), nc), dim3(kBlock), 0,
-                       h->stream, ma);
-  else
-    hipLaunchKernelGGL(k_b_mass_apply, dim3(grid_of(E, wpb), nc), dim3(kBlock), 0, h->stream, ma);
-  HIPCALL(hipGetLastError());
-  h->b_launches += 1;
-  return NX_OK;
+  return batch_edge_launch<MassArgs, k_b_mass_apply_seg<16>, k_b_mass_apply_seg<32>,
+                           k_b_mass_apply>(h, nc, ma);
 }
 
 int batch_edge_form2(nx_network* h, const BatchWs& ws, int nc, const double* L, int64_t l_ld) {
-  const int64_t E = h->E;
   const Form2Args fa{EdgeArgs{h->edge_x, h->edge_lm, h->edge_seg, h->E, h->N}, ws.X, ws.Xd, L,
                      ws.Ld, ws.cols.ld, l_ld, ws.gR, ws.gf, ws.gbc, ws.HR, ws.Hf, ws.Hbc};
-  constexpr int wpb = kBlock / 64;
-  if (h->N < 16)
-    hipLaunchKernelGGL(k_b_edge_form2_seg<16>, dim3(grid_of(E, wpb * 4), nc), dim3(kBlock), 0,
-                       h->stream, fa);
-  else if (h->N < 32)
-    hipLaunchKernelGGL(k_b_edge_form2_seg<32>, dim3(grid_of(E, wpb * 2), nc), dim3(kBlock), 0,
-                       h->stream, fa);
-  else
-    hipLaunchKernelGGL(k_b_edge_form2, dim3(grid_of(E, wpb), nc), dim3(kBlock), 0, h->stream, fa);
-  HIPCALL(hipGetLastError());
-  h->b_launches += 1;
-  return NX_OK;
+  return batch_edge_launch<Form2Args, k_b_edge_form2_seg<16>, k_b_edge_form2_seg<32>,
+                           k_b_edge_form2>(h, nc, fa);
 }
 
 // nx_batch_hvp (edge_R null) and nx_ensemble_hvp (edge_R: every scenario against its own
@@ -15071,95 +15096,39 @@ int batch_hvp_run(nx_network* h, int32_t n_cols, const double* edge_R, const dou
                   double* hess_f, int32_t* iters, double* relres, int32_t* converged) {
   const bool ens = edge_R != nullptr;
   const bool gn = gauss_newton != 0;
-  const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+  const int made_current = batch_pending(h);
   CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
-  if (!h) return fail(NX_ERR_ARG, "null handle");
-  if (n_cols < 1) return fail(NX_ERR_ARG, "n_cols must be >= 1");
-  if (!edge_bc || !value || !hess_R) return fail(NX_ERR_ARG, "edge_bc / value / hess_R is NULL");
-  if (n_obs < 1 || !obs_rows || !obs_w) return fail(NX_ERR_ARG, "at least one observed row");
-  if (kind != 0 && kind != 1) return fail(NX_ERR_ARG, "kind: 0 linear, 1 least squares");
-  if (kind == 1 && !obs_d) return fail(NX_ERR_ARG, "the least-squares objective needs obs_d");
+  CHECK(batch_adjoint_args(h, n_cols, edge_bc && value && hess_R,
+                           "edge_bc / value / hess_R is NULL", kind, n_obs, obs_rows, obs_w,
+                           obs_d));
   if (!dir_R && !dir_bc && !dir_f)
     return fail(NX_ERR_ARG, "a direction is needed: dir_R, dir_bc or dir_f");
   if (gauss_newton != 0 && gauss_newton != 1) return fail(NX_ERR_ARG, "gauss_newton: 0 or 1");
   if (gn && kind == 0)
     return fail(NX_ERR_ARG, "the Gauss-Newton product needs the least-squares objective");
-  if (ens ? !ensemble_ok(h) : !batch_ok(h))
-    return fail(NX_ERR_STATE, ens ? "nx_ensemble_hvp: the batched ensemble does not apply to this "
-                                    "handle (nx_ensemble_supported)"
-                                  : "nx_batch_hvp: the batched direct solve does not apply to "
-                                    "this handle (nx_batch_supported)");
-  if (!h->have_lhs)
-    return fail(NX_ERR_STATE, ens ? "assemble the matrix before nx_ensemble_hvp"
-                                  : "assemble the matrix before nx_batch_hvp");
-  const int64_t n = h->n_own, E = h->E;
-  if (ens && ensemble_R_bad(edge_R, (int64_t)n_cols * E))
-    return fail(NX_ERR_ARG, "nx_ensemble_hvp: R must be finite and positive");
-  CHECK(batch_obs_rows_check(n, n_obs, obs_rows));
-  CHECK(set_device(h));
-  h->b_refined = h->b_fallback = 0;
-  if (ens) h->ecyc_unit = h->ecyc_storage = 0;
-  h->b_launches = made_current + (!ens && h->dq_stale ? 1 : 0);
-  int chunk = 0;
-  CHECK(batch_workspace(h, n_cols, &chunk, true, ens, true));
-  h->b_chunk = chunk;
-  const BatchWs ws = batch_carve(h, h->bws_cap);
-  const BatchEns be = batch_ens(h, ws);
-  const BatchEns* ep = ens ? &be : nullptr;
-  if (!ens) CHECK(batch_make_current(h, ws));  // (an ensemble reads no dq of the handle's)
-  ObsDev od{};
-  CHECK(batch_obs_upload(h, n_obs, chunk, obs_rows, obs_w, &od));
-  const int64_t ld = ws.cols.ld;
-  const int slices = grid_of(n, kObsSpan);
-  std::vector<double> stats;
-  int32_t a_it = 1, a_cv = 1;
-  double a_rr = 0.0;
-  const bool one_adj = kind == 0 && !ens;  // (kind 0 is never Gauss-Newton)
-  if (one_adj) {  // the same adjoint column for every scenario: solved once per call
-    hipLaunchKernelGGL(k_b_obs, dim3(slices, 1), dim3(kObsThreads), 0, h->stream, nullptr, ld, n,
-                       0, n_obs, od.rows, od.w, nullptr, ws.C, nullptr);
-    HIPCALL(hipGetLastError());
-    h->b_launches += 1;
-    CHECK(batch_solve_cols(h, ws, 1, ws.C, ws.L, rtol, &a_it, &a_rr, &a_cv, stats));
-    CHECK(batch_zero_cols(h, ws.L, ld, 1, stats));
-  }
-  auto quarter = [&](int q, int c0, int32_t** it, double** rr, int32_t** cv) {
-    *it = iters ? iters + (int64_t)q * n_cols + c0 : nullptr;
-    *rr = relres ? relres + (int64_t)q * n_cols + c0 : nullptr;
-    *cv = converged ? converged + (int64_t)q * n_cols + c0 : nullptr;
-  };
-  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
-    const int nc = std::min(chunk, n_cols - c0);
-    int32_t *q_it, *q_cv;
-    double* q_rr;
+  AdjointRun r;
+  CHECK(batch_adjoint_begin(h, ens ? "nx_ensemble_hvp" : "nx_batch_hvp", made_current,
+                            BatchParts{BatchParts::kHvp}, n_cols, edge_R, rtol, kind, n_obs,
+                            obs_rows, obs_w, &r));
+  const BatchWs& ws = r.ws;
+  const BatchStatus st{iters, relres, converged};
+  const bool one_adj = r.one_adj;  // (kind 0 is never Gauss-Newton)
+  const int64_t n = h->n_own, E = h->E, ld = ws.cols.ld;
+  for (int c0 = 0; c0 < n_cols; c0 += r.chunk) {
+    const int nc = std::min(r.chunk, n_cols - c0);
+    auto quarter = [&](int q) { return st.at((int64_t)q * n_cols + c0); };
     // forward: A x = b
     CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const, edge_R));
-    quarter(0, c0, &q_it, &q_rr, &q_cv);
-    CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.X, rtol, q_it, q_rr, q_cv, stats, ep));
-    CHECK(batch_zero_cols(h, ws.X, ld, nc, stats));  // b = 0: x = 0 exactly
-    if (kind == 1)
-      HIPCALL(hipMemcpyAsync(od.d, obs_d + (int64_t)c0 * n_obs, sizeof(double) * n_obs * nc,
-                             hipMemcpyHostToDevice, h->stream));
+    CHECK(r.solve(nc, ws.B, ws.X, quarter(0)));
+    if (kind == 1) CHECK(r.upload_data(obs_d, c0, nc));
     // adjoint: A l = c(x), and the objective
-    quarter(1, c0, &q_it, &q_rr, &q_cv);
     if (gn || one_adj) {  // the objective alone
-      hipLaunchKernelGGL(k_b_obs, dim3(1, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n, kind,
-                         n_obs, od.rows, od.w, kind ? od.d : nullptr, nullptr, ws.gJ);
-      HIPCALL(hipGetLastError());
-      h->b_launches += 1;
+      CHECK(r.observe(nc, ws.X, kind, nullptr, ws.gJ));
       if (one_adj)
-        for (int c = 0; c < nc; ++c) {
-          if (q_it) q_it[c] = a_it;
-          if (q_rr) q_rr[c] = a_rr;
-          if (q_cv) q_cv[c] = a_cv;
-        }
+        for (int c = 0; c < nc; ++c) quarter(1).set(c, r.a_it, r.a_rr, r.a_cv);
     } else {
-      hipLaunchKernelGGL(k_b_obs, dim3(slices, nc), dim3(kObsThreads), 0, h->stream, ws.X, ld, n,
-                         kind, n_obs, od.rows, od.w, kind ? od.d : nullptr, ws.C, ws.gJ);
-      HIPCALL(hipGetLastError());
-      h->b_launches += 1;
-      CHECK(batch_solve_cols(h, ws, nc, ws.C, ws.L, rtol, q_it, q_rr, q_cv, stats, ep));
-      CHECK(batch_zero_cols(h, ws.L, ld, nc, stats));
+      CHECK(r.observe(nc, ws.X, kind, ws.C, ws.gJ));
+      CHECK(r.solve(nc, ws.C, ws.L, quarter(1)));
     }
     // tangent: A xd = bd - Ad x (ws.B, ws.bc, ws.ef are free: the forward solve is done)
     if (dir_R)
@@ -15169,33 +15138,23 @@ int batch_hvp_run(nx_network* h, int32_t n_cols, const double* edge_R, const dou
       HIPCALL(hipMemsetAsync(ws.vR, 0, sizeof(double) * E * nc, h->stream));
     CHECK(batch_dir_rhs_chunk(h, ws, c0, nc, dir_bc, dir_f));
     CHECK(batch_mass_apply(h, ws, nc, ws.X, ld, ws.B));
-    quarter(2, c0, &q_it, &q_rr, &q_cv);
-    CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.Xd, rtol, q_it, q_rr, q_cv, stats, ep));
-    CHECK(batch_zero_cols(h, ws.Xd, ld, nc, stats));
+    CHECK(r.solve(nc, ws.B, ws.Xd, quarter(2)));
     // second-order adjoint: A ld = cd - Ad l (ws.C is free: the adjoint solve is done)
-    hipLaunchKernelGGL(k_b_obs_dir, dim3(slices, nc), dim3(kObsThreads), 0, h->stream, ws.Xd, ld,
-                       n, kind, n_obs, od.rows, od.w, ws.C);
+    hipLaunchKernelGGL(k_b_obs_dir, dim3(grid_of(n, kObsSpan), nc), dim3(kObsThreads), 0,
+                       h->stream, ws.Xd, ld, n, kind, n_obs, r.od.rows, r.od.w, ws.C);
     HIPCALL(hipGetLastError());
     h->b_launches += 1;
     if (!gn) CHECK(batch_mass_apply(h, ws, nc, ws.L, one_adj ? 0 : ld, ws.C));
-    quarter(3, c0, &q_it, &q_rr, &q_cv);
-    CHECK(batch_solve_cols(h, ws, nc, ws.C, ws.Ld, rtol, q_it, q_rr, q_cv, stats, ep));
-    CHECK(batch_zero_cols(h, ws.Ld, ld, nc, stats));
+    CHECK(r.solve(nc, ws.C, ws.Ld, quarter(3)));
     CHECK(batch_edge_form2(h, ws, nc, gn ? nullptr : ws.L, one_adj ? 0 : ld));
-    // the chunk's outputs straight into the caller's arrays (no staging, no host unpack)
-    auto out = [&](double* dst, const double* src, int64_t per) {
-      return dst ? hipMemcpyAsync(dst + (int64_t)c0 * per, src, sizeof(double) * per * nc,
-                                  hipMemcpyDeviceToHost, h->stream)
-                 : hipSuccess;
-    };
-    HIPCALL(out(value, ws.gJ, 1));
-    HIPCALL(out(hess_R, ws.HR, E));
-    HIPCALL(out(hess_f, ws.Hf, E));
-    HIPCALL(out(hess_bc, ws.Hbc, 2 * E));
+    HIPCALL(r.out(value, ws.gJ, 1, c0, nc));
+    HIPCALL(r.out(hess_R, ws.HR, E, c0, nc));
+    HIPCALL(r.out(hess_f, ws.Hf, E, c0, nc));
+    HIPCALL(r.out(hess_bc, ws.Hbc, 2 * E, c0, nc));
     if (!gn) {
-      HIPCALL(out(grad_R, ws.gR, E));
-      HIPCALL(out(grad_f, ws.gf, E));
-      HIPCALL(out(grad_bc, ws.gbc, 2 * E));
+      HIPCALL(r.out(grad_R, ws.gR, E, c0, nc));
+      HIPCALL(r.out(grad_f, ws.gf, E, c0, nc));
+      HIPCALL(r.out(grad_bc, ws.gbc, 2 * E, c0, nc));
     }
     HIPCALL(hipStreamSynchronize(h->stream));
   }
@@ -15242,7 +15201,7 @@ NX_API int nx_ensemble_solve(nx_network_t* h, int32_t n_cols, const double* edge
                              const double* edge_bc, const double* edge_f, const double* f_const,
                              double rtol, int32_t order, double* out, int32_t* iters,
                              double* relres, int32_t* converged) {
-  const int made_current = (h && (h->pend_lhs || h->pend_rhs) && h->E > 0) ? 1 : 0;
+  const int made_current = batch_pending(h);
   CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
   CHECK(batch_check_args(h, n_cols, edge_bc, out));
   if (!edge_R) return fail(NX_ERR_ARG, "edge_R is NULL");
@@ -15263,33 +15222,19 @@ NX_API int nx_ensemble_solve(nx_network_t* h, int32_t n_cols, const double* edge
   h->ecyc_unit = h->ecyc_storage = 0;
   h->b_launches = made_current;  // (the handle's lumped mass is not read: no ensure_dq)
   int chunk = 0;
-  CHECK(batch_workspace(h, n_cols, &chunk, false, true));
+  CHECK(batch_workspace(h, n_cols, &chunk, BatchParts{BatchParts::kEns}));
   h->b_chunk = chunk;
-  const BatchWs ws = batch_carve(h, h->bws_cap);
+  const BatchWs ws = batch_carve(h);
   const BatchEns be = batch_ens(h, ws);
-  const int64_t n = h->n_own, ld = ws.cols.ld;
-  std::vector<double> stats;
-  for (int c0 = 0; c0 < n_cols; c0 += chunk) {
-    const int nc = std::min(chunk, n_cols - c0);
-    CHECK(batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const, edge_R));
-    CHECK(batch_solve_cols(h, ws, nc, ws.B, ws.X, rtol, iters ? iters + c0 : nullptr,
-                           relres ? relres + c0 : nullptr, converged ? converged + c0 : nullptr,
-                           stats, &be));
-    const double* src = ws.X;
-    if (order != 0) {
-      hipLaunchKernelGGL(k_b_gather, dim3(grid_of(n, kBlock), nc), dim3(kBlock), 0, h->stream, ws.X,
-                         ld, h->out_idx, n, ws.D);
-      HIPCALL(hipGetLastError());
-      h->b_launches += 1;
-      src = ws.D;
-    }
-    HIPCALL(hipMemcpyAsync(out + (int64_t)c0 * n, src, sizeof(double) * n * nc,
-                           hipMemcpyDeviceToHost, h->stream));
-    HIPCALL(hipStreamSynchronize(h->stream));
-    for (int c = 0; c < nc; ++c)  // b = 0: x = 0 exactly (no division by ||b||)
-      if (stats[2 * c + 1] == 0.0) std::fill_n(out + (int64_t)(c0 + c) * n, n, 0.0);
-  }
-  return NX_OK;
+  const BatchStatus st{iters, relres, converged};
+  return batch_chunks(
+      h, ws, n_cols, chunk, order, out,
+      [&](int c0, int nc) {
+        return batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const, edge_R);
+      },
+      [&](int c0, int nc, std::vector<double>& stats) {
+        return batch_solve_p1(h, ws, nc, ws.B, ws.X, rtol, st.at(c0), stats, &be);
+      });
 }
 
 NX_API int nx_stash_solution(nx_network_t* h, int32_t restore) {
