@@ -530,6 +530,69 @@ int nx_fe_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc, cons
                     const double* f_const, double* out);
 
 /*
+ * nx_batch_solve for continuous pressure (k > m >= 1) on a forest: many boundary / source
+ * scenarios against the current matrix in one batched pass of the node-condensed direct solve
+ * (nx_fe_set_cp). The single solve factors the matrix again on every pass of every scenario;
+ * here what depends on the matrix alone is formed once per call and a chunk of columns sweeps
+ * its right-hand sides only.
+ *
+ * nx_cp_batch_supported: *ok = 1 when nx_cp_batch_solve takes the batched kernels on this
+ * handle, else 0: an nx_create_fe handle with the node-condensed solve attached
+ * (nx_fe_set_cp), nx_set_solver(h, 1, 1), one rank (no nx_fe_cp_ranks, not in a group, no
+ * ghosts), no chords attached (nx_fe_cp_set_cycles) and at least one edge. (k, 0) and P1/DG0
+ * handles give 0.
+ *
+ * nx_cp_batch_solve: the arguments of nx_fe_batch_solve; out = n_cols x n_rows. NX_ERR_STATE
+ * where nx_cp_batch_supported says 0, where the matrix has not been assembled for the
+ * resident coefficients, or order != 0 without an output map; NX_ERR_ARG as nx_batch_solve
+ * (and maxit < 1). A pending deferred assembly is flushed first.
+ * Once per call (the factor stage; it writes the batch's workspace alone):
+ *   k_cp_b_factor     k_cp_edge's sweep without a right-hand side: per vertex the pivot
+ *                     inverse and couplings Pi | C | W (16 doubles, cp_fac's edge-minor
+ *                     layout), per edge the 4 x 4 border block Se
+ *   the node forest's up-sweep of the single solve (k_cp_nodes / k_cp_nodes_rec / k_cp_level)
+ *                     on those blocks and a zero right-hand side: every node's pivot inverse
+ * Per chunk (the chunk rule is nx_batch_solve's; a grid covers columns as well as edges or
+ * nodes, kCpTile = 4 columns per work item):
+ *   k_fe_b_rhs        every column's rhs, bit-equal to nx_assemble's rhs of that scenario
+ *   k_cp_b_fwd        per edge: the cells' interior rhs condensed onto the vertices, the rho
+ *                     chain; z = Pi rho per vertex and ge per edge, per column
+ *   k_cp_b_nodes / k_cp_b_level   the node forest on right-hand sides only, up (h_n = b rows +
+ *                     sum ge - the children's terms; the node's own term B^T P^-1 h_n) and
+ *                     down (x_n = P_n^-1 (h_n - B x_parent)), over the single solve's level runs
+ *   k_cp_b_back       per edge: the vertex recursion and the cells' interiors into the chunk's
+ *                     columns (added in a refinement pass); the node rows by cp_nown's edge
+ *   k_b_res / k_b_norms   the true residual against this handle's CSR
+ *   k_b_gather        when order != 0, then one copy per chunk
+ * The workspace is the handle's columns (nx_batch_solve's) plus, owned by the handle, the
+ * call's factors (16 (N + 1) E + 20 E + 12 nodes + n_rows doubles) and per column
+ * 2 (N + 1) E + 4 E + 6 nodes doubles; allocated on first use, freed by nx_destroy and by
+ * nx_fe_set_cp. The handle's own factors, node arrays, coefficients, rhs, x, tmp, published
+ * state and snapshots are left as they were.
+ * Per column the policy is nx_fe_batch_solve's: one refinement pass over the columns above
+ * rtol, then the single-column route (fe_cp_solve, then MINRES capped at maxit), the refined
+ * column standing where that ends unconverged and no better; b = 0 gives x = 0, relres = 0,
+ * converged = 1. A column's bits do not depend on the other columns, its position, n_cols or
+ * the chunk size.
+ *
+ * Launches (nx_get_batch_info): F + chunks x S, plus 1 for a flushed assembly. With U / D the
+ * launches of the node forest's up / down pass -- one per run of levels: U = D = 1 where no
+ * level of the forest holds more than 128 nodes -- the factor stage is F = 1 + U and a chunk
+ * is S = 6 + U + D with order != 0 (rhs, forward, up, down, back, residual, norms, gather),
+ * 5 + U + D with order = 0, whatever its column count. A chunk with a refinement pass adds
+ * 4 + U + D.
+ *
+ * nx_cp_batch_rhs (test hook): k_fe_b_rhs alone; out = n_cols x n_rows, device layout.
+ */
+int nx_cp_batch_supported(nx_network_t* h, int32_t* ok);
+int nx_cp_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                      const double* edge_f, const double* f_const, double rtol, int32_t maxit,
+                      int32_t order, double* out, int32_t* iters, double* relres,
+                      int32_t* converged);
+int nx_cp_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc, const double* edge_f,
+                    const double* f_const, double* out);
+
+/*
  * Adjoint gradients of an observed-row objective with respect to every edge's R, every
  * boundary value and every edge's source, for n_cols scenarios, in two batched direct solves;
  * no solution leaves the device (the reference has no counterpart). Per scenario j over the

@@ -59,6 +59,10 @@ _SIGS = {
     "nx_fe_batch_solve": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _pd, _pi32, _pd,
                                     _pi32]),
     "nx_fe_batch_rhs": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd]),
+    "nx_cp_batch_supported": (C.c_int, [_h, _pi32]),
+    "nx_cp_batch_solve": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _pd, _pi32, _pd,
+                                    _pi32]),
+    "nx_cp_batch_rhs": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd]),
     "nx_batch_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd, _pd,
                                     _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
     "nx_ensemble_supported": (C.c_int, [_h, _pi32]),
@@ -491,6 +495,38 @@ class Handle:
         B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
         out = np.empty((B, self.n_rows), dtype=np.float64)
         check(lib().nx_fe_batch_rhs(self.ptr, B, _ptr(bc, C.c_double), _ptr(ef, C.c_double),
+                                    _ptr(fc, C.c_double), _ptr(out, C.c_double)))
+        return out
+
+    def cp_batch_supported(self) -> bool:
+        """Whether ``nx_cp_batch_solve`` takes the batched kernels on this continuous-pressure
+        handle."""
+        ok = C.c_int32(0)
+        check(lib().nx_cp_batch_supported(self.ptr, C.byref(ok)))
+        return bool(ok.value)
+
+    def cp_batch_solve(self, edge_bc, edge_f=None, f_const=None, rtol: float = 1e-12,
+                       maxit: int = 50000, blocks: bool = True):
+        """``nx_cp_batch_solve``: as :meth:`batch_solve` for a continuous-pressure handle with
+        the node-condensed solve attached; ``maxit`` caps the MINRES of a column's
+        single-column fallback."""
+        B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
+        out = self.batch_output(B)
+        it = np.zeros(B, dtype=np.int32)
+        rr = np.zeros(B, dtype=np.float64)
+        cv = np.zeros(B, dtype=np.int32)
+        check(lib().nx_cp_batch_solve(self.ptr, B, _ptr(bc, C.c_double), _ptr(ef, C.c_double),
+                                      _ptr(fc, C.c_double), float(rtol), int(maxit),
+                                      1 if blocks else 0, _ptr(out, C.c_double),
+                                      _ptr(it, C.c_int32), _ptr(rr, C.c_double),
+                                      _ptr(cv, C.c_int32)))
+        return out, it, rr, cv.astype(bool)
+
+    def cp_batch_rhs(self, edge_bc, edge_f=None, f_const=None) -> np.ndarray:
+        """``nx_cp_batch_rhs`` (test hook): the scenarios' right-hand sides, device layout."""
+        B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
+        out = np.empty((B, self.n_rows), dtype=np.float64)
+        check(lib().nx_cp_batch_rhs(self.ptr, B, _ptr(bc, C.c_double), _ptr(ef, C.c_double),
                                     _ptr(fc, C.c_double), _ptr(out, C.c_double)))
         return out
 

@@ -8530,6 +8530,12 @@ struct nx_network {
   void* fe_bws = nullptr;
   int fe_bws_cap = 0;
   size_t fe_bws_bytes = 0;
+  // nx_cp_batch_solve on a continuous-pressure handle: bws holds this handle's columns; cp_bws
+  // the call's factors and the sweeps' per-column scratch (cp_layout), owned here: freed in
+  // nx_destroy and when nx_fe_set_cp detaches or attaches again
+  void* cp_bws = nullptr;
+  int cp_bws_cap = 0;
+  size_t cp_bws_bytes = 0;
 };
 
 struct nx_group {
@@ -11002,6 +11008,14 @@ NX_API int nx_fe_templates(nx_network_t* h, int32_t* n_shapes, int32_t* rows_per
   return NX_OK;
 }
 
+// nx_cp_batch_solve's own part of the workspace (the factors belong to the attachment)
+static void cp_batch_free(nx_network* h) {
+  if (h->cp_bws) (void)hipFree(h->cp_bws);
+  h->cp_bws = nullptr;
+  h->cp_bws_cap = 0;
+  h->cp_bws_bytes = 0;
+}
+
 NX_API int nx_destroy(nx_network_t* h) {
   if (h) h->pend_lhs = h->pend_rhs = 0;  // nothing to assemble for a dying handle
   if (h == nullptr) return NX_OK;
@@ -11043,6 +11057,7 @@ NX_API int nx_destroy(nx_network_t* h) {
     if (p) (void)hipFree(p);
   if (h->bws) (void)hipFree(h->bws);
   if (h->fe_bws) (void)hipFree(h->fe_bws);
+  cp_batch_free(h);
   if (h->gobs) (void)hipFree(h->gobs);
   if (h->stash) (void)hipFree(h->stash);
   std::free(h->stash_state);
@@ -12989,58 +13004,88 @@ bool cp_pipe_on() {
   return e == nullptr || std::atoi(e) != 0;
 }
 
-// The node forest's solve: levels of more than kCpWide nodes as grid launches (a thread per
-// node), the runs of narrower levels in one workgroup each; up deepest first, then down.
-void cp_nodes_launch(nx_network* h, const CpArgs& a, const CpTree& tr, const double* b) {
+// The node forest's level runs in one pass's order (up: deepest first): levels of more than
+// kCpWide nodes alone (on_wide(L): a grid launch, a thread per node), a run of wide levels in
+// subtree chunks (on_run(run): one workgroup per chunk), consecutive narrower levels together
+// (on_narrow(La, Lb, pipe): levels [La, Lb) in one workgroup; pipe: the pipelined kernel's
+// conditions hold). rec: the node records are in use. Returns the number of runs (launches).
+template <class Run, class Wide, class Narrow>
+int cp_level_walk(const nx_network* h, bool rec, int up, Run on_run, Wide on_wide,
+                  Narrow on_narrow) {
   const std::vector<int>& lo = h->cp_lev_host;
   const int nl = h->cp_nlev;
   // (pipelined: levels of more than 1024 nodes go to the grid launches)
-  const int wmax = tr.rec != nullptr && cp_pipe_on() ? 1024 : kCpWide;
+  const int wmax = rec && cp_pipe_on() ? 1024 : kCpWide;
   auto wide = [&](int L) { return lo[L + 1] - lo[L] > wmax; };
-  for (int up = 1; up >= 0; --up) {
-    // runs of levels in the pass's order: a wide level alone, consecutive narrow ones together
-    int k = 0;
-    while (k < nl) {
-      const int L = up ? nl - 1 - k : k;
-      const nx_network::CpRun* run = nullptr;  // a run of wide levels in subtree chunks
-      if (wmax == 1024)
-        for (const auto& r : h->cp_runs)
-          if (up ? L == r.L1 - 1 : L == r.L0) run = &r;
-      if (run != nullptr) {
-        hipLaunchKernelGGL(k_cp_nodes_rec, dim3(run->nch), dim3(kCpChunk), 0, h->stream, a, tr,
-                           b, h->cp_rng + run->off, run->L0, run->L1, up);
-        k += run->L1 - run->L0;
-        continue;
-      }
-      if (wide(L)) {
+  int launches = 0;
+  // runs of levels in the pass's order: a wide level alone, consecutive narrow ones together
+  int k = 0;
+  while (k < nl) {
+    const int L = up ? nl - 1 - k : k;
+    const nx_network::CpRun* run = nullptr;  // a run of wide levels in subtree chunks
+    if (wmax == 1024)
+      for (const auto& r : h->cp_runs)
+        if (up ? L == r.L1 - 1 : L == r.L0) run = &r;
+    ++launches;
+    if (run != nullptr) {
+      on_run(*run);
+      k += run->L1 - run->L0;
+      continue;
+    }
+    if (wide(L)) {
+      on_wide(L);
+      ++k;
+      continue;
+    }
+    // (a narrow run ends at a wide level or where a chunked run starts)
+    auto run_at = [&](int Lq) {
+      if (wmax != 1024) return false;
+      for (const auto& r : h->cp_runs)
+        if (up ? Lq == r.L1 - 1 : Lq == r.L0) return true;
+      return false;
+    };
+    int k1 = k;
+    while (k1 < nl && !wide(up ? nl - 1 - k1 : k1) && (k1 == k || !run_at(up ? nl - 1 - k1 : k1)))
+      ++k1;
+    const int La = up ? nl - k1 : k, Lb = up ? nl - k : k1;  // levels [La, Lb)
+    // (the pipelined kernel: records, at most 1024 nodes per level and kCpPipeLv levels)
+    bool pipe = rec && Lb - La <= kCpPipeLv && cp_pipe_on();
+    for (int Lq = La; Lq < Lb && pipe; ++Lq)
+      pipe = lo[Lq + 1] - lo[Lq] <= 1024 && h->cp_lev_full[Lq];
+    on_narrow(La, Lb, pipe);
+    k = k1;
+  }
+  return launches;
+}
+
+// One pass of the node forest's solve (up: the eliminations, deepest level first; else the
+// back-substitution, root first) over cp_level_walk's runs; returns its launches.
+int cp_nodes_pass(nx_network* h, const CpArgs& a, const CpTree& tr, const double* b, int up) {
+  const std::vector<int>& lo = h->cp_lev_host;
+  return cp_level_walk(
+      h, tr.rec != nullptr, up,
+      [&](const nx_network::CpRun& run) {
+        hipLaunchKernelGGL(k_cp_nodes_rec, dim3(run.nch), dim3(kCpChunk), 0, h->stream, a, tr, b,
+                           h->cp_rng + run.off, run.L0, run.L1, up);
+      },
+      [&](int L) {
         const int n = lo[L + 1] - lo[L];
         hipLaunchKernelGGL(k_cp_level, dim3(grid_of(n, 256)), dim3(256), 0, h->stream, a, tr, b,
                            lo[L], lo[L + 1], up);
-        ++k;
-        continue;
-      }
-      // (a narrow run ends at a wide level or where a chunked run starts)
-      auto run_at = [&](int Lq) {
-        if (wmax != 1024) return false;
-        for (const auto& r : h->cp_runs)
-          if (up ? Lq == r.L1 - 1 : Lq == r.L0) return true;
-        return false;
-      };
-      int k1 = k;
-      while (k1 < nl && !wide(up ? nl - 1 - k1 : k1) && (k1 == k || !run_at(up ? nl - 1 - k1 : k1)))
-        ++k1;
-      const int La = up ? nl - k1 : k, Lb = up ? nl - k : k1;  // levels [La, Lb)
-      // (the pipelined kernel: records, at most 1024 nodes per level and kCpPipeLv levels)
-      bool pipe = tr.rec != nullptr && Lb - La <= kCpPipeLv && cp_pipe_on();
-      for (int L = La; L < Lb && pipe; ++L) pipe = lo[L + 1] - lo[L] <= 1024 && h->cp_lev_full[L];
-      if (pipe)
-        hipLaunchKernelGGL(k_cp_nodes_rec, dim3(1), dim3(1024), 0, h->stream, a, tr, b,
-                           (const int*)nullptr, La, Lb, up);
-      else
-        hipLaunchKernelGGL(k_cp_nodes, dim3(1), dim3(1024), 0, h->stream, a, tr, b, La, Lb, up);
-      k = k1;
-    }
-  }
+      },
+      [&](int La, int Lb, bool pipe) {
+        if (pipe)
+          hipLaunchKernelGGL(k_cp_nodes_rec, dim3(1), dim3(1024), 0, h->stream, a, tr, b,
+                             (const int*)nullptr, La, Lb, up);
+        else
+          hipLaunchKernelGGL(k_cp_nodes, dim3(1), dim3(1024), 0, h->stream, a, tr, b, La, Lb, up);
+      });
+}
+
+// The node forest's solve: up deepest first, then down.
+void cp_nodes_launch(nx_network* h, const CpArgs& a, const CpTree& tr, const double* b) {
+  cp_nodes_pass(h, a, tr, b, 1);
+  cp_nodes_pass(h, a, tr, b, 0);
 }
 
 // A graph with cycles: the capacitance matrix of the chords' correction, once per version
@@ -14828,6 +14873,755 @@ NX_API int nx_fe_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge
             [&](int ncs) { return fe_batch_apply(h, ws, wa, nullptr, ncs, ws.B, ws.X, 0, c0 == 0); },
             [&](const int* list, int nr) {
               return fe_batch_apply(h, ws, wa, list, nr, ws.R, ws.X, 1, false);
+            },
+            BatchFallback{BatchFallback::kKeep, maxit});
+      });
+}
+
+// ---- nx_cp_batch_solve: nx_batch_solve for a continuous-pressure handle (k > m >= 1) on a
+// forest, through its node-condensed direct solve (nx_fe_set_cp) split in two: what depends on
+// the matrix alone -- every vertex's pivot inverse and couplings, every edge's border block,
+// every node's pivot inverse -- is formed once per call (the factor stage), and a chunk's
+// columns sweep their right-hand sides only. Everything the batch writes lives in its own
+// workspace (cp_bws): the handle's cp_fac / cp_se / cp_Pinv / cp_hv / cp_ctr / cp_xn stay the
+// single-column solve's, which a fallback column runs.
+namespace {
+
+constexpr int kCpTile = 4;    // columns a work item carries (12 doubles of state per column)
+constexpr int kCpBFac = 16;   // per vertex: Pi 4 | C 4 | W 8, un-multiplied
+
+struct CpCols {
+  int64_t col[kCpTile];
+};
+__device__ __forceinline__ CpCols cp_cols(const int* __restrict__ list, int c0, int nt) {
+  CpCols t;
+#pragma unroll
+  for (int k = 0; k < kCpTile; ++k) t.col[k] = k < nt ? (list ? list[c0 + k] : c0 + k) : 0;
+  return t;
+}
+
+// a: the handle's tables with fac / se pointing at the batch's factors (kCpBFac per vertex in
+// cp_fac's edge-minor layout; Se 16 | zeros 4 per edge). Column c of B / X starts at c * ld, of
+// the per-column scratch at c times its own length: z 2 (N + 1) E (edge-minor), ge 4 E, hv /
+// ct / xn 2 nn (the node's condensed rhs, its term for its parent, its values).
+struct CpBatch {
+  CpArgs a;
+  const double* Pinv;  // 4 per node (the factor stage's)
+  const int* list;     // the columns a launch serves (device), or null: 0 .. ncols - 1
+  int ncols, nn;
+  const double* B;
+  double* X;
+  int64_t ld;
+  double *z, *ge, *hv, *ct, *xn;
+};
+
+// k_cp_edge's sweep without a right-hand side: per vertex Pi | C | W as the sweep uses them
+// (the last cell's columns of C already moved to W), per edge Se (and a zero ge, so the node
+// kernels of the single solve factor the forest from these blocks on a zero right-hand side).
+__global__ __launch_bounds__(256) void k_cp_b_factor(CpArgs a) {
+#pragma clang fp contract(off)
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.E) return;
+  const int N = a.N;
+  const double* hl = a.cellh + e * N;
+  const double* Kh = a.cst;
+  const int au = a.eb[4 * e + 2], av = a.eb[4 * e + 3];
+  const double R = a.edge_R[e];
+  double* fe = a.fac + e;
+  const int64_t E = a.E;
+  double P[4] = {0.0, 0.0, 0.0, 1.0}, W[8] = {0.0};
+  W[1] = (double)au;  // q_0 <-> lam_u
+  double Sb[16] = {0.0};
+  const int tV[4] = {1, -1, 1, -1};
+  for (int c = 0; c < N; ++c) {
+    const double s = R * hl[c];
+    double K[16];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) K[4 * r + q] = Kh[4 * r + q] * cp_pow(s, (tV[r] + tV[q]) / 2);
+    double C[4], Pn[4], Wn[8] = {0.0};
+    if (c == 0) {  // the left p is the border p_u
+      P[0] += K[0];
+      W[0] += K[1];
+      Sb[0] += K[5];
+      C[0] = K[2]; C[1] = K[3]; C[2] = 0.0; C[3] = 0.0;
+      Wn[0] = K[9];   // right q <-> p_u
+      Wn[4] = K[13];  // right p <-> p_u
+    } else {
+      P[0] += K[0]; P[1] += K[1]; P[2] += K[4]; P[3] += K[5];
+      C[0] = K[2]; C[1] = K[3]; C[2] = K[6]; C[3] = K[7];
+    }
+    if (c + 1 < N) {
+      Pn[0] = K[10]; Pn[1] = K[11]; Pn[2] = K[14]; Pn[3] = K[15];
+    } else {  // the right p is the border p_v
+      Sb[10] += K[15];
+      if (c == 0) {  // (N = 1: p_u <-> p_v)
+        Sb[2] += K[7];
+        Sb[8] += K[13];
+      }
+      Wn[2] += K[11];      // right q <-> p_v
+      Wn[3] = (double)av;  // right q <-> lam_v
+      Wn[4] = 0.0;         // (the right p slot is a dummy)
+      W[2] += C[1];        // left rows <-> p_v
+      W[6] += C[3];
+      C[1] = 0.0;
+      C[3] = 0.0;
+      Pn[0] = K[10]; Pn[1] = 0.0; Pn[2] = 0.0; Pn[3] = 1.0;
+    }
+    double Pi[4];
+    inv2(P, Pi);
+    double X[4], Y[8];  // Pi C, Pi W
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) X[2 * r + q] = Pi[2 * r] * C[q] + Pi[2 * r + 1] * C[2 + q];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) Y[4 * r + q] = Pi[2 * r] * W[q] + Pi[2 * r + 1] * W[4 + q];
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {  // C^T X, C^T Y into the right vertex
+#pragma unroll
+      for (int q = 0; q < 2; ++q) Pn[2 * r + q] -= C[r] * X[q] + C[2 + r] * X[2 + q];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) Wn[4 * r + q] -= C[r] * Y[q] + C[2 + r] * Y[4 + q];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)  // W^T Y into the border
+#pragma unroll
+      for (int q = 0; q < 4; ++q) Sb[4 * r + q] -= W[r] * Y[q] + W[4 + r] * Y[4 + q];
+    double* f = fe + (int64_t)c * kCpBFac * E;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i * E] = Pi[i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[(4 + i) * E] = C[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[(8 + i) * E] = W[i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) P[i] = Pn[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) W[i] = Wn[i];
+  }
+  {  // the last vertex (no vertex after it: C = 0)
+    double Pi[4];
+    inv2(P, Pi);
+    double Y[8];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) Y[4 * r + q] = Pi[2 * r] * W[q] + Pi[2 * r + 1] * W[4 + q];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) Sb[4 * r + q] -= W[r] * Y[q] + W[4 + r] * Y[4 + q];
+    double* f = fe + (int64_t)N * kCpBFac * E;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i * E] = Pi[i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[(4 + i) * E] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[(8 + i) * E] = W[i];
+  }
+  double* o = a.se + 20 * e;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) o[i] = Sb[i];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) o[16 + i] = 0.0;
+}
+
+// The forward sweep's right-hand side part, one edge and one tile of columns per thread
+// (blockIdx.y: the tile): per column k_cp_edge's rV, rho, rn and gb in its order, the vertex
+// factors loaded once per tile; z = Pi rho per vertex and ge per edge written per column.
+__global__ __launch_bounds__(64) void k_cp_b_fwd(CpBatch p) {
+#pragma clang fp contract(off)
+  const CpArgs& a = p.a;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.E) return;
+  const int c0 = (int)blockIdx.y * kCpTile;
+  const int nt = min(kCpTile, p.ncols - c0);
+  const CpCols cl = cp_cols(p.list, c0, nt);
+  const int N = a.N, k = a.k, m = a.m, nI = a.nI;
+  const int nf = k * N + 1, per = nf + m * N - 1;
+  const int64_t base = e * (int64_t)per, E = a.E;
+  const double* hl = a.cellh + e * N;
+  const double* Ch = a.cst + 16;
+  const double R = a.edge_R[e];
+  const double* fe = a.fac + e;
+  const int64_t zld = 2 * (int64_t)(N + 1) * E;
+  auto prow = [&](int j) { return nf + j - 1; };  // interior pressure position j (local row)
+  const double* bl[kCpTile];
+  double rho[kCpTile][2], gb[kCpTile][4];
+#pragma unroll
+  for (int t = 0; t < kCpTile; ++t) {
+    bl[t] = p.B + cl.col[t] * p.ld + base;
+    rho[t][0] = bl[t][0];
+    rho[t][1] = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) gb[t][r] = 0.0;
+  }
+  for (int c = 0; c <= N; ++c) {
+    double f[kCpBFac];
+    const double* fp = fe + (int64_t)c * kCpBFac * E;
+#pragma unroll
+    for (int q = 0; q < kCpBFac; ++q) f[q] = fp[q * E];
+    const double* Pi = f;
+    const double* C = f + 4;
+    const double* W = f + 8;
+    double rn[kCpTile][2];
+    if (c < N) {
+      const double s = R * hl[c];
+      const double si = 1.0 / s;
+      double rV[kCpTile][4];
+#pragma unroll
+      for (int t = 0; t < kCpTile; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rV[t][r] = 0.0;
+      for (int i = 0; i < nI; ++i) {  // the cell's interior rhs condensed onto its vertices
+        const int ti = a.tI[i];
+        const int row = ti > 0 ? c * k + 1 + i : prow(c * m + 1 + (i - (k - 1)));
+        // (flux rows r = 0, 2: exponent (1 - ti) / 2; pressure rows r = 1, 3: (-1 - ti) / 2)
+        const double pq = ti > 0 ? 1.0 : s, pp = ti > 0 ? si : 1.0;
+        const double cf[4] = {Ch[i] * pq, Ch[nI + i] * pp, Ch[2 * nI + i] * pq,
+                              Ch[3 * nI + i] * pp};
+#pragma unroll
+        for (int t = 0; t < kCpTile; ++t) {
+          const double bi = bl[t][row];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) rV[t][r] -= cf[r] * bi;
+        }
+      }
+      const int rq = c + 1 < N ? k * (c + 1) : nf - 1;
+      const int rp = c + 1 < N ? prow(m * (c + 1)) : 0;
+#pragma unroll
+      for (int t = 0; t < kCpTile; ++t) {
+        rho[t][0] += rV[t][0];
+        if (c == 0) gb[t][0] += rV[t][1];  // the left p is the border p_u
+        else rho[t][1] += rV[t][1];
+        rn[t][0] = rV[t][2] + bl[t][rq];
+        if (c + 1 < N) {
+          rn[t][1] = rV[t][3] + bl[t][rp];
+        } else {  // the right p is the border p_v
+          gb[t][2] += rV[t][3];
+          rn[t][1] = 0.0;
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < kCpTile; ++t) {
+      const double z0 = Pi[0] * rho[t][0] + Pi[1] * rho[t][1];
+      const double z1 = Pi[2] * rho[t][0] + Pi[3] * rho[t][1];
+      if (c < N) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) rn[t][r] -= C[r] * z0 + C[2 + r] * z1;
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) gb[t][r] -= W[r] * z0 + W[4 + r] * z1;
+      if (t < nt) {
+        double* zp = p.z + cl.col[t] * zld + (int64_t)(2 * c) * E + e;
+        zp[0] = z0;
+        zp[E] = z1;
+      }
+      if (c < N) {
+        rho[t][0] = rn[t][0];
+        rho[t][1] = rn[t][1];
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < kCpTile; ++t)
+    if (t < nt) {
+      double* o = p.ge + cl.col[t] * 4 * E + 4 * e;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = gb[t][r];
+    }
+}
+
+// One node's condensed right-hand side, one tile of columns: h_n = b rows + sum ge - sum of
+// the children's terms, in cp_node_up's order; then its own term B^T (P^-1 h) for its parent
+// (cp_up_term's expressions). i: the node's level-order index.
+__device__ __forceinline__ void cp_b_node_up(const CpBatch& p, const CpTree& t, int i,
+                                             const CpCols& cl, int nt) {
+#pragma clang fp contract(off)
+  const CpArgs& a = p.a;
+  int n, pr, lr, ni = -1, nc = -1, pp, pe, pend;
+  int r[kCpRecPad];
+  if (t.rec != nullptr) {
+    const int4* q4 = reinterpret_cast<const int4*>(t.rec + (int64_t)kCpRecPad * i);
+#pragma unroll
+    for (int w = 0; w < kCpRecPad / 4; ++w) {
+      const int4 v = q4[w];
+      r[4 * w] = v.x;
+      r[4 * w + 1] = v.y;
+      r[4 * w + 2] = v.z;
+      r[4 * w + 3] = v.w;
+    }
+    n = r[0];
+    pr = r[1];
+    lr = r[2];
+    ni = r[3];
+    nc = r[kCpRecC];
+    pp = r[kCpRecP];
+    pe = r[kCpRecP + 1];
+    pend = r[kCpRecP + 2];
+  } else {
+    n = t.order[i];
+    pr = a.nrow[2 * n];
+    lr = a.nrow[2 * n + 1];
+    pp = t.parent[3 * n];
+    pe = t.parent[3 * n + 1];
+    pend = t.parent[3 * n + 2];
+  }
+  const int64_t E = a.E, nn2 = 2 * (int64_t)p.nn;
+  double g[kCpTile][2];
+#pragma unroll
+  for (int k = 0; k < kCpTile; ++k) {
+    const double* b = p.B + cl.col[k] * p.ld;
+    g[k][0] = b[pr];
+    g[k][1] = lr >= 0 ? b[lr] : 0.0;
+  }
+  auto edge = [&](int e, int end) {
+#pragma unroll
+    for (int k = 0; k < kCpTile; ++k) {
+      const double* q = p.ge + cl.col[k] * 4 * E + 4 * (int64_t)e + 2 * end;
+      g[k][0] += q[0];
+      g[k][1] += q[1];
+    }
+  };
+  auto child = [&](int c) {
+#pragma unroll
+    for (int k = 0; k < kCpTile; ++k) {
+      const double* q = p.ct + cl.col[k] * nn2 + 2 * (int64_t)c;
+      g[k][0] -= q[0];
+      g[k][1] -= q[1];
+    }
+  };
+  if (ni >= 0) {
+#pragma unroll
+    for (int j = 0; j < kCpRecInc; ++j)
+      if (j < ni) edge(r[4 + 2 * j], r[5 + 2 * j]);
+  } else {
+    for (int j = t.inc_off[n]; j < t.inc_off[n + 1]; ++j) edge(t.inc[2 * j], t.inc[2 * j + 1]);
+  }
+  if (nc >= 0) {
+#pragma unroll
+    for (int j = 0; j < kCpRecCh; ++j)
+      if (j < nc) child(r[kCpRecC + 1 + 3 * j]);
+  } else {
+    for (int j = t.child_off[n]; j < t.child_off[n + 1]; ++j) child(t.child[j]);
+  }
+  double Bk[4] = {0.0, 0.0, 0.0, 0.0}, Pc[4] = {0.0, 0.0, 0.0, 0.0};
+  if (pp >= 0) {
+    cp_block(a.se, pe, pend, 1 - pend, Bk);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) Pc[q] = p.Pinv[4 * (int64_t)n + q];
+  }
+#pragma unroll
+  for (int k = 0; k < kCpTile; ++k)
+    if (k < nt) {
+      double* hq = p.hv + cl.col[k] * nn2 + 2 * (int64_t)n;
+      hq[0] = g[k][0];
+      hq[1] = g[k][1];
+      if (pp >= 0) {
+        const double z0 = Pc[0] * g[k][0] + Pc[1] * g[k][1];
+        const double z1 = Pc[2] * g[k][0] + Pc[3] * g[k][1];
+        double* cq = p.ct + cl.col[k] * nn2 + 2 * (int64_t)n;
+        cq[0] = Bk[0] * z0 + Bk[2] * z1;
+        cq[1] = Bk[1] * z0 + Bk[3] * z1;
+      }
+    }
+}
+
+// ... and its back-substitution x_n = P_n^-1 (h_n - B x_parent), cp_node_down's expressions.
+__device__ __forceinline__ void cp_b_node_down(const CpBatch& p, const CpTree& t, int i,
+                                               const CpCols& cl, int nt) {
+#pragma clang fp contract(off)
+  const CpArgs& a = p.a;
+  int n, pp, pe, pend;
+  if (t.rec != nullptr) {
+    const int* q = t.rec + (int64_t)kCpRecPad * i;
+    const int4 h = *reinterpret_cast<const int4*>(q);
+    const int4 v = *reinterpret_cast<const int4*>(q + 20);  // [22] parent, [23] its edge
+    const int4 w = *reinterpret_cast<const int4*>(q + 24);  // [24] this node's end of it
+    n = h.x;
+    pp = v.z;
+    pe = v.w;
+    pend = w.x;
+  } else {
+    n = t.order[i];
+    pp = t.parent[3 * n];
+    pe = t.parent[3 * n + 1];
+    pend = t.parent[3 * n + 2];
+  }
+  const int64_t nn2 = 2 * (int64_t)p.nn;
+  double Bk[4] = {0.0, 0.0, 0.0, 0.0}, Pn[4];
+  if (pp >= 0) cp_block(a.se, pe, pend, 1 - pend, Bk);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) Pn[q] = p.Pinv[4 * (int64_t)n + q];
+#pragma unroll
+  for (int k = 0; k < kCpTile; ++k)
+    if (k < nt) {
+      const double* hq = p.hv + cl.col[k] * nn2 + 2 * (int64_t)n;
+      double r0 = hq[0], r1 = hq[1];
+      if (pp >= 0) {
+        const double* xp = p.xn + cl.col[k] * nn2 + 2 * (int64_t)pp;
+        r0 -= Bk[0] * xp[0] + Bk[1] * xp[1];
+        r1 -= Bk[2] * xp[0] + Bk[3] * xp[1];
+      }
+      double* xq = p.xn + cl.col[k] * nn2 + 2 * (int64_t)n;
+      xq[0] = Pn[0] * r0 + Pn[1] * r1;
+      xq[1] = Pn[2] * r0 + Pn[3] * r1;
+    }
+}
+
+// Levels [L0, L1) of the node forest, a thread per node and tile of columns (blockIdx.y: the
+// tile), a barrier per level -- paid per tile, not per column. rng: a run of wide levels in
+// subtree chunks, one per workgroup (k_cp_nodes_rec's ranges), or null: the levels whole, in
+// one workgroup.
+__global__ __launch_bounds__(1024) void k_cp_b_nodes(CpBatch p, CpTree t,
+                                                     const int* __restrict__ rng, int L0, int L1,
+                                                     int up) {
+  const int c0 = (int)blockIdx.y * kCpTile;
+  const int nt = min(kCpTile, p.ncols - c0);
+  const CpCols cl = cp_cols(p.list, c0, nt);
+  const int nlv = L1 - L0;
+  for (int k = 0; k < nlv; ++k) {
+    const int L = up ? nlv - 1 - k : k;
+    int lo, hi;
+    if (rng != nullptr) {
+      lo = rng[2 * ((int64_t)blockIdx.x * nlv + L)];
+      hi = rng[2 * ((int64_t)blockIdx.x * nlv + L) + 1];
+    } else {
+      lo = t.lev_off[L0 + L];
+      hi = t.lev_off[L0 + L + 1];
+    }
+    for (int i = lo + (int)threadIdx.x; i < hi; i += (int)blockDim.x) {
+      if (up) cp_b_node_up(p, t, i, cl, nt);
+      else cp_b_node_down(p, t, i, cl, nt);
+    }
+    __syncthreads();
+  }
+}
+
+// One level [i0, i1) of level-order nodes across the grid (a wide level)
+__global__ __launch_bounds__(256) void k_cp_b_level(CpBatch p, CpTree t, int i0, int i1, int up) {
+  const int i = i0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= i1) return;
+  const int c0 = (int)blockIdx.y * kCpTile;
+  const int nt = min(kCpTile, p.ncols - c0);
+  const CpCols cl = cp_cols(p.list, c0, nt);
+  if (up) cp_b_node_up(p, t, i, cl, nt);
+  else cp_b_node_down(p, t, i, cl, nt);
+}
+
+// Back-substitution of one edge and one tile of columns (one thread): k_cp_back's vertex
+// recursion y = z - (Pi W) x_border - (Pi C) y_next with the two products formed once per
+// vertex and tile, then the cells' interiors; the columns' rows of X stored directly (accum:
+// added -- the refinement pass), the node rows by the node's designated edge (nown).
+__global__ __launch_bounds__(64) void k_cp_b_back(CpBatch p, const int* __restrict__ nown,
+                                                  int accum) {
+#pragma clang fp contract(off)
+  const CpArgs& a = p.a;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.E) return;
+  const int c0 = (int)blockIdx.y * kCpTile;
+  const int nt = min(kCpTile, p.ncols - c0);
+  const CpCols cl = cp_cols(p.list, c0, nt);
+  const int N = a.N, k = a.k, m = a.m, nI = a.nI;
+  const int nf = k * N + 1, per = nf + m * N - 1;
+  const int64_t base = e * (int64_t)per, E = a.E, nn2 = 2 * (int64_t)p.nn;
+  const double* hl = a.cellh + e * N;
+  const int u = a.eb[4 * e], v = a.eb[4 * e + 1];
+  const double* fe = a.fac + e;
+  const double* Eh = a.cst + 16 + 4 * nI;
+  const double* Fh = Eh + 4 * nI;
+  const double R = a.edge_R[e];
+  const int64_t zld = 2 * (int64_t)(N + 1) * E;
+  auto prow = [&](int j) { return nf + j - 1; };  // (local row)
+  const double* bl[kCpTile];
+  double* xl[kCpTile];
+  double xb[kCpTile][4], yn[kCpTile][2], xv[kCpTile][4];
+#pragma unroll
+  for (int t = 0; t < kCpTile; ++t) {
+    bl[t] = p.B + cl.col[t] * p.ld + base;
+    xl[t] = p.X + cl.col[t] * p.ld + base;
+    const double* xn = p.xn + cl.col[t] * nn2;
+    xb[t][0] = xn[2 * u];
+    xb[t][1] = xn[2 * u + 1];
+    xb[t][2] = xn[2 * v];
+    xb[t][3] = xn[2 * v + 1];
+    yn[t][0] = 0.0;
+    yn[t][1] = 0.0;
+  }
+  auto putl = [&](int t, int r, double val) { xl[t][r] = accum ? xl[t][r] + val : val; };
+  for (int i = N; i >= 0; --i) {
+    double f[kCpBFac];
+    const double* fp = fe + (int64_t)i * kCpBFac * E;
+#pragma unroll
+    for (int q = 0; q < kCpBFac; ++q) f[q] = fp[q * E];
+    const double* Pi = f;
+    const double* C = f + 4;
+    const double* W = f + 8;
+    double Xc[4], Y[8];  // Pi C, Pi W
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) Xc[2 * r + q] = Pi[2 * r] * C[q] + Pi[2 * r + 1] * C[2 + q];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) Y[4 * r + q] = Pi[2 * r] * W[q] + Pi[2 * r + 1] * W[4 + q];
+    }
+#pragma unroll
+    for (int t = 0; t < kCpTile; ++t) {
+      const double* zp = p.z + cl.col[t] * zld + (int64_t)(2 * i) * E + e;
+      double y0 = zp[0], y1 = zp[E];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        y0 -= Y[q] * xb[t][q];
+        y1 -= Y[4 + q] * xb[t][q];
+      }
+      y0 -= Xc[0] * yn[t][0] + Xc[1] * yn[t][1];
+      y1 -= Xc[2] * yn[t][0] + Xc[3] * yn[t][1];
+      if (t < nt) {
+        putl(t, k * i, y0);
+        if (i > 0 && i < N) putl(t, prow(m * i), y1);
+      }
+      // cell i's vertex values (q_i, p_i, q_{i+1}, p_{i+1})
+      xv[t][0] = y0;
+      xv[t][1] = i == 0 ? xb[t][0] : y1;
+      xv[t][2] = yn[t][0];
+      xv[t][3] = i + 1 == N ? xb[t][2] : yn[t][1];
+      yn[t][0] = y0;
+      yn[t][1] = y1;
+    }
+    if (i < N) {  // cell i: its interior nodes
+      const double s = R * hl[i];
+      const double si = 1.0 / s;
+      for (int j = 0; j < nI; ++j) {
+        const int tj = a.tI[j];
+        double val[kCpTile];
+#pragma unroll
+        for (int t = 0; t < kCpTile; ++t) val[t] = 0.0;
+        for (int l = 0; l < nI; ++l) {
+          const int tl = a.tI[l];
+          const int row = tl > 0 ? i * k + 1 + l : prow(i * m + 1 + (l - (k - 1)));
+          const int ex = -(tj + tl) / 2;  // cp_pow's exponent
+          const double cf = Fh[j * nI + l] * (ex > 0 ? s : ex < 0 ? si : 1.0);
+#pragma unroll
+          for (int t = 0; t < kCpTile; ++t) val[t] += cf * bl[t][row];
+        }
+        // (vertex types +1, -1, +1, -1: exponents (-tj + 1) / 2 and (-tj - 1) / 2)
+        const double pq = tj > 0 ? 1.0 : s, pp = tj > 0 ? si : 1.0;
+        const double ce[4] = {Eh[j * 4] * pq, Eh[j * 4 + 1] * pp, Eh[j * 4 + 2] * pq,
+                              Eh[j * 4 + 3] * pp};
+        const int row = tj > 0 ? i * k + 1 + j : prow(i * m + 1 + (j - (k - 1)));
+#pragma unroll
+        for (int t = 0; t < kCpTile; ++t) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) val[t] -= ce[q] * xv[t][q];
+          if (t < nt) putl(t, row, val[t]);
+        }
+      }
+    }
+  }
+  // the border rows: node values written once (the node's designated edge, nown)
+  for (int end = 0; end < 2; ++end) {
+    const int n = end ? v : u;
+    if (nown[n] != e) continue;
+    const int pr = a.nrow[2 * n], lr = a.nrow[2 * n + 1];
+#pragma unroll
+    for (int t = 0; t < kCpTile; ++t)
+      if (t < nt) {
+        double* x = p.X + cl.col[t] * p.ld;
+        const double* xn = p.xn + cl.col[t] * nn2;
+        x[pr] = accum ? x[pr] + xn[2 * n] : xn[2 * n];
+        if (lr >= 0) x[lr] = accum ? x[lr] + xn[2 * n + 1] : xn[2 * n + 1];
+      }
+  }
+}
+
+bool cp_batch_ok(const nx_network* h) {
+  return h && h->fe && h->fe_cp && h->solver == 1 && !proc_rank(h) && h->group == nullptr &&
+         h->nranks == 1 && h->n_ghost == 0 && h->cp_Eg == 0 && h->cpc_ns == 0 && h->E > 0;
+}
+
+// The continuous-pressure part of the workspace. Per call: the vertex factors, Se, the node
+// pivots, what the factoring up-sweep writes beside them (its rhs, terms) and the zero
+// right-hand side it reads; per column: z, ge, hv, the child terms, xn.
+struct CpWs {
+  double *fac, *se, *Pinv, *fhv, *fctr, *zero;
+  double *z, *ge, *hv, *ct, *xn;
+  size_t bytes;
+};
+CpWs cp_layout(const nx_network* h, int cap, void* base) {
+  const int64_t E = h->E, nn = h->cp_nn, N1 = h->N + 1;
+  CpWs w{};
+  WsWalk k{static_cast<double*>(base)};
+  w.fac = k.take(E * N1 * kCpBFac);
+  w.se = k.take(20 * E);
+  w.Pinv = k.take(4 * nn);
+  w.fhv = k.take(2 * nn);
+  w.fctr = k.take(6 * nn);
+  w.zero = k.take(h->n_col);
+  w.z = k.take(cap * 2 * N1 * E);
+  w.ge = k.take(cap * 4 * E);
+  w.hv = k.take(cap * 2 * nn);
+  w.ct = k.take(cap * 2 * nn);
+  w.xn = k.take(cap * 2 * nn);
+  w.bytes = 8 * (size_t)k.off + 64;
+  return w;
+}
+size_t cp_bytes(const nx_network* h, int cap) { return cp_layout(h, cap, nullptr).bytes; }
+bool cp_batch_fits(const nx_network* h, int cap) {
+  return batch_fits(h, cap, BatchParts{}) && h->cp_bws != nullptr && cap <= h->cp_bws_cap &&
+         cp_bytes(h, h->cp_bws_cap) <= h->cp_bws_bytes && h->cp_bws_cap == h->bws_cap;
+}
+
+// batch_workspace for the two parts together, as fe_batch_workspace.
+int cp_batch_workspace(nx_network* h, int n_cols, int* chunk_out) {
+  auto release = [&]() {
+    batch_free(h);
+    cp_batch_free(h);
+  };
+  auto alloc = [&](int cap) {
+    if (!batch_alloc(h, cap, BatchParts{})) return false;
+    const size_t bytes = cp_bytes(h, cap);
+    if (hipMalloc(&h->cp_bws, bytes) != hipSuccess) {
+      h->cp_bws = nullptr;
+      batch_free(h);
+      return false;
+    }
+    h->cp_bws_cap = cap;
+    h->cp_bws_bytes = bytes;
+    return true;
+  };
+  return batch_chunk_rule(
+      h, n_cols, false, "nx_cp_batch_solve", [&](int cap) { return cp_batch_fits(h, cap); },
+      [&](int cap) { return batch_bytes(h, cap, BatchParts{}) + cp_bytes(h, cap); }, release,
+      alloc, chunk_out);
+}
+
+CpArgs cp_batch_args(const nx_network* h, const CpWs& wc) {
+  return CpArgs{(int)h->N, h->cp_k, h->cp_m, h->cp_nI, h->E, h->edge_R, h->fe_cellh, h->cp_cst,
+                h->cp_tI, h->cp_eb, h->cp_nrow, wc.fac, wc.se, nullptr, nullptr};
+}
+CpTree cp_batch_tree(const nx_network* h, const CpWs& wc) {
+  return CpTree{h->cp_nn, h->cp_nlev, h->cp_lev_off, h->cp_order, h->cp_inc_off, h->cp_inc,
+                h->cp_parent, h->cp_child_off, h->cp_child, wc.Pinv, wc.fhv, h->cp_rec,
+                h->cp_rec ? wc.fctr : nullptr};
+}
+
+// The factor stage, once per call: k_cp_b_factor, then the node forest's up-sweep of the
+// single solve on those blocks and a zero right-hand side (it leaves every node's pivot
+// inverse in the workspace). Launches: 1 + the forest's up runs.
+int cp_batch_factor(nx_network* h, const CpWs& wc) {
+  const CpArgs a = cp_batch_args(h, wc);
+  HIPCALL(hipMemsetAsync(wc.zero, 0, sizeof(double) * h->n_col, h->stream));
+  hipLaunchKernelGGL(k_cp_b_factor, dim3(grid_of(h->E, 64)), dim3(64), 0, h->stream, a);
+  h->b_launches += 1;
+  h->b_launches += cp_nodes_pass(h, a, cp_batch_tree(h, wc), wc.zero, 1);
+  HIPCALL(hipGetLastError());
+  return NX_OK;
+}
+
+// X (+)= A^{-1} Bv on nc columns (list: which, device; null: the first nc): the forward
+// sweep, the node forest up and down over cp_level_walk's runs, the back-substitution.
+// Launches: 2 + the forest's up and down runs, whatever nc.
+int cp_batch_apply(nx_network* h, const BatchWs& ws, const CpWs& wc, const int* list, int nc,
+                   const double* Bv, double* Xv, int accum) {
+  const CpBatch p{cp_batch_args(h, wc), wc.Pinv, list, nc, h->cp_nn, Bv, Xv, ws.cols.ld,
+                  wc.z, wc.ge, wc.hv, wc.ct, wc.xn};
+  CpTree tr = cp_batch_tree(h, wc);
+  const int tiles = grid_of(nc, kCpTile), eb = grid_of(h->E, 64);
+  const std::vector<int>& lo = h->cp_lev_host;
+  hipLaunchKernelGGL(k_cp_b_fwd, dim3(eb, tiles), dim3(64), 0, h->stream, p);
+  h->b_launches += 1;
+  for (int up = 1; up >= 0; --up)
+    h->b_launches += cp_level_walk(
+        h, tr.rec != nullptr, up,
+        [&](const nx_network::CpRun& run) {
+          hipLaunchKernelGGL(k_cp_b_nodes, dim3(run.nch, tiles), dim3(kCpChunk), 0, h->stream, p,
+                             tr, h->cp_rng + run.off, run.L0, run.L1, up);
+        },
+        [&](int L) {
+          hipLaunchKernelGGL(k_cp_b_level, dim3(grid_of(lo[L + 1] - lo[L], 256), tiles), dim3(256),
+                             0, h->stream, p, tr, lo[L], lo[L + 1], up);
+        },
+        [&](int La, int Lb, bool) {
+          hipLaunchKernelGGL(k_cp_b_nodes, dim3(1, tiles), dim3(1024), 0, h->stream, p, tr,
+                             (const int*)nullptr, La, Lb, up);
+        });
+  hipLaunchKernelGGL(k_cp_b_back, dim3(eb, tiles), dim3(64), 0, h->stream, p, h->cp_nown, accum);
+  h->b_launches += 1;
+  HIPCALL(hipGetLastError());
+  return NX_OK;
+}
+
+int cp_batch_state(nx_network* h, const char* who) {
+  if (!cp_batch_ok(h))
+    return fail(NX_ERR_STATE, std::string(who) + ": the batched node-condensed solve does not "
+                                                 "apply to this handle (nx_cp_batch_supported)");
+  return NX_OK;
+}
+
+}  // namespace
+
+NX_API int nx_cp_batch_supported(nx_network_t* h, int32_t* ok) {
+  if (!h || !ok) return fail(NX_ERR_ARG, "null argument");
+  *ok = cp_batch_ok(h) ? 1 : 0;
+  return NX_OK;
+}
+
+NX_API int nx_cp_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                           const double* edge_f, const double* f_const, double* out) {
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  CHECK(batch_check_args(h, n_cols, edge_bc, out));
+  CHECK(cp_batch_state(h, "nx_cp_batch_rhs"));
+  CHECK(set_device(h));
+  int chunk = 0;
+  CHECK(cp_batch_workspace(h, n_cols, &chunk));
+  const BatchWs ws = batch_carve(h);
+  return batch_chunks(
+      h, ws, n_cols, chunk, 0, out,
+      [&](int c0, int nc) { return fe_batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const); },
+      nullptr);
+}
+
+NX_API int nx_cp_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                             const double* edge_f, const double* f_const, double rtol,
+                             int32_t maxit, int32_t order, double* out, int32_t* iters,
+                             double* relres, int32_t* converged) {
+  // (a flushed assembly is counted in the call's launches, as in nx_batch_solve)
+  const int made_current = batch_pending(h);
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  CHECK(batch_check_args(h, n_cols, edge_bc, out));
+  if (maxit < 1) return fail(NX_ERR_ARG, "maxit must be >= 1");
+  CHECK(cp_batch_state(h, "nx_cp_batch_solve"));
+  if (!h->have_lhs || h->asm_coef_version != h->coef_version)
+    return fail(NX_ERR_STATE, "nx_cp_batch_solve: assemble the matrix for the resident "
+                              "coefficients first");
+  if (order != 0 && !h->out_idx) return fail(NX_ERR_STATE, "nx_set_output_map first");
+  CHECK(set_device(h));
+  h->b_refined = h->b_fallback = 0;
+  h->b_launches = made_current;
+  int chunk = 0;
+  CHECK(cp_batch_workspace(h, n_cols, &chunk));
+  h->b_chunk = chunk;
+  const BatchWs ws = batch_carve(h);
+  const CpWs wc = cp_layout(h, h->cp_bws_cap, h->cp_bws);
+  CHECK(cp_batch_factor(h, wc));
+  // the policy's operator: the right-hand-side sweeps on the call's factors (the refinement
+  // accumulates into ws.X); the single-column route is fe_cp_solve on the handle's own arrays,
+  // then MINRES capped at maxit, and where that ends unconverged and no better, the refined
+  // column stands
+  const BatchStatus st{iters, relres, converged};
+  return batch_chunks(
+      h, ws, n_cols, chunk, order, out,
+      [&](int c0, int nc) { return fe_batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const); },
+      [&](int c0, int nc, std::vector<double>& stats) {
+        return batch_solve_cols(
+            h, ws, nc, ws.B, ws.X, rtol, st.at(c0), stats,
+            [&](int ncs) { return cp_batch_apply(h, ws, wc, nullptr, ncs, ws.B, ws.X, 0); },
+            [&](const int* list, int nr) {
+              return cp_batch_apply(h, ws, wc, list, nr, ws.R, ws.X, 1);
             },
             BatchFallback{BatchFallback::kKeep, maxit});
       });
@@ -16667,6 +17461,7 @@ NX_API int nx_fe_set_cp(nx_network_t* h, int32_t k, int32_t m, int32_t nI, const
   }
   h->cp_runs.clear();
   h->fe_cp = false;
+  cp_batch_free(h);  // (nx_cp_batch_solve's workspace is laid out for the tables that leave)
   CHECK(cpc_clear(h));  // (the chords belong to the tables that leave)
   if (k == 0) {
     h->cp_Eown = h->cp_Eg = 0;

@@ -892,3 +892,266 @@ def cp_model(lay: FeLayout, tab: CpTables, val: np.ndarray, b: np.ndarray, R: np
             yn = y
     del A
     return x
+
+
+def cp_factor_model(lay: FeLayout, tab: CpTables, R: np.ndarray, cell_h: np.ndarray) -> dict:
+    """numpy restatement of ``nx_cp_batch_solve``'s factor stage (k_cp_b_factor, then the node
+    forest's up-sweep on a zero right-hand side), in the kernels' order of operations: what
+    the node-condensed solve derives from the matrix alone. No right-hand side enters.
+    Returns ``fac`` (E, N + 1, 16): per vertex Pi | C | W, ``Se`` (E, 16) and ``Pinv``
+    (n_nodes, 4), for :func:`cp_apply_model`."""
+    N, E = lay.N, lay.E
+    Kh = np.asarray(tab.cst[:16], dtype=np.float64)
+    tV = (1, -1, 1, -1)
+    eb = tab.eb.reshape(-1, 4)
+    nrow = tab.nrow.reshape(-1, 2)
+    h = np.asarray(cell_h, dtype=np.float64).reshape(E, N)
+
+    def pw(s, ex):
+        return s if ex > 0 else (1.0 / s if ex < 0 else 1.0)
+
+    def inv2(P):
+        idet = 1.0 / (P[0] * P[3] - P[1] * P[2])
+        return [P[3] * idet, -P[1] * idet, -P[2] * idet, P[0] * idet]
+
+    fac = np.zeros((E, N + 1, 16))
+    Se = np.zeros((E, 16))
+    for e in range(E):
+        P = [0.0, 0.0, 0.0, 1.0]
+        W = [0.0] * 8
+        W[1] = float(eb[e, 2])
+        Sb = [0.0] * 16
+        for c in range(N):
+            s = float(R[e]) * float(h[e, c])
+            K = [float(Kh[4 * r + q]) * pw(s, (tV[r] + tV[q]) // 2)
+                 for r in range(4) for q in range(4)]
+            Wn = [0.0] * 8
+            if c == 0:
+                P[0] += K[0]
+                W[0] += K[1]
+                Sb[0] += K[5]
+                C = [K[2], K[3], 0.0, 0.0]
+                Wn[0], Wn[4] = K[9], K[13]
+            else:
+                P[0] += K[0]
+                P[1] += K[1]
+                P[2] += K[4]
+                P[3] += K[5]
+                C = [K[2], K[3], K[6], K[7]]
+            if c + 1 < N:
+                Pn = [K[10], K[11], K[14], K[15]]
+            else:
+                Sb[10] += K[15]
+                if c == 0:
+                    Sb[2] += K[7]
+                    Sb[8] += K[13]
+                Wn[2] += K[11]
+                Wn[3] = float(eb[e, 3])
+                Wn[4] = 0.0
+                W[2] += C[1]
+                W[6] += C[3]
+                C[1] = C[3] = 0.0
+                Pn = [K[10], 0.0, 0.0, 1.0]
+            Pi = inv2(P)
+            X = [Pi[2 * r] * C[q] + Pi[2 * r + 1] * C[2 + q] for r in range(2) for q in range(2)]
+            Y = [Pi[2 * r] * W[q] + Pi[2 * r + 1] * W[4 + q] for r in range(2) for q in range(4)]
+            for r in range(2):
+                for q in range(2):
+                    Pn[2 * r + q] -= C[r] * X[q] + C[2 + r] * X[2 + q]
+                for q in range(4):
+                    Wn[4 * r + q] -= C[r] * Y[q] + C[2 + r] * Y[4 + q]
+            for r in range(4):
+                for q in range(4):
+                    Sb[4 * r + q] -= W[r] * Y[q] + W[4 + r] * Y[4 + q]
+            fac[e, c] = Pi + C + W
+            P, W = Pn, Wn
+        Pi = inv2(P)
+        Y = [Pi[2 * r] * W[q] + Pi[2 * r + 1] * W[4 + q] for r in range(2) for q in range(4)]
+        for r in range(4):
+            for q in range(4):
+                Sb[4 * r + q] -= W[r] * Y[q] + W[4 + r] * Y[4 + q]
+        fac[e, N] = Pi + [0.0] * 4 + W
+        Se[e] = Sb
+    n = tab.n_nodes
+    inc = tab.inc.reshape(-1, 2)
+    par = tab.parent.reshape(-1, 3)
+    Pinv = np.zeros((n, 4))
+    lev = tab.lev_off
+    for L in range(lev.size - 2, -1, -1):
+        for i in range(lev[L], lev[L + 1]):
+            nd = tab.order[i]
+            D = [0.0] * 4
+            for j in range(tab.inc_off[nd], tab.inc_off[nd + 1]):
+                e, end = inc[j]
+                Bk = _cp_blk(Se, e, end, end)
+                for q in range(4):
+                    D[q] += Bk[q]
+            if nrow[nd, 1] < 0:
+                D[3] = 1.0
+            for j in range(tab.child_off[nd], tab.child_off[nd + 1]):
+                c = tab.child[j]
+                Bk = _cp_blk(Se, par[c, 1], par[c, 2], 1 - par[c, 2])
+                Pc = Pinv[c]
+                X = [Pc[2 * r] * Bk[q] + Pc[2 * r + 1] * Bk[2 + q]
+                     for r in range(2) for q in range(2)]
+                for r in range(2):
+                    for q in range(2):
+                        D[2 * r + q] -= Bk[r] * X[q] + Bk[2 + r] * X[2 + q]
+            Pinv[nd] = inv2(D)
+    return {"fac": fac, "Se": Se, "Pinv": Pinv}
+
+
+def _cp_blk(Se, e, ra, cb):
+    """cp_block: rows of end ``ra``, columns of end ``cb`` of edge ``e``'s border block."""
+    S = Se[e]
+    return [float(S[4 * (2 * ra) + 2 * cb]), float(S[4 * (2 * ra) + 2 * cb + 1]),
+            float(S[4 * (2 * ra + 1) + 2 * cb]), float(S[4 * (2 * ra + 1) + 2 * cb + 1])]
+
+
+def cp_apply_model(lay: FeLayout, tab: CpTables, fm: dict, Bm: np.ndarray, R: np.ndarray,
+                   cell_h: np.ndarray) -> np.ndarray:
+    """numpy restatement of ``nx_cp_batch_solve``'s right-hand-side sweeps (k_cp_b_fwd,
+    k_cp_b_nodes, k_cp_b_back) on the factors ``fm`` of :func:`cp_factor_model`: ``Bm``
+    ``(n_cols, n_rows)`` right-hand sides, returns the ``(n_cols, n_rows)`` solutions. Every
+    operation is elementwise over the columns, in the kernels' order, so a column's bits do
+    not depend on the columns beside it."""
+    Bm = np.ascontiguousarray(Bm, dtype=np.float64)
+    nc = Bm.shape[0]
+    N, k, m, nI, E = lay.N, lay.k, lay.m, tab.nI, lay.E
+    nf = k * N + 1
+    per = nf + m * N - 1
+    Ch = np.asarray(tab.cst[16:16 + 4 * nI], dtype=np.float64).reshape(4, nI)
+    Eh = np.asarray(tab.cst[16 + 4 * nI:16 + 8 * nI], dtype=np.float64).reshape(nI, 4)
+    Fh = np.asarray(tab.cst[16 + 8 * nI:], dtype=np.float64).reshape(nI, nI)
+    tI = [int(t) for t in tab.tI]
+    eb = tab.eb.reshape(-1, 4)
+    nrow = tab.nrow.reshape(-1, 2)
+    h = np.asarray(cell_h, dtype=np.float64).reshape(E, N)
+    fac, Se, Pinv = fm["fac"], fm["Se"], fm["Pinv"]
+    zero = np.zeros(nc)
+
+    def lrow(c, i):  # cell c's interior node i (local row)
+        return c * k + 1 + i if tI[i] > 0 else nf + (c * m + 1 + (i - (k - 1))) - 1
+
+    z = np.zeros((E, N + 1, 2, nc))
+    ge = np.zeros((E, 4, nc))
+    for e in range(E):
+        bl = Bm[:, e * per:(e + 1) * per]
+        rho = [bl[:, 0].copy(), zero.copy()]
+        gb = [zero.copy() for _ in range(4)]
+        for c in range(N + 1):
+            f = [float(v) for v in fac[e, c]]
+            Pi, C, W = f[:4], f[4:8], f[8:]
+            if c < N:
+                s = float(R[e]) * float(h[e, c])
+                si = 1.0 / s
+                rV = [zero.copy() for _ in range(4)]
+                for i in range(nI):
+                    pq, pp = (1.0, si) if tI[i] > 0 else (s, 1.0)
+                    cf = [float(Ch[0, i]) * pq, float(Ch[1, i]) * pp, float(Ch[2, i]) * pq,
+                          float(Ch[3, i]) * pp]
+                    bi = bl[:, lrow(c, i)]
+                    for r in range(4):
+                        rV[r] = rV[r] - cf[r] * bi
+                rho[0] = rho[0] + rV[0]
+                if c == 0:
+                    gb[0] = gb[0] + rV[1]
+                else:
+                    rho[1] = rho[1] + rV[1]
+                if c + 1 < N:
+                    rn = [rV[2] + bl[:, k * (c + 1)], rV[3] + bl[:, nf + m * (c + 1) - 1]]
+                else:
+                    gb[2] = gb[2] + rV[3]
+                    rn = [rV[2] + bl[:, nf - 1], zero.copy()]
+            z0 = Pi[0] * rho[0] + Pi[1] * rho[1]
+            z1 = Pi[2] * rho[0] + Pi[3] * rho[1]
+            if c < N:
+                for r in range(2):
+                    rn[r] = rn[r] - (C[r] * z0 + C[2 + r] * z1)
+            for r in range(4):
+                gb[r] = gb[r] - (W[r] * z0 + W[4 + r] * z1)
+            z[e, c, 0], z[e, c, 1] = z0, z1
+            if c < N:
+                rho = rn
+        for r in range(4):
+            ge[e, r] = gb[r]
+    n = tab.n_nodes
+    inc = tab.inc.reshape(-1, 2)
+    par = tab.parent.reshape(-1, 3)
+    hv, ct, xn = np.zeros((n, 2, nc)), np.zeros((n, 2, nc)), np.zeros((n, 2, nc))
+    lev = tab.lev_off
+    for L in range(lev.size - 2, -1, -1):
+        for i in range(lev[L], lev[L + 1]):
+            nd = tab.order[i]
+            g0 = Bm[:, nrow[nd, 0]].copy()
+            g1 = Bm[:, nrow[nd, 1]].copy() if nrow[nd, 1] >= 0 else zero.copy()
+            for j in range(tab.inc_off[nd], tab.inc_off[nd + 1]):
+                e, end = inc[j]
+                g0 = g0 + ge[e, 2 * end]
+                g1 = g1 + ge[e, 2 * end + 1]
+            for j in range(tab.child_off[nd], tab.child_off[nd + 1]):
+                c = tab.child[j]
+                g0 = g0 - ct[c, 0]
+                g1 = g1 - ct[c, 1]
+            hv[nd, 0], hv[nd, 1] = g0, g1
+            if par[nd, 0] >= 0:
+                Bk = _cp_blk(Se, par[nd, 1], par[nd, 2], 1 - par[nd, 2])
+                Pc = [float(v) for v in Pinv[nd]]
+                z0 = Pc[0] * g0 + Pc[1] * g1
+                z1 = Pc[2] * g0 + Pc[3] * g1
+                ct[nd, 0] = Bk[0] * z0 + Bk[2] * z1
+                ct[nd, 1] = Bk[1] * z0 + Bk[3] * z1
+    for L in range(lev.size - 1):
+        for i in range(lev[L], lev[L + 1]):
+            nd = tab.order[i]
+            r0, r1 = hv[nd, 0].copy(), hv[nd, 1].copy()
+            if par[nd, 0] >= 0:
+                Bk = _cp_blk(Se, par[nd, 1], par[nd, 2], 1 - par[nd, 2])
+                xp = xn[par[nd, 0]]
+                r0 = r0 - (Bk[0] * xp[0] + Bk[1] * xp[1])
+                r1 = r1 - (Bk[2] * xp[0] + Bk[3] * xp[1])
+            Pn = [float(v) for v in Pinv[nd]]
+            xn[nd, 0] = Pn[0] * r0 + Pn[1] * r1
+            xn[nd, 1] = Pn[2] * r0 + Pn[3] * r1
+    X = np.zeros_like(Bm)
+    for nd in range(n):
+        X[:, nrow[nd, 0]] = xn[nd, 0]
+        if nrow[nd, 1] >= 0:
+            X[:, nrow[nd, 1]] = xn[nd, 1]
+    for e in range(E):
+        base = e * per
+        bl = Bm[:, base:base + per]
+        xb = [xn[eb[e, 0], 0], xn[eb[e, 0], 1], xn[eb[e, 1], 0], xn[eb[e, 1], 1]]
+        yn = [zero.copy(), zero.copy()]
+        for i in range(N, -1, -1):
+            f = [float(v) for v in fac[e, i]]
+            Pi, C, W = f[:4], f[4:8], f[8:]
+            Xc = [Pi[2 * r] * C[q] + Pi[2 * r + 1] * C[2 + q] for r in range(2) for q in range(2)]
+            Y = [Pi[2 * r] * W[q] + Pi[2 * r + 1] * W[4 + q] for r in range(2) for q in range(4)]
+            y0, y1 = z[e, i, 0].copy(), z[e, i, 1].copy()
+            for q in range(4):
+                y0 = y0 - Y[q] * xb[q]
+                y1 = y1 - Y[4 + q] * xb[q]
+            y0 = y0 - (Xc[0] * yn[0] + Xc[1] * yn[1])
+            y1 = y1 - (Xc[2] * yn[0] + Xc[3] * yn[1])
+            X[:, base + k * i] = y0
+            if 0 < i < N:
+                X[:, base + nf + m * i - 1] = y1
+            if i < N:
+                s = float(R[e]) * float(h[e, i])
+                si = 1.0 / s
+                xv = [y0, xb[0] if i == 0 else y1, yn[0], xb[2] if i + 1 == N else yn[1]]
+                for j in range(nI):
+                    val = zero.copy()
+                    for l in range(nI):  # noqa: E741
+                        ex = -(tI[j] + tI[l]) // 2
+                        cf = float(Fh[j, l]) * (s if ex > 0 else si if ex < 0 else 1.0)
+                        val = val + cf * bl[:, lrow(i, l)]
+                    pq, pp = (1.0, si) if tI[j] > 0 else (s, 1.0)
+                    ce = [float(Eh[j, 0]) * pq, float(Eh[j, 1]) * pp, float(Eh[j, 2]) * pq,
+                          float(Eh[j, 3]) * pp]
+                    for q in range(4):
+                        val = val - ce[q] * xv[q]
+                    X[:, base + lrow(i, j)] = val
+            yn = [y0, y1]
+    return X

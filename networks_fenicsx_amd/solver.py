@@ -214,6 +214,15 @@ class Solver:
             ``None`` reads ``NXHIP_FE_BATCH`` (``"1"`` on; off when unset). Off, these degrees
             take the per-scenario loop, whose columns are bit-equal to single solves; the
             batched columns agree with them to rounding.
+        batch_continuous: let :meth:`solve_many` (and ``terminal_conductance``) take the
+            batched path for continuous pressure (k > m >= 1) on a forest
+            (``nx_cp_batch_solve``: the node-condensed direct solve factored once per call,
+            its right-hand-side sweeps with a column dimension). ``None`` reads
+            ``NXHIP_CP_BATCH`` (``"1"`` on; off when unset). Off -- and on a graph with cycles
+            (``cycle_direct``), with several ranks or with ``ksp_type="minres"`` -- these
+            degrees take the per-scenario loop, whose columns are bit-equal to single solves;
+            the batched columns agree with them to rounding (with the
+            measurements).
     """
 
     def __init__(
@@ -225,11 +234,15 @@ class Solver:
         *,
         ensemble_cycles: bool | None = None,
         batch_degrees: bool | None = None,
+        batch_continuous: bool | None = None,
     ):
         self._assembler = assembler
         if batch_degrees is None:
             batch_degrees = os.environ.get("NXHIP_FE_BATCH", "") == "1"
         self._fe_batch = bool(batch_degrees)
+        if batch_continuous is None:
+            batch_continuous = os.environ.get("NXHIP_CP_BATCH", "") == "1"
+        self._cp_batch = bool(batch_continuous)
         if ensemble_cycles is None:
             ensemble_cycles = os.environ.get("NXHIP_ENS_CYCLES", "") == "1"
         self._ens_cycles = bool(ensemble_cycles)
@@ -329,7 +342,10 @@ class Solver:
         solve) the scenarios go through ``nx_batch_solve`` in one batched pass
         (``path == "batched"``); with ``batch_degrees`` so do flux degrees k >= 2 with DG0
         pressure where ``nx_fe_batch_supported`` holds (``nx_fe_batch_solve``: the condensed
-        direct solve with a column dimension). Otherwise -- general degrees, ``ksp_type="minres"``,
+        direct solve with a column dimension), and with ``batch_continuous`` continuous
+        pressure on a forest where ``nx_cp_batch_supported`` holds (``nx_cp_batch_solve``: the
+        node-condensed solve factored once per call). Otherwise -- general degrees,
+        ``ksp_type="minres"``,
         ``pc_type="none"``, the lumped mass, the global-memory sweeps, or ``NXHIP_BATCH=0`` --
         the per-scenario loop runs (``"sequential"``): the rhs coefficients alone are set (R
         is never uploaded again), then rhs assembly, solve, gather; afterwards the coefficients
@@ -360,12 +376,21 @@ class Solver:
         fe_batched = (not batched and self._fe_batch and want != "0" and worth and self._direct
                       and len(asm.degrees) == 2 and asm.degrees[0] >= 2 and asm.degrees[1] == 0
                       and h.fe_batch_supported())
+        # (k, m), m >= 1, with batch_continuous: the node-condensed solve's batched pass
+        cp_batched = (not batched and not fe_batched and self._cp_batch and want != "0" and worth
+                      and self._direct and len(asm.degrees) == 2 and asm.degrees[1] >= 1
+                      and h.cp_batch_supported())
         if batched:
             x, it, rr, conv = h.batch_solve(edge_bc, edge_f, f_const, self._rtol, blocks=True)
             info = h.batch_info()
         elif fe_batched:
             batched = True
             x, it, rr, conv = h.fe_batch_solve(edge_bc, edge_f, f_const, self._rtol,
+                                               self._maxit, blocks=True)
+            info = h.batch_info()
+        elif cp_batched:
+            batched = True
+            x, it, rr, conv = h.cp_batch_solve(edge_bc, edge_f, f_const, self._rtol,
                                                self._maxit, blocks=True)
             info = h.batch_info()
         else:
