@@ -905,6 +905,16 @@ int nx_get_direct_dense(nx_network_t* h, int32_t* ran, int32_t* builds);
  * Either pointer may be NULL. Replaces the caller-side choice between the reference's
  * assemble_lhs and assemble_rhs (assembly.py:333-358, solver.py:101). */
 int nx_get_values_kept(nx_network_t* h, int32_t* last_step_kept, int64_t* value_writes);
+/* The chains' R-only factors kept across values-free steps:
+ * every cell's length h and mass R h / 6 and every chain's T, 1 / T, mo and 1 / mo depend on
+ * the geometry, N, the decomposition and R alone, so the values-free dense step reads them
+ * from a per-handle table (k_dir_step_kg) instead of forming them in every launch. The table
+ * is built by the step's own device functions (the same bits), lazily before the first such
+ * step, and again only after R's contents or the decomposition changed; new boundary values
+ * or a new source leave it alone (NXHIP_KEEP_GEO=0, read per solve, keeps the recomputing
+ * step k_dir_step_kv). *ran = 1 when the last step read the table; *builds = how many times
+ * this handle built it. Either pointer may be NULL. Replaces nothing in the reference. */
+int nx_get_geo_kept(nx_network_t* h, int32_t* ran, int32_t* builds);
 /* (path 2: the (k, 0) condensed route of nx_fe_set_direct; path 4: the continuous-pressure
  * node-condensed route of nx_fe_set_cp; path 3: several ranks, the
  * exchange step k_dir_xr / k_dir_xg, one launch per rank.)

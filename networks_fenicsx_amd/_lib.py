@@ -100,6 +100,7 @@ _SIGS = {
     "nx_get_direct_sup": (C.c_int, [_h, _pi32]),
     "nx_get_direct_dense": (C.c_int, [_h, _pi32, _pi32]),
     "nx_get_values_kept": (C.c_int, [_h, _pi32, _pi64]),
+    "nx_get_geo_kept": (C.c_int, [_h, _pi32, _pi32]),
     "nx_debug_set_wait_polls": (C.c_int, [_h, C.c_uint32]),
     "nx_debug_xr_rehearse": (C.c_int, [_h, _f64, _i32, _pd]),
     "nx_test_seg_shuffle": (C.c_int, [_pd, _pi32, _i32, _pd, _pd, _pi32, _pi32, _pi32]),
@@ -810,6 +811,14 @@ class Handle:
         k, w = C.c_int32(0), C.c_int64(0)
         check(lib().nx_get_values_kept(self.ptr, C.byref(k), C.byref(w)))
         return {"kept": bool(k.value), "writes": int(w.value)}
+
+    def geo_kept(self) -> dict:
+        """The chains' R-only factors kept across values-free steps (nx_get_geo_kept; DESIGN.md
+        section 3c, round 10): ``ran`` -- the last step read the kept table (k_dir_step_kg);
+        ``builds`` -- how many times this handle built it."""
+        r, b = C.c_int32(0), C.c_int32(0)
+        check(lib().nx_get_geo_kept(self.ptr, C.byref(r), C.byref(b)))
+        return {"ran": bool(r.value), "builds": int(b.value)}
 
     def direct_path(self) -> str:
         """What the last direct solve ran (nx_get_direct_path): ``"fused"`` (k_dir_step, one

@@ -1449,6 +1449,12 @@ struct ChainLane {
   // resistance distances and the chain total from rho / rhoN (k_dir_step sets those from
   // the masses it just assembled: the same bits as setup's loads of dq)
   __device__ __forceinline__ void finish() {
+    const double acc = dists();
+    T = seg_sum<W>(acc + rhoN);
+  }
+  // the resistance distances alone; returns the lane's own sum of rho (k_dir_step_kg takes T
+  // from the handle's kept chain factors instead of summing it again)
+  __device__ __forceinline__ double dists() {
     double acc = 0.0;
 #pragma unroll
     for (int t = 0; t < CPL; ++t) {
@@ -1458,7 +1464,7 @@ struct ChainLane {
     const double excl = seg_incl_scan<W>(acc) - acc;
 #pragma unroll
     for (int t = 0; t < CPL; ++t) D[t] += excl;
-    T = seg_sum<W>(acc + rhoN);
+    return acc;
   }
 };
 
@@ -1474,10 +1480,11 @@ struct ChainLane {
 // by N: forward y_k = r_k - l_k y_{k-1}, backward x_k = (y_k - x_{k+1}) / u_k; pa.Tlu =
 // [l_0..l_N | 1/u_0..1/u_N], l_0 = 0); T is persymmetric, so the chain direction (flip)
 // does not matter. out[t] = the solution at element t (0 where the lane has none).
-template <int W, int CPL>
+// KG (k_dir_step_kg): 1 / ch.mo is the handle's kept one (imo_kept), not divided again.
+template <int W, int CPL, bool KG = false>
 __device__ __forceinline__ void chain_mass_solve(const PcArgs& pa, const ChainLane<W, CPL>& ch,
                                                  const double* rq, double rqN,
-                                                 double (&out)[CPL + 1]) {
+                                                 double (&out)[CPL + 1], double imo_kept = 0.0) {
   constexpr int NE = CPL + 1;
   const int N = pa.N;
   const int l = lane_of<W>();
@@ -1538,7 +1545,7 @@ __device__ __forceinline__ void chain_mass_solve(const PcArgs& pa, const ChainLa
   });
   double x = seg_down_nc<W, 1>(B);  // x at the start of the next lane (0 after q_N: _nc)
   if (l == W - 1) x = 0.0;
-  const double imo = 1.0 / ch.mo;
+  const double imo = KG ? imo_kept : 1.0 / ch.mo;
 #pragma unroll
   for (int t = NE - 1; t >= 0; --t) {
     out[t] = 0.0;
@@ -1818,13 +1825,14 @@ constexpr int kModeDirect = 3;
 // chain lies between chain fluxes k and k + 1, whose orientation flips the sign). ytop / ybot
 // (valid in every lane): the multiplier rows' K^T y at the chain's top / bottom end -- the
 // layout puts -1 at q_0 (source multiplier) and +1 at q_N (target multiplier).
-template <int W, int CPL>
+template <int W, int CPL, bool KG = false>
 __device__ __forceinline__ void direct_cell_inputs(const PcArgs& pa, const ChainLane<W, CPL>& ch,
                                                    int flip, const double* bq, double bqN,
-                                                   double* vc, double& ytop, double& ybot) {
+                                                   double* vc, double& ytop, double& ybot,
+                                                   double imo_kept = 0.0) {
 #pragma clang fp contract(off)
   double yv[CPL + 1];
-  chain_mass_solve<W, CPL>(pa, ch, bq, bqN, yv);
+  chain_mass_solve<W, CPL, KG>(pa, ch, bq, bqN, yv, imo_kept);
   const int N = pa.N;
   const int l = lane_of<W>();
   // (_nc: the segment's last lane holds chain cell W CPL - 1 >= N - 1 in its last element,
@@ -4543,6 +4551,12 @@ struct DirStep {
   // the dense top (k_dir_step's SUP instantiation): where the workgroup's index lists start in
   // the dynamic LDS (doubles from its base; kDn*), and the number of posted inputs (pa.u)
   int dense_off, n_u;
+  // k_dir_step_kg: the chains' R-only factors kept across values-free steps (k_chain_geo;
+  // nx_network::geo_version) -- per cell {h, R h / 6} in chain order, lane-major (lane l of
+  // chain c: 2 CPL doubles at (c W + l) 2 CPL, zeros past cell N - 1), and per chain
+  // {T, 1 / T, mo, 1 / mo} (ChainLane's T and mo)
+  const double* geo_cell;
+  const double* geo_chain;
 };
 
 // The dense fused step's index lists in LDS (ints): the chains' input positions (chain_uit /
@@ -4582,9 +4596,19 @@ struct DirLane {
 // mass of chain flux k (between chain cells k - 1 and k) in k_assemble's order of additions
 // (so ch.rho has dq's bits) -- edge flux q: d = md_q + mo_q, then (mo_{q-1} + md_{q-1}) + d;
 // q = N: mo_{N-1} + md_{N-1}.
-template <int W, int CPL>
+// The chain's R-only factors as the handle keeps them across values-free steps (k_chain_geo
+// stores what dir_lane_chain formed: ch.T, 1 / ch.T, ch.mo, 1 / ch.mo)
+struct ChainGeo {
+  double T, iT, mo, imo;
+};
+
+// KG (k_dir_step_kg): ch.T and ch.mo are the kept ones (g) -- no sum over the segment, no
+// moves of the end masses, no division; an inactive lane group holds chain 0's, which
+// nothing reads (every consumer is under valid / has_last / active)
+template <int W, int CPL, bool KG = false>
 __device__ __forceinline__ void dir_lane_chain(const PcArgs& pa, const DirLane<W, CPL>& L,
-                                               bool active, ChainLane<W, CPL>& ch) {
+                                               bool active, ChainLane<W, CPL>& ch,
+                                               const ChainGeo* g = nullptr) {
 #pragma clang fp contract(off)
   const int N = pa.N;
   const int l = lane_of<W>();
@@ -4636,6 +4660,12 @@ __device__ __forceinline__ void dir_lane_chain(const PcArgs& pa, const DirLane<W
     if (ch.has_last) ch.rhoN = flip ? mdl + mol : mol + mdl;
   }
   // ChainLane::setup's mo: the edge's q_0 lumped mass / 3 (chain flux 0, or N when flipped)
+  if constexpr (KG) {
+    ch.mo = g->mo;
+    ch.dists();
+    ch.T = g->T;
+    return;
+  }
   // (both moves before the choice: every lane of the segment takes part in each)
   const double dqN = __shfl(ch.rhoN, (N - 1) / CPL, W), dqF = seg_bcast0<W>(ch.rho[0]);
   const double dq0 = flip ? dqN : dqF;
@@ -5189,16 +5219,18 @@ __device__ __forceinline__ int fresh_chain(int c0) {
   return c;
 }
 
+// KG (k_dir_step_kg): without the end points and R -- the kept factors stand for them
+template <bool KG = false>
 __device__ __forceinline__ void chain_rec_load(const DirStep& da, int c, bool active,
                                                ChainRec& r) {
   const int cc = active ? c : 0;
   const double* p = da.crec + 10 * (int64_t)cc;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    r.x0[i] = p[i];
-    r.x1[i] = p[3 + i];
+    r.x0[i] = KG ? 0.0 : p[i];
+    r.x1[i] = KG ? 0.0 : p[3 + i];
   }
-  r.R = p[6];
+  r.R = KG ? 0.0 : p[6];
   r.fe = p[7];
   r.bc0 = p[8];
   r.bc1 = p[9];
@@ -5281,10 +5313,27 @@ __device__ __forceinline__ void lane_from_lds(const PcArgs& pa, const double* re
   L.bN = (active && l == (N - 1) / CPL) ? (flip ? r.bc0 : r.bc1) : 0.0;
 }
 
-// dir_chain_asm from a chain record (the same arithmetic, the same bits)
-template <int W, int CPL>
+// The R-only part of dir_chain_asm_rec, one cell: edge cell kp's length h and mass R h / 6.
+// k_chain_geo keeps them across values-free steps (nx_network::d_geo_cell).
+__device__ __forceinline__ void dir_cell_geo(const ChainRec& r, int kp, int N, double invN,
+                                             double& h, double& mo) {
+#pragma clang fp contract(off)
+  double va[3], vb[3];
+  vertex(r.x0, r.x1, kp, N, invN, va);
+  vertex(r.x0, r.x1, kp + 1, N, invN, vb);
+  const double d0 = vb[0] - va[0], d1 = vb[1] - va[1], d2 = vb[2] - va[2];
+  h = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+  mo = r.R * h / 6.0;  // (R h / 3 = 2 mo, bit for bit)
+}
+
+// dir_chain_asm from a chain record (the same arithmetic, the same bits): per cell the
+// R-only part (dir_cell_geo), then the rest.
+// KG (k_dir_step_kg): the R-only part from the handle's kept table instead (kh, kmo: the
+// lane's cells' h and R h / 6, lane_geo_load); the rest as it is.
+template <int W, int CPL, bool KG = false>
 __device__ __forceinline__ void dir_chain_asm_rec(const PcArgs& pa, const ChainRec& r, bool active,
-                                                  DirLane<W, CPL>& L) {
+                                                  DirLane<W, CPL>& L, const double* kh = nullptr,
+                                                  const double* kmo = nullptr) {
 #pragma clang fp contract(off)
   const int N = pa.N;
   const int l = threadIdx.x & (W - 1);
@@ -5305,17 +5354,46 @@ __device__ __forceinline__ void dir_chain_asm_rec(const PcArgs& pa, const ChainR
     L.bc[t] = 0.0;
     L.bq[t] = 0.0;
     if (valid) {
-      double va[3], vb[3];
-      vertex(r.x0, r.x1, kp, N, invN, va);
-      vertex(r.x0, r.x1, kp + 1, N, invN, vb);
-      const double d0 = vb[0] - va[0], d1 = vb[1] - va[1], d2 = vb[2] - va[2];
-      const double h = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-      L.mo[t] = r.R * h / 6.0;  // (R h / 3 = 2 L.mo[t], bit for bit)
+      double h;
+      if constexpr (KG) {
+        h = kh[t];
+        L.mo[t] = kmo[t];
+      } else {
+        dir_cell_geo(r, kp, N, invN, h, L.mo[t]);
+      }
       L.bc[t] = -(r.fe * h);  // negated pressure row: -(f h)
       L.bq[t] = qp == 0 ? r.bc0 : (qp == N ? r.bc1 : 0.0);
     }
   }
   L.bN = (active && l == (N - 1) / CPL) ? (flip ? r.bc0 : r.bc1) : 0.0;
+}
+
+// A lane's share of the kept factors (DirStep::geo_cell / geo_chain), loaded in the step's
+// first round beside the stash and the chain record
+template <int CPL>
+struct LaneGeo {
+  double h[CPL], mo[CPL];
+  ChainGeo g;
+};
+template <int W, int CPL>
+__device__ __forceinline__ void lane_geo_load(const DirStep& da, int c, bool active,
+                                              LaneGeo<CPL>& K) {
+  const int cc = active ? c : 0;
+  const int l = threadIdx.x & (W - 1);
+  const double2* p =
+      reinterpret_cast<const double2*>(da.geo_cell) + ((int64_t)cc * W + l) * CPL;
+#pragma unroll
+  for (int t = 0; t < CPL; ++t) {
+    const double2 v = p[t];
+    K.h[t] = v.x;
+    K.mo[t] = v.y;
+  }
+  const double2* q = reinterpret_cast<const double2*>(da.geo_chain) + 2 * (int64_t)cc;
+  const double2 a = q[0], b = q[1];
+  K.g.T = a.x;
+  K.g.iT = a.y;
+  K.g.mo = b.x;
+  K.g.imo = b.y;
 }
 
 // The job's static arrays in LDS at the start of the dynamic LDS (ints, fixed offsets, so
@@ -5428,10 +5506,10 @@ __device__ __forceinline__ void job_stash_store(const JobStash& S, const StashRe
 // the up sweep, the top part's inputs posted write-through; sA_ / sB_ the slot's
 // back-substitution coefficients (thread = slot). MULTI: every chain's T / It / Ib and
 // every slot's D / J / A / B also to global memory, as k_pc_up_lds stores them.
-template <int W, int CPL>
+template <int W, int CPL, bool KG = false>
 __device__ __forceinline__ void dir_sup_chain_core(const ChainLane<W, CPL>& ch,
                                                    const DirLane<W, CPL>& L, const double* vc,
-                                                   double* park);
+                                                   double* park, double iT_kept = 0.0);
 // the job's slots in one wave with the host-built set-up: phase 1's junction phases then run
 // in wave 0 alone (no workgroup barriers), and the superposition's chain part is split
 // around them (dir_up_v2, dir_sup_core_wave0)
@@ -5439,11 +5517,14 @@ __device__ __forceinline__ bool sup_wslots(const JobStash& S) {
   return S.jwave > 0 && S.js1 - S.js0 <= 64 && S.lv1 > S.lv0;
 }
 
-template <int W, int CPL, bool MULTI = false, bool DENSE = false>
+// KG (k_dir_step_kg: one chain pass): the lane state from the kept factors (kg) and the
+// record's step data; T, 1 / T, mo, 1 / mo of the chain as kept.
+template <int W, int CPL, bool MULTI = false, bool DENSE = false, bool KG = false>
 __device__ __forceinline__ void dir_up_v2(const PcArgs& pa, const DirStep& da, double* lds,
                                           const JobStash& S, ChainRec& rec, DirLane<W, CPL>& L,
                                           double& sA_, double& sB_, double* park = nullptr,
-                                          const int* dn = nullptr, int rootu = -1) {
+                                          const int* dn = nullptr, int rootu = -1,
+                                          const LaneGeo<CPL>* kg = nullptr) {
   double* sT = lds;
   double* sIt = sT + kCapC;
   double* sIb = sIt + kCapC;
@@ -5470,21 +5551,23 @@ __device__ __forceinline__ void dir_up_v2(const PcArgs& pa, const DirStep& da, d
   for (int cb = c0; cb < c1; cb += G) {
     const int c = cb + seg;
     const bool active = c < c1;
-    if (cb != c0) chain_rec_load(da, c, active, rec);
+    if (!KG && cb != c0) chain_rec_load(da, c, active, rec);
     const int cu = !active ? -1 : (cb == c0 ? S.cup(seg) : pa.chain_up[c]);
     const int clo = !active ? -1 : (cb == c0 ? S.clo(seg) : pa.chain_lo[c]);
-    dir_chain_asm_rec<W, CPL>(pa, rec, active, L);
+    dir_chain_asm_rec<W, CPL, KG>(pa, rec, active, L, KG ? kg->h : nullptr,
+                                  KG ? kg->mo : nullptr);
     ChainLane<W, CPL> ch;
-    dir_lane_chain<W, CPL>(pa, L, active, ch);
+    dir_lane_chain<W, CPL, KG>(pa, L, active, ch, KG ? &kg->g : nullptr);
     double vc[CPL];
 #pragma unroll
     for (int t = 0; t < CPL; ++t) vc[t] = L.bc[t];
     double ytop = 0.0, ybot = 0.0;
-    direct_cell_inputs<W, CPL>(pa, ch, L.flip, L.bq, L.bN, vc, ytop, ybot);
+    direct_cell_inputs<W, CPL, KG>(pa, ch, L.flip, L.bq, L.bN, vc, ytop, ybot,
+                                   KG ? kg->g.imo : 0.0);
     // phase 2's u-independent part of the chain (superposition, one pass), here while its
     // lane state is at hand -- or kept for after the barrier (wslots)
     if (core_now) {
-      dir_sup_chain_core<W, CPL>(ch, L, vc, park);
+      dir_sup_chain_core<W, CPL, KG>(ch, L, vc, park, KG ? kg->g.iT : 0.0);
     } else if (park) {  // (the cell inputs wait in the park's cell slots, not in registers)
 #pragma unroll
       for (int t = 0; t < CPL; ++t) park[t * kPcThreads + threadIdx.x] = vc[t];
@@ -5528,11 +5611,11 @@ __device__ __forceinline__ void dir_up_v2(const PcArgs& pa, const DirStep& da, d
   NX_DSTAMP(33);
   if (wslots && threadIdx.x >= 64) {  // the other waves: their chains' part, then leave
     ChainLane<W, CPL> ch;
-    dir_lane_chain<W, CPL>(pa, L, c0 + seg < c1, ch);
+    dir_lane_chain<W, CPL, KG>(pa, L, c0 + seg < c1, ch, KG ? &kg->g : nullptr);
     double vc[CPL];
 #pragma unroll
     for (int t = 0; t < CPL; ++t) vc[t] = park[t * kPcThreads + threadIdx.x];
-    dir_sup_chain_core<W, CPL>(ch, L, vc, park);
+    dir_sup_chain_core<W, CPL, KG>(ch, L, vc, park, KG ? kg->g.iT : 0.0);
     return;
   }
   for (int sl = threadIdx.x; sl < ns; sl += kPcThreads) {  // phase A (ns <= kCapS: one pass)
@@ -5993,12 +6076,13 @@ __device__ __forceinline__ void dir_sup_slots(const PcArgs& pa, double* sup, con
 // not in registers: phase 2's registers are at the 128-VGPR budget of 1024 threads). Run by
 // phase 1 (dir_up_v2) on its chain lane state: ch, L and vc = the cell inputs w_c
 // (direct_cell_inputs), so the Thomas scans of M^{-1} b_q are not repeated.
-template <int W, int CPL>
+// KG (k_dir_step_kg): 1 / T is the handle's kept one (iT_kept), not divided again.
+template <int W, int CPL, bool KG>
 __device__ __forceinline__ void dir_sup_chain_core(const ChainLane<W, CPL>& ch,
                                                    const DirLane<W, CPL>& L, const double* vc,
-                                                   double* park) {
+                                                   double* park, double iT_kept) {
   double zc[CPL], xq[CPL + 1];
-  const double T = ch.T, iT = 1.0 / T;
+  const double T = ch.T, iT = KG ? iT_kept : 1.0 / T;
   double a[CPL], bs[CPL], sa = 0.0, sb = 0.0;
 #pragma unroll
   for (int t = 0; t < CPL; ++t) {
@@ -6028,27 +6112,30 @@ __device__ __forceinline__ void dir_sup_chain_core(const ChainLane<W, CPL>& ch,
 
 // Wave 0's chains' u-independent part (sup_wslots: deferred from phase 1 into the wait; the
 // cell inputs wait in the park's cell slots)
-template <int W, int CPL>
+template <int W, int CPL, bool KG = false>
 __device__ __forceinline__ void dir_sup_core_wave0(const PcArgs& pa, const DirLane<W, CPL>& L,
-                                                   bool active, double* park) {
+                                                   bool active, double* park,
+                                                   const ChainGeo* g = nullptr) {
   if (threadIdx.x >= 64) return;
   ChainLane<W, CPL> ch;
-  dir_lane_chain<W, CPL>(pa, L, active, ch);
+  dir_lane_chain<W, CPL, KG>(pa, L, active, ch, g);
   double vc[CPL];
 #pragma unroll
   for (int t = 0; t < CPL; ++t) vc[t] = park[t * kPcThreads + threadIdx.x];
-  dir_sup_chain_core<W, CPL>(ch, L, vc, park);
+  dir_sup_chain_core<W, CPL, KG>(ch, L, vc, park, KG ? g->iT : 0.0);
 }
 
 // After the top values (sTop by top position): every slot's value (sZ over sZp), then the
 // chains' values from their end values, the fused true residual of those final values, the
 // chains' posts and the job's partial sums (rpart). park: dir_sup_chain_core's values on entry,
 // the final ones on return (stored by dir_sup_store_x after the hand-off).
-template <int W, int CPL>
+// KG (k_dir_step_kg): the chain's T and 1 / T as kept (g).
+template <int W, int CPL, bool KG = false>
 __device__ __forceinline__ void dir_sup_finish(const PcArgs& pa, const DirStep& da, double* lds,
                                                const double* sTop, const JobStash& S,
                                                const DirLane<W, CPL>& L, double* sup,
-                                               double* park, int job) {
+                                               double* park, int job,
+                                               const ChainGeo* g = nullptr) {
   double* sZ = sup + 2 * kCapS;  // (over sZp)
   const double* sH = sZ + kCapS;
   const int* sRho = reinterpret_cast<const int*>(sH + kCapS);
@@ -6073,14 +6160,14 @@ __device__ __forceinline__ void dir_sup_finish(const PcArgs& pa, const DirStep& 
   const double zt = up < 0 ? 0.0 : (up >= js0 && up < js1) ? sZ[up - js0] : sTop[up - ts0];
   const double zb = lo < 0 ? 0.0 : (lo >= js0 && lo < js1) ? sZ[lo - js0] : sTop[lo - ts0];
   ChainLane<W, CPL> ch;
-  dir_lane_chain<W, CPL>(pa, L, active, ch);
+  dir_lane_chain<W, CPL, KG>(pa, L, active, ch, g);
   double zc[CPL], xq[CPL + 1];
 #pragma unroll
   for (int t = 0; t < CPL; ++t) zc[t] = park[t * kPcThreads + threadIdx.x];
 #pragma unroll
   for (int t = 0; t <= CPL; ++t) xq[t] = park[(CPL + t) * kPcThreads + threadIdx.x];
   {
-    const double T = ch.T, iT = 1.0 / T;
+    const double T = ch.T, iT = KG ? g->iT : 1.0 / T;
 #pragma unroll
     for (int t = 0; t < CPL; ++t) {
       const double Dk = ch.D[t];
@@ -6555,8 +6642,14 @@ __device__ __forceinline__ bool dir_publish_xr(const PcArgs& pa, const DirStep& 
 // posts, partials, the published state and all the arithmetic as they are. No step reads
 // da.val or da.val_lm (the residual is formed from the lanes' registers, the multiplier rows'
 // from the posts), so nothing else changes.
-template <int W, int CPL, bool XR, bool SUP, bool DENSE = false, bool KV = false>
+// KG (k_dir_step_kg, the values-free step on the handle's kept chain factors): the chain
+// record is loaded without its end points and R, the lane's share of the table (LaneGeo)
+// in the same first round of loads; the lanes' masses and cell rhs come from the kept h and
+// R h / 6, the chains' T, mo and their reciprocals from the kept entry. Posts, hand-offs,
+// polls, stores, the publish, the give-up paths and the LDS layout are KV's.
+template <int W, int CPL, bool XR, bool SUP, bool DENSE = false, bool KV = false, bool KG = false>
 __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& da, int job) {
+  static_assert(!KG || KV, "the kept chain factors: the values-free step's");
   static_assert(!DENSE || (SUP && !XR), "the dense top: one rank, superposition");
   static_assert(!KV || DENSE, "the values-free step: the dense top's");
   extern __shared__ double dsm[];
@@ -6571,6 +6664,9 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
   NX_DSTAMP(0);
   JobStash S;
   ChainRec rec;
+  LaneGeo<CPL> kgeo;  // (KG) this lane's share of the kept factors
+  const LaneGeo<CPL>* kg = KG ? &kgeo : nullptr;
+  const ChainGeo* kgc = KG ? &kgeo.g : nullptr;
   // DENSE: the job's index lists (kDn*) and its header's dense words: the needed top slots
   // [dn_n0, + dn_need), the owned ones [dn_o0, + dn_own), the root's input position
   int* dn = DENSE ? reinterpret_cast<int*>(dsm + da.dense_off) : nullptr;
@@ -6599,7 +6695,10 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
       if (t <= nt_) d_u0 = pa.top_uoff[t];
       if (t + kPcThreads <= nt_) d_u1 = pa.top_uoff[t + kPcThreads];
     }
-    chain_rec_load(da, S.c0 + (int)threadIdx.x / W, S.c0 + (int)threadIdx.x / W < S.c1, rec);
+    chain_rec_load<KG>(da, S.c0 + (int)threadIdx.x / W, S.c0 + (int)threadIdx.x / W < S.c1, rec);
+    if constexpr (KG)  // (the same round of loads: no dependent round added)
+      lane_geo_load<W, CPL>(da, S.c0 + (int)threadIdx.x / W, S.c0 + (int)threadIdx.x / W < S.c1,
+                            kgeo);
     job_stash_store(S, R, min(S.c1 - S.c0, G));
     if constexpr (DENSE) {
       const int t = threadIdx.x, nt_ = pa.top_nt;
@@ -6655,8 +6754,8 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
   double sA_ = 0.0, sB_ = 0.0;
   const int nt = pa.top_nt, ts0 = pa.top_ts0;
   if (rec_lds) rec_to_lds<W>(rec_lds, c0 + (int)threadIdx.x / W < c1, rec);
-  dir_up_v2<W, CPL, false, DENSE>(pa, da, smem, S, rec, L, sA_, sB_, sup ? park : nullptr, dn,
-                                  dn_rootu);
+  dir_up_v2<W, CPL, false, DENSE, KG>(pa, da, smem, S, rec, L, sA_, sB_, sup ? park : nullptr,
+                                      dn, dn_rootu, kg);
   if (lpark) {
 #pragma unroll
     for (int t = 0; t < CPL; ++t) {
@@ -6710,7 +6809,7 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
       if (grow && col < nt) sG[wv * nt + col] = gp[i];
     }
     dir_sup_slots<W, CPL>(pa, sup_lds, S);
-    if (sup_wslots(S)) dir_sup_core_wave0<W, CPL>(pa, L, lane_on, park);
+    if (sup_wslots(S)) dir_sup_core_wave0<W, CPL, KG>(pa, L, lane_on, park, kgc);
     sup_s = true;
     NX_DSTAMP(20);
     // own stores in the wait, but not wave 0's (it polls and loads: nothing queued before them)
@@ -6865,7 +6964,7 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
         if (sup) {  // its slots' z_p / H and wave 0's chains' part now (not before the top
                     // part: on its own path either way, and there it delayed the top values)
           dir_sup_slots<W, CPL>(pa, sup_lds, S);
-          if (sup_wslots(S)) dir_sup_core_wave0<W, CPL>(pa, L, lane_on, park);
+          if (sup_wslots(S)) dir_sup_core_wave0<W, CPL, KG>(pa, L, lane_on, park, kgc);
           sup_s = true;
         }
       }
@@ -6903,7 +7002,7 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
       // when they fit) in the wait
       if (sup) {
         dir_sup_slots<W, CPL>(pa, sup_lds, S);
-        if (sup_wslots(S)) dir_sup_core_wave0<W, CPL>(pa, L, lane_on, park);
+        if (sup_wslots(S)) dir_sup_core_wave0<W, CPL, KG>(pa, L, lane_on, park, kgc);
         sup_s = true;
         NX_DSTAMP(20);
       }
@@ -6952,10 +7051,10 @@ __device__ __forceinline__ void dir_step_body(const PcArgs& pa, const DirStep& d
   if (sup) {
     if (!sup_s) {  // no top part: the slots now
       dir_sup_slots<W, CPL>(pa, sup_lds, S);
-      if (sup_wslots(S)) dir_sup_core_wave0<W, CPL>(pa, L, lane_on, park);
+      if (sup_wslots(S)) dir_sup_core_wave0<W, CPL, KG>(pa, L, lane_on, park, kgc);
       __syncthreads();
     }
-    dir_sup_finish<W, CPL>(pa, da, smem, sTop, S, L, sup_lds, park, job);
+    dir_sup_finish<W, CPL, KG>(pa, da, smem, sTop, S, L, sup_lds, park, job, kgc);
   } else {
     const bool sl = (int)threadIdx.x < kCapS;
     dir_down_v2<W, CPL>(pa, da, smem, sTop, S, L, keep, sl ? sup_lds[threadIdx.x] : 0.0,
@@ -7035,6 +7134,51 @@ __global__ __launch_bounds__(kPcThreads) void k_dir_step(PcArgs pa, DirStep da) 
 template <int W, int CPL>
 __global__ __launch_bounds__(kPcThreads) void k_dir_step_kv(PcArgs pa, DirStep da) {
   dir_step_body<W, CPL, false, true, true, true>(pa, da, blockIdx.x);
+}
+
+// the values-free step on the chains' kept R-only factors (DirStep::geo_cell / geo_chain,
+// k_chain_geo): the same step without the cells' geometry, the chain sums and the
+// reciprocals, which do not change while R and the decomposition stand; its own name again
+template <int W, int CPL>
+__global__ __launch_bounds__(kPcThreads) void k_dir_step_kg(PcArgs pa, DirStep da) {
+  dir_step_body<W, CPL, false, true, true, true, true>(pa, da, blockIdx.x);
+}
+
+// The kept factors of every chain, by the step's own device functions (dir_cell_geo: the
+// cells' h and R h / 6; dir_lane_chain: the chain's T and mo) from the chain records: the
+// same bits as k_dir_step_kv forms per launch. One lane group per chain, as in the step.
+constexpr int kGeoThreads = 256;
+template <int W, int CPL>
+__global__ __launch_bounds__(kGeoThreads) void k_chain_geo(PcArgs pa, DirStep da, int nc,
+                                                           double* __restrict__ cell,
+                                                           double* __restrict__ chain) {
+  const int c = (int)blockIdx.x * (kGeoThreads / W) + (int)threadIdx.x / W;
+  const int l = threadIdx.x & (W - 1);
+  const bool active = c < nc;
+  ChainRec r;
+  chain_rec_load(da, c, active, r);
+  DirLane<W, CPL> L;
+  double h[CPL];
+#pragma unroll
+  for (int t = 0; t < CPL; ++t) {  // (zeros in the slots past cell N - 1)
+    const int k = l * CPL + t;
+    h[t] = L.mo[t] = 0.0;
+    if (active && k < pa.N)
+      dir_cell_geo(r, r.flip ? pa.N - 1 - k : k, pa.N, pa.invN, h[t], L.mo[t]);
+  }
+  L.e = r.e;
+  L.flip = r.flip;
+  ChainLane<W, CPL> ch;
+  dir_lane_chain<W, CPL>(pa, L, active, ch);
+  if (!active) return;
+  double2* o = reinterpret_cast<double2*>(cell) + ((int64_t)c * W + l) * CPL;
+#pragma unroll
+  for (int t = 0; t < CPL; ++t) o[t] = make_double2(h[t], L.mo[t]);
+  if (l == 0) {
+    double2* q = reinterpret_cast<double2*>(chain) + 2 * (int64_t)c;
+    q[0] = make_double2(ch.T, 1.0 / ch.T);
+    q[1] = make_double2(ch.mo, 1.0 / ch.mo);
+  }
 }
 
 // superposition with the top part solved by the last workgroup to arrive (no top part, a top
@@ -8375,7 +8519,17 @@ struct nx_network {
   int64_t val_version = -1;
   int last_kept = 0;       // the last assembly launch or fused step left the values alone
   int64_t val_writes = 0;  // launches of this handle that wrote them (nx_get_values_kept)
-  bool last_sup = false;    // the last one-launch step ran the superposition instantiation
+  // the chains' R-only factors kept across values-free steps (round 10; k_chain_geo,
+  // k_dir_step_kg): per cell {h, R h / 6}, per chain {T, 1 / T, mo, 1 / mo}, of R version
+  // geo_version and the current decomposition (-1: none; nx_set_preconditioner resets it).
+  // Allocated by the first values-free dense <8, 2> step, freed with the handle. New boundary
+  // values or a new source change the chain records, not these.
+  double* d_geo_cell = nullptr;
+  double* d_geo_chain = nullptr;
+  int64_t geo_version = -1;
+  int geo_builds = 0;  // launches of k_chain_geo (nx_get_geo_kept)
+  int last_geo = 0;    // the last step read them (k_dir_step_kg)
+  bool last_sup = false;   // the last one-launch step ran the superposition instantiation
   unsigned* d_tsync = nullptr;  // k_dir_team_up's arrival counter (several ranks; pc_bufs)
   bool need_r = false;     // the last pass kept no residual: a refinement step forms it first
   int last_dir_path = 0;   // the last direct solve: 0 four launches, 1 k_dir_step
@@ -11050,7 +11204,8 @@ NX_API int nx_destroy(nx_network_t* h) {
                   h->cpc_slot, h->cpc_ent_off, h->cpc_ent, h->cpc_slot_of, h->cpc_nrow2,
                   h->cpc_rec2, h->cpc_inv, h->cpc_gj, h->cpc_scr, h->cpc_w, h->cpc_nb2,
                   h->cpc_se0, h->cpc_rho, h->cpc_xd,
-                  h->fe_tpl_rbuf, h->fe_tpl_rs, h->fe_tpl_shape, h->fe_tpl_lam};
+                  h->fe_tpl_rbuf, h->fe_tpl_rs, h->fe_tpl_shape, h->fe_tpl_lam,
+                  h->d_geo_cell, h->d_geo_chain};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   for (void* p : h->pc_bufs)
@@ -11179,6 +11334,7 @@ int launch_assembly(nx_network* h, int lhs, int rhs, int dq = -1, hipStream_t s 
   if (!s) s = h->stream;
   if (dq < 0) dq = lhs;
   if (dq) h->dq_stale = false;
+  if (lhs || rhs) h->last_geo = 0;  // (a separate assembly: no step read the kept factors)
   if (lhs) {  // every value, stream-ordered ahead of its readers: the stamp (val_version)
     h->val_writes += 1;
     h->last_kept = 0;
@@ -11526,9 +11682,13 @@ size_t dense_lds_extra(const nx_network* h);
 // <8, 2> step's values-free one, k_dir_step_kv, which run_dstep asks for with kv while the
 // values in device memory are current). A storing step's stamp is reset here, before its
 // launch (nx_network::val_version; run_dstep sets it again once the state was published).
+// kg (with kv; run_dstep made the kept chain factors current): k_dir_step_kg, the values-free
+// step that reads them.
 template <int W, int CPL>
-bool launch_dstep_wc(nx_network* h, double rtol, bool prof, bool kv) {
+bool launch_dstep_wc(nx_network* h, double rtol, bool prof, bool kv, bool kg) {
   DirStep da = dir_args(h, rtol);
+  da.geo_cell = h->d_geo_cell;
+  da.geo_chain = h->d_geo_chain;
   const bool sup = sup_launch<CPL>(da);
   h->last_sup = sup;
   // the dense top (run_dstep decided and made G valid): its index lists come after the rest
@@ -11543,6 +11703,13 @@ bool launch_dstep_wc(nx_network* h, double rtol, bool prof, bool kv) {
   }
   const hipEvent_t e0 = prof ? h->dev[0] : nullptr, e1 = prof ? h->dev[1] : nullptr;
   if constexpr (W == 8 && CPL == 2) {
+    if (dense && kv && kg) {
+      opt_in_lds(reinterpret_cast<const void*>(&k_dir_step_kg<W, CPL>), kDirLdsMax);
+      hipExtLaunchKernelGGL((k_dir_step_kg<W, CPL>), dim3(h->pc_jobs), dim3(kPcThreads), lds,
+                            h->stream, e0, e1, 0, h->pa, da);
+      h->last_geo = 1;
+      return false;
+    }
     if (dense && kv) {
       opt_in_lds(reinterpret_cast<const void*>(&k_dir_step_kv<W, CPL>), kDirLdsMax);
       hipExtLaunchKernelGGL((k_dir_step_kv<W, CPL>), dim3(h->pc_jobs), dim3(kPcThreads), lds,
@@ -11642,23 +11809,54 @@ int ensure_top_inverse(nx_network* h) {
   return NX_OK;
 }
 
+// The chains' R-only factors (nx_network::d_geo_*), valid for this decomposition and this R
+// before a values-free dense <8, 2> step reads them: k_chain_geo from the chain records,
+// stream-ordered ahead of the step like ensure_top_inverse; rebuilt only when R's contents or
+// the decomposition change (r_version / geo_version), not for new boundary values or a new
+// source. Only a values-free step asks, so a caller who changes R every step never pays.
+// NXHIP_KEEP_GEO=0 (read per solve: tests and the A/B switch it) keeps k_dir_step_kv.
+bool keep_geo_on(const nx_network* h) {
+  const char* e = std::getenv("NXHIP_KEEP_GEO");
+  return (e == nullptr || std::atoi(e) != 0) && h->dense_now && h->dstep_variant == 5 &&
+         h->d_crec != nullptr && h->E > 0;
+}
+int ensure_chain_geo(nx_network* h) {
+  if (h->geo_version == h->r_version) return NX_OK;
+  constexpr int W = 8, CPL = 2;
+  if (!h->d_geo_cell) CHECK(dalloc(&h->d_geo_cell, (int64_t)h->E * W * 2 * CPL));
+  if (!h->d_geo_chain) CHECK(dalloc(&h->d_geo_chain, 4 * (int64_t)h->E));
+  DirStep da{};
+  da.crec = h->d_crec;
+  da.ci = h->d_ci;
+  hipLaunchKernelGGL((k_chain_geo<W, CPL>), dim3(grid_of(h->E, kGeoThreads / W)),
+                     dim3(kGeoThreads), 0, h->stream, h->pa, da, (int)h->E, h->d_geo_cell,
+                     h->d_geo_chain);
+  HIPCALL(hipGetLastError());
+  h->geo_version = h->r_version;
+  h->geo_builds += 1;
+  return NX_OK;
+}
+
 // Launch k_dir_step and wait for its published state (the host's sequence advances).
 int run_dstep(nx_network* h, double rtol, bool prof) {
   h->dense_now = dstep_dense_on(h);
   if (h->dense_now) CHECK(ensure_top_inverse(h));
   // (ensure_top_inverse's dq-only assembly launch writes no values: the stamp stands)
   const bool kv = values_current(h);
+  const bool kg = kv && keep_geo_on(h);
+  if (kg) CHECK(ensure_chain_geo(h));
+  h->last_geo = 0;
   const int64_t rv = h->r_version;
   bool stored = true;
   switch (h->dstep_variant) {
-    case 0: stored = launch_dstep_wc<16, 1>(h, rtol, prof, kv); break;
-    case 1: stored = launch_dstep_wc<16, 2>(h, rtol, prof, kv); break;
-    case 2: stored = launch_dstep_wc<16, 4>(h, rtol, prof, kv); break;
-    case 3: stored = launch_dstep_wc<64, 2>(h, rtol, prof, kv); break;
-    case 5: stored = launch_dstep_wc<8, 2>(h, rtol, prof, kv); break;
-    case 7: stored = launch_dstep_wc<8, 4>(h, rtol, prof, kv); break;
-    case 10: stored = launch_dstep_wc<8, 3>(h, rtol, prof, kv); break;
-    default: stored = launch_dstep_wc<64, 4>(h, rtol, prof, kv); break;
+    case 0: stored = launch_dstep_wc<16, 1>(h, rtol, prof, kv, kg); break;
+    case 1: stored = launch_dstep_wc<16, 2>(h, rtol, prof, kv, kg); break;
+    case 2: stored = launch_dstep_wc<16, 4>(h, rtol, prof, kv, kg); break;
+    case 3: stored = launch_dstep_wc<64, 2>(h, rtol, prof, kv, kg); break;
+    case 5: stored = launch_dstep_wc<8, 2>(h, rtol, prof, kv, kg); break;
+    case 7: stored = launch_dstep_wc<8, 4>(h, rtol, prof, kv, kg); break;
+    case 10: stored = launch_dstep_wc<8, 3>(h, rtol, prof, kv, kg); break;
+    default: stored = launch_dstep_wc<64, 4>(h, rtol, prof, kv, kg); break;
   }
   HIPCALL(hipGetLastError());
   h->dstep_epoch += 1;
@@ -16338,6 +16536,14 @@ NX_API int nx_get_values_kept(nx_network_t* h, int32_t* last_step_kept, int64_t*
   return NX_OK;
 }
 
+NX_API int nx_get_geo_kept(nx_network_t* h, int32_t* ran, int32_t* builds) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  // (no flush: a deferred nx_assemble stays deferred, as for nx_get_values_kept)
+  if (ran) *ran = h->last_geo;
+  if (builds) *builds = h->geo_builds;
+  return NX_OK;
+}
+
 NX_API int nx_debug_set_wait_polls(nx_network_t* h, uint32_t polls) {
   if (!h) return fail(NX_ERR_ARG, "null handle");
   h->dstep_polls = polls;
@@ -16942,6 +17148,7 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
   h->d_job_hdr = nullptr;
   h->d_crec = nullptr;
   h->d_ci = nullptr;
+  h->geo_version = -1;  // (ensure_chain_geo: a new decomposition's chain order)
   if (h->dstep_ok || h->xr_ok) {
     std::vector<int> hdr((size_t)kJobHdr * n_jobs, 0);
     int mlv = 1, mns = 0, mnd = 0, mch = 0;
