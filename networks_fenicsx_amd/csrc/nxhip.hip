@@ -12378,8 +12378,14 @@ int launch_xr_wc(const Team& t, double rtol) {
     HIPCALL(hipMemcpyAsync(g->xg_dev, g->xg_host, bp + bd + bo, hipMemcpyHostToDevice, g->stream));
     const char* db = static_cast<const char*>(g->xg_dev);
     const int cap = (int)(160 * 1024 - xr_static_lds(t.hs[0]->dstep_variant));
-    for (int r = 0; r < P; ++r) t.hs[r]->last_sup = sup_launch<CPL>(das[0]);
-    if (sup_launch<CPL>(das[0])) {
+    // one instantiation for every rank's workgroups: superposition only if every rank asks
+    // for it (the SUP body ignores da.sup -- a rank with a several-pass job or without the
+    // park must not run it); the plain body reads nothing that da.sup guards, and lds is
+    // the ranks' largest
+    bool sup = true;
+    for (int r = 0; r < P; ++r) sup = sup && sup_launch<CPL>(das[r]);
+    for (int r = 0; r < P; ++r) t.hs[r]->last_sup = sup;
+    if (sup) {
       opt_in_lds(reinterpret_cast<const void*>(&k_dir_xg<W, CPL, CPL <= 2>), cap);
       hipLaunchKernelGGL((k_dir_xg<W, CPL, CPL <= 2>), dim3(goff[P]), dim3(kPcThreads), lds,
                          g->stream, reinterpret_cast<const PcArgs*>(db),

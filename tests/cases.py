@@ -90,6 +90,9 @@ CASES = {
     "tree5_N15": (lambda: ng.make_tree(5, 5, 5), 15, "smallest_last", p_y),
     "tree5_N16": (lambda: ng.make_tree(5, 5, 5), 16, "smallest_last", p_y),
     "tree5_3d_N31": (lambda: ng.make_tree(5, 2, 3), 31, "smallest_last", p_x),
+    # 511 edges: one job of a rank's half has 255 or 256 chains, two chain passes of the
+    # one-launch step (tests/unlike_ranks.py)
+    "tree9_N15": (lambda: ng.make_tree(9, 9, 9), 15, "smallest_last", p_y),
 }
 
 # every configuration of tests/golden/systems.npz (tests/golden/make_golden.py)

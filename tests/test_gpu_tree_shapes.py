@@ -689,8 +689,11 @@ def test_group_direct_on_hubs(name, nranks):
             x[DM.global_rows(a.local_problem, E, mesh.bifurcation_index)] = xl
         err = block_errors(x, x_ref, E, N)
         d1 = np.linalg.norm(x - x_one) / np.linalg.norm(x_one)
-        print(f"{name} P{nranks}: passes {it} rr {rr:.2e} blocks "
+        paths = [a.handle.direct_path() for a in grp.assemblers]
+        sups = [a.handle.direct_sup() for a in grp.assemblers]
+        print(f"{name} P{nranks}: paths {paths} sup {sups} passes {it} rr {rr:.2e} blocks "
               + " ".join(f"{e:.2e}" for e in err) + f"; vs one rank {d1:.2e}")
+        assert len(set(paths)) == 1, paths  # (which direct path ran: the same on every rank)
         assert conv and grp.solver_used == "direct" and it in (1, 2) and rr <= 1e-12, (it, rr)
         assert max(err) <= SOL_TOL, err
         assert d1 <= 1e-12, d1

@@ -44,7 +44,8 @@ def _free_port() -> int:
         return int(s.getsockname()[1])
 
 
-def _run(tmp_path, case, P, steps=6, give_up_rank=-1, which=1, give_up_step=2, timeout=240):
+def _run(tmp_path, case, P, steps=6, give_up_rank=-1, which=1, give_up_step=2, timeout=240,
+         target_jobs=None):
     port = _free_port()
     procs = []
     for r in range(P):
@@ -54,6 +55,8 @@ def _run(tmp_path, case, P, steps=6, give_up_rank=-1, which=1, give_up_step=2, t
                "--steps", str(steps), "--give-up-rank", str(give_up_rank),
                "--give-up-which", str(which), "--give-up-step", str(give_up_step),
                "--out", str(tmp_path)]
+        if target_jobs is not None:
+            cmd += ["--target-jobs", *[str(j) for j in target_jobs]]
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.STDOUT, start_new_session=True))
     outs = []
@@ -115,6 +118,28 @@ def test_processes_exchange_step(tmp_path, case, P):
     for x in xs[1:]:
         np.testing.assert_array_equal(x, xs[0])
     assert all(s["xr"]["why"] == 0 and not s["xr"]["off"] for r in ranks for s in r)
+
+
+@pytest.mark.parametrize("jobs,sup", [((256, 1), (True, False)), ((1, 256), (False, True))],
+                         ids=["U1", "U2"])
+def test_processes_unlike_ranks(tmp_path, jobs, sup):
+    """Unlike ranks across processes (tests/unlike_ranks.py, U1 and U2 with the case's own
+    coefficients): one rank of 64 jobs of at most 4 chains, which takes the superposition
+    instantiation of ``k_dir_xr``, and one rank of ONE job of 255 / 256 chains -- two chain
+    passes, the plain kernel -- exchange through the IPC mailboxes (``xr_coarse`` and
+    ``dir_publish_xr`` do not depend on the instantiation). Every step on the exchange path on
+    every rank, the same residual bits on every rank, the oracle at 1e-10, the steps
+    bit-identical, ``direct_sup()`` per rank as the rank's own decomposition decides it."""
+    case, P = "tree9_N15", 2
+    Ab, x_ref = _reference(case)
+    ranks, data = _run(tmp_path, case, P, target_jobs=jobs)
+    xs = _check_steps(ranks, data, Ab, x_ref)
+    assert {s["path"] for r in ranks for s in r} == {"exchange"}
+    for x in xs[1:]:
+        np.testing.assert_array_equal(x, xs[0])
+    assert all(s["xr"]["why"] == 0 and not s["xr"]["off"] for r in ranks for s in r)
+    for k in range(len(ranks[0])):
+        assert tuple(r[k]["sup"] for r in ranks) == sup, (k, [r[k]["sup"] for r in ranks])
 
 
 @pytest.mark.parametrize("P", [2, 3])

@@ -9,7 +9,8 @@ agreement, the graph path -- with its collectives through shared memory. Host co
 
 Each step: assemble + solve (the direct solve), then a gloo barrier (a host collective
 between steps, as a user's code would have). Writes ``rank<r>.json`` (per step: residual,
-path, exchange status) and ``rank<r>.npz`` (global rows, x per step) into ``--out``.
+path, superposition or plain phase 2, exchange status) and ``rank<r>.npz`` (global rows, x per
+step) into ``--out``.
 """
 
 from __future__ import annotations
@@ -32,6 +33,8 @@ def main() -> int:
     ap.add_argument("--give-up-rank", type=int, default=-1)
     ap.add_argument("--give-up-which", type=int, default=1, help="0: exchange 1, 1: exchange 2")
     ap.add_argument("--give-up-step", type=int, default=2)
+    ap.add_argument("--target-jobs", type=int, nargs="*", default=None,
+                    help="one value per rank: that rank's decomposition (256: the default's)")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
 
@@ -51,6 +54,18 @@ def main() -> int:
     G = make() if rank == 0 else None
     mesh = NetworkMesh(G, N=N, color_strategy=strategy, comm=TorchComm())
     asm = HydraulicNetworkAssembler(mesh)
+    if args.target_jobs is not None:
+        # unlike ranks (tests/unlike_ranks.py): a rank whose value is not the default's builds
+        # its own decomposition; EVERY rank uploads again -- set_preconditioner holds an
+        # all-reduce and an all-gather
+        from networks_fenicsx_amd.precond import build_tree_preconditioner
+
+        assert len(args.target_jobs) == world, args.target_jobs
+        if args.target_jobs[rank] != 256:
+            src, dst = mesh.edges
+            asm._pc = build_tree_preconditioner(asm.local_problem, src, dst, mesh.degrees,
+                                                target_jobs=args.target_jobs[rank])
+        asm.set_preconditioner(True)
     asm.compute_forms(p_bc_ex=pbc)
     asm.set_direct(True)
     h = asm.handle
@@ -63,7 +78,7 @@ def main() -> int:
         it, rr, conv = h.solve(1e-12, 50000, 4)
         steps.append({"step": k, "iterations": it, "relres": rr, "converged": conv,
                       "solver": "direct" if h.solver()[1] == 1 else "minres",
-                      "path": h.direct_path(), "xr": h.xr_status()})
+                      "path": h.direct_path(), "sup": h.direct_sup(), "xr": h.xr_status()})
         xs.append(h.solution())
         dist.barrier()
     out = Path(args.out)
