@@ -246,6 +246,14 @@ int nx_get_pc_exact(nx_network_t* h, int32_t* enabled);
  */
 int nx_set_pc_kernels(nx_network_t* h, int32_t global);
 int nx_get_pc_kernels(nx_network_t* h, int32_t* lds);
+/*
+ * The lane shapes of the uploaded preconditioner (read only; tests pin the selection with
+ * it): a chain is run by W lanes of CPL cells each. sweep_*: the shape of the sweep kernels.
+ * step_*: the shape the one-launch / exchange step has for the handle's N, or (0, 0) where no
+ * one-launch instantiation exists (N > 256). NX_ERR_STATE without a preconditioner.
+ */
+int nx_get_lane_shapes(nx_network_t* h, int32_t* sweep_w, int32_t* sweep_cpl, int32_t* step_w,
+                       int32_t* step_cpl);
 
 /*
  * Which solve nx_solve runs. solver = 0 (default): MINRES. solver = 1: the direct solve

@@ -124,6 +124,7 @@ _SIGS = {
     "nx_set_cut": (C.c_int, [_h, _i32, _pi32, _pi32, _pi32, _pd]),
     "nx_set_pc_kernels": (C.c_int, [_h, _i32]),
     "nx_get_pc_kernels": (C.c_int, [_h, _pi32]),
+    "nx_get_lane_shapes": (C.c_int, [_h, _pi32, _pi32, _pi32, _pi32]),
     "nx_set_pc_dense": (C.c_int, [_h, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32,
                                   _pi32, _pi32, _pi32, _pi32]),
     "nx_set_pc_exact": (C.c_int, [_h, _i32]),
@@ -1054,6 +1055,13 @@ class Handle:
         v = C.c_int32(0)
         check(lib().nx_get_pc_kernels(self.ptr, C.byref(v)))
         return bool(v.value)
+
+    def lane_shapes(self) -> tuple[tuple[int, int], tuple[int, int]]:
+        """``nx_get_lane_shapes``: the ``(W, CPL)`` of the sweep kernels and of the one-launch /
+        exchange step (``(0, 0)`` where no one-launch instantiation exists, N > 256)."""
+        v = [C.c_int32(0) for _ in range(4)]
+        check(lib().nx_get_lane_shapes(self.ptr, *[C.byref(x) for x in v]))
+        return (v[0].value, v[1].value), (v[2].value, v[3].value)
 
     def set_cut(self, n_cut: int, lm_cut, gk_off, gk_row, gk_coef) -> None:
         """Cut bifurcations of a multi-rank problem (``nx_set_cut``): their multiplier rows

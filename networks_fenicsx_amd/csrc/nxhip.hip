@@ -6283,9 +6283,9 @@ __device__ __forceinline__ void dir_stores_v2(const PcArgs& pa, const DirStep& d
 // k_dir_step's waiting workgroups leave the stores of their first kDirFreeWaves waves until
 // after phase 2: those waves poll for the top values and load them without waiting for the
 // drain of the others' stores. The top solver's assembly is stored by the first workgroups to
-// arrive (helpers), one chain per wave on the other waves: kDirHelpChains chains each.
+// arrive (helpers), one chain per wave on the other waves: kPcThreads / 64 - kDirFreeWaves
+// chains each.
 constexpr int kDirFreeWaves = 4;
-constexpr int kDirHelpChains = kPcThreads / 64 - kDirFreeWaves;
 // dynamic LDS of k_dir_step: at most this (the static __shared__ words -- flags, the partial
 // sums of phase 2 and the publish -- take the rest of the CU's 160 KiB)
 constexpr int kDirLdsMax = 160 * 1024 - 2048;
@@ -8297,6 +8297,86 @@ __global__ void k_group_sum(GroupPtrs g, int P, int n) {
 // Host side
 // ======================================================================================
 
+// ---- lane shapes: which <W, CPL> instantiation runs an edge of N cells --------------------
+// A chain is swept by W lanes of CPL cells each. The table below is the only place that
+// names the shapes, their sizes and which kernel families are compiled for them; the
+// handle stores two of them (nx_network::sweep_lane / step_lane) and every launch site goes
+// through with_lane.
+namespace {
+enum class Lane : int { k8x2, k8x3, k8x4, k16x2, k16x4, k64x2, k64x4, k64x8, k64x16 };
+// the kernel families: the sweeps (k_pc_*, k_b_*, k_dir_team_up), the one-launch step
+// (k_dir_step*), the exchange step (k_dir_xr / k_dir_xg)
+enum : unsigned { kLaneSweep = 1, kLaneStep = 2, kLaneXr = 4 };
+struct LaneInfo {
+  int w, cpl;
+  unsigned sets;
+};
+constexpr LaneInfo kLanes[] = {
+    {8, 2, kLaneSweep | kLaneStep | kLaneXr},  // k8x2
+    {8, 3, kLaneStep | kLaneXr},               // k8x3
+    {8, 4, kLaneStep | kLaneXr},               // k8x4
+    {16, 2, kLaneSweep},                       // k16x2
+    {16, 4, kLaneSweep | kLaneStep | kLaneXr}, // k16x4
+    {64, 2, kLaneSweep | kLaneStep},           // k64x2
+    {64, 4, kLaneSweep | kLaneStep},           // k64x4
+    // (N > 256: the step's lane state would spill thousands of VGPRs -- the separate launches
+    // run those; no one-launch instantiation)
+    {64, 8, kLaneSweep},                       // k64x8
+    {64, 16, kLaneSweep},                      // k64x16
+};
+constexpr int kNumLanes = (int)(sizeof(kLanes) / sizeof(kLanes[0]));
+constexpr int kMaxCellsPerEdge = 1024;  // 64 x 16
+constexpr const LaneInfo& lane_info(Lane s) { return kLanes[(int)s]; }
+constexpr bool lane_in(Lane s, unsigned set) { return (lane_info(s).sets & set) != 0; }
+
+// the sweeps' shape for N <= kMaxCellsPerEdge cells per edge
+Lane sweep_lane_of(int N) {
+  if (N <= 16) return Lane::k8x2;  // 8 lanes x 2 cells: one chain round per job (swept: 16x1 +8%)
+  // (N <= 32 by 8 lanes x 4 cells, 128 chains per pass: slower, 8-rank C4 rehearsal r03o --
+  // team up 50 -> 57 us, down 41 -> 66 us per rank; the lanes' serial work dominates)
+  if (N <= 32) return Lane::k16x2;
+  if (N <= 64) return Lane::k16x4;
+  if (N <= 128) return Lane::k64x2;
+  if (N <= 256) return Lane::k64x4;
+  if (N <= 512) return Lane::k64x8;
+  return Lane::k64x16;
+}
+// the one-launch / exchange step's shape (k_dir_step / k_dir_xr / k_dir_xg): N <= 32 by 8
+// lanes so a job's <= 128 chains run in ONE pass (phase 2 on phase 1's registers, no reloads):
+// 2 cells per lane up to N = 16, 3 up to 24 (C4's N = 19), 4 up to 32 (register spills); above
+// that the sweeps' shape, which has a step only where the table says so
+Lane step_lane_of(int N, Lane sweep) {
+  return N <= 16 ? Lane::k8x2 : N <= 24 ? Lane::k8x3 : N <= 32 ? Lane::k8x4 : sweep;
+}
+
+// f(integral_constant<int, W>, integral_constant<int, CPL>) -> int for the runtime shape s, when
+// s belongs to SET; NX_ERR_STATE otherwise. One direct switch (the per-step launch path runs
+// through it): no default, so a new enumerator without a case is a -Wswitch warning.
+template <unsigned SET, Lane S, class F>
+int lane_call(F& f) {
+  if constexpr (lane_in(S, SET))
+    return f(std::integral_constant<int, lane_info(S).w>{},
+             std::integral_constant<int, lane_info(S).cpl>{});
+  else
+    return fail(NX_ERR_STATE, "no kernel of this family is compiled for the handle's lane shape");
+}
+template <unsigned SET, class F>
+int with_lane(Lane s, F&& f) {
+  switch (s) {
+    case Lane::k8x2: return lane_call<SET, Lane::k8x2>(f);
+    case Lane::k8x3: return lane_call<SET, Lane::k8x3>(f);
+    case Lane::k8x4: return lane_call<SET, Lane::k8x4>(f);
+    case Lane::k16x2: return lane_call<SET, Lane::k16x2>(f);
+    case Lane::k16x4: return lane_call<SET, Lane::k16x4>(f);
+    case Lane::k64x2: return lane_call<SET, Lane::k64x2>(f);
+    case Lane::k64x4: return lane_call<SET, Lane::k64x4>(f);
+    case Lane::k64x8: return lane_call<SET, Lane::k64x8>(f);
+    case Lane::k64x16: return lane_call<SET, Lane::k64x16>(f);
+  }
+  return fail(NX_ERR_STATE, "lane shape out of range");
+}
+}  // namespace
+
 struct LeanGraphs {
   hipGraphExec_t head_exec = nullptr;
   hipGraph_t head_graph = nullptr;
@@ -8383,11 +8463,8 @@ struct nx_network {
   // tree Schur preconditioner (nx_set_preconditioner)
   bool pc = false;
   bool pc_lds = false;  // every job fits the LDS kernels' caps
-  int pc_variant = 0;   // (W, CPL) instantiation
-  // the fused step's (W, CPL) (k_dir_step / k_dir_xr / k_dir_xg): N <= 32 by 8 lanes so a
-  // job's <= 128 chains run in ONE pass (phase 2 on phase 1's registers, no reloads): 2
-  // cells per lane up to N = 16, 3 up to 24 (C4's N = 19), 4 up to 32 (register spills)
-  int dstep_variant = 0;
+  Lane sweep_lane = Lane::k64x4;  // the sweeps' <W, CPL> (sweep_lane_of)
+  Lane step_lane = Lane::k64x4;   // the one-launch / exchange step's (step_lane_of)
   int pc_jobs = 0;
   int64_t pc_slots = 0;
   int64_t pc_ndc = 0;
@@ -9063,18 +9140,11 @@ void launch_pc_wc(nx_network* h, double* y, const double* r2, MrState* st, MrSta
 template <bool MULTI>
 void launch_pc(nx_network* h, double* y, const double* r2, MrState* st, MrState* other, int mode,
                int half, double* zout = nullptr, const hipEvent_t* evs = nullptr) {
-  switch (h->pc_variant) {
-    case 0: launch_pc_wc<MULTI, 16, 1>(h, y, r2, st, other, mode, half, zout, evs); break;
-    case 1: launch_pc_wc<MULTI, 16, 2>(h, y, r2, st, other, mode, half, zout, evs); break;
-    case 2: launch_pc_wc<MULTI, 16, 4>(h, y, r2, st, other, mode, half, zout, evs); break;
-    case 3: launch_pc_wc<MULTI, 64, 2>(h, y, r2, st, other, mode, half, zout, evs); break;
-    case 5: launch_pc_wc<MULTI, 8, 2>(h, y, r2, st, other, mode, half, zout, evs); break;
-    case 6: launch_pc_wc<MULTI, 4, 4>(h, y, r2, st, other, mode, half, zout, evs); break;
-    case 7: launch_pc_wc<MULTI, 8, 4>(h, y, r2, st, other, mode, half, zout, evs); break;
-    case 8: launch_pc_wc<MULTI, 64, 8>(h, y, r2, st, other, mode, half, zout, evs); break;
-    case 9: launch_pc_wc<MULTI, 64, 16>(h, y, r2, st, other, mode, half, zout, evs); break;
-    default: launch_pc_wc<MULTI, 64, 4>(h, y, r2, st, other, mode, half, zout, evs); break;
-  }
+  // (sweep_lane is a sweep shape by construction: sweep_lane_of)
+  (void)with_lane<kLaneSweep>(h->sweep_lane, [&](auto w, auto cpl) {
+    launch_pc_wc<MULTI, w(), cpl()>(h, y, r2, st, other, mode, half, zout, evs);
+    return NX_OK;
+  });
 }
 
 int nB_of(const nx_network* h) { return h->pc ? h->pc_jobs + 1 : h->nB; }
@@ -11436,11 +11506,6 @@ int chain_rec_refresh(nx_network* h) {
   HIPCALL(hipStreamSynchronize(h->stream));
   return NX_OK;
 }
-// the tile width W of a (W, CPL) variant (nx_set_preconditioner's choice)
-int variant_w(int v) { return v == 5 || v == 7 || v == 10 ? 8 : v == 6 ? 4 : v <= 2 ? 16 : 64; }
-int variant_cpl(int v) {
-  return v == 0 ? 1 : (v == 1 || v == 3 || v == 5) ? 2 : v == 10 ? 3 : v == 8 ? 8 : v == 9 ? 16 : 4;
-}
 }  // namespace
 
 NX_API int nx_assemble(nx_network_t* h, int32_t lhs, int32_t rhs) {
@@ -11718,13 +11783,15 @@ bool launch_dstep_wc(nx_network* h, double rtol, bool prof, bool kv, bool kg) {
     }
   }
   h->val_version = -1;
-  if constexpr (CPL <= 2) {
+  if constexpr (W == 8 && CPL == 2) {  // (dense_now: dstep_dense_on asks for this shape)
     if (dense) {
       opt_in_lds(reinterpret_cast<const void*>(&k_dir_step<W, CPL, true>), kDirLdsMax);
       hipExtLaunchKernelGGL((k_dir_step<W, CPL, true>), dim3(h->pc_jobs), dim3(kPcThreads), lds,
                             h->stream, e0, e1, 0, h->pa, da);
       return true;
     }
+  }
+  if constexpr (CPL <= 2) {
     if (sup) {
       opt_in_lds(reinterpret_cast<const void*>(&k_dir_step_ts<W, CPL>), kDirLdsMax);
       hipExtLaunchKernelGGL((k_dir_step_ts<W, CPL>), dim3(h->pc_jobs), dim3(kPcThreads), lds,
@@ -11750,17 +11817,10 @@ void launch_dteam_wc(nx_network* h) {
                      h->pa, da);
 }
 void launch_dteam(nx_network* h) {
-  switch (h->pc_variant) {
-    case 0: launch_dteam_wc<16, 1>(h); break;
-    case 1: launch_dteam_wc<16, 2>(h); break;
-    case 2: launch_dteam_wc<16, 4>(h); break;
-    case 3: launch_dteam_wc<64, 2>(h); break;
-    case 5: launch_dteam_wc<8, 2>(h); break;
-    case 7: launch_dteam_wc<8, 4>(h); break;
-    case 8: launch_dteam_wc<64, 8>(h); break;
-    case 9: launch_dteam_wc<64, 16>(h); break;
-    default: launch_dteam_wc<64, 4>(h); break;
-  }
+  (void)with_lane<kLaneSweep>(h->sweep_lane, [&](auto w, auto cpl) {
+    launch_dteam_wc<w(), cpl()>(h);
+    return NX_OK;
+  });
 }
 // k_dir_team_up applies: the LDS sweeps with a top part (every rank's coarse junctions are
 // top slots), the fused residual, the counter, one pending assembly of values and rhs.
@@ -11786,7 +11846,7 @@ bool dstep_dense_on(const nx_network* h) {
   const int nt = h->top_nt;
   const int nup = (h->dense_nu + 1) & ~1, ntp = (nt + 1) & ~1;
   return h->pa.dense && h->dense_hdr && nt > 0 && h->pa.n_top == nt && h->pa.G != nullptr &&
-         h->dstep_variant == 5 /* <8, 2>: the one measured */ && h->dstep_park && !h->dstep_multi &&
+         h->step_lane == Lane::k8x2 /* the one measured */ && h->dstep_park && !h->dstep_multi &&
          (dir_sup_mode() & 1) != 0 && nup + ntp <= h->dstep_main &&
          h->dstep_lds + dense_lds_extra(h) <= (size_t)kDirLdsMax;
 }
@@ -11817,7 +11877,7 @@ int ensure_top_inverse(nx_network* h) {
 // NXHIP_KEEP_GEO=0 (read per solve: tests and the A/B switch it) keeps k_dir_step_kv.
 bool keep_geo_on(const nx_network* h) {
   const char* e = std::getenv("NXHIP_KEEP_GEO");
-  return (e == nullptr || std::atoi(e) != 0) && h->dense_now && h->dstep_variant == 5 &&
+  return (e == nullptr || std::atoi(e) != 0) && h->dense_now && h->step_lane == Lane::k8x2 &&
          h->d_crec != nullptr && h->E > 0;
 }
 int ensure_chain_geo(nx_network* h) {
@@ -11848,16 +11908,10 @@ int run_dstep(nx_network* h, double rtol, bool prof) {
   h->last_geo = 0;
   const int64_t rv = h->r_version;
   bool stored = true;
-  switch (h->dstep_variant) {
-    case 0: stored = launch_dstep_wc<16, 1>(h, rtol, prof, kv, kg); break;
-    case 1: stored = launch_dstep_wc<16, 2>(h, rtol, prof, kv, kg); break;
-    case 2: stored = launch_dstep_wc<16, 4>(h, rtol, prof, kv, kg); break;
-    case 3: stored = launch_dstep_wc<64, 2>(h, rtol, prof, kv, kg); break;
-    case 5: stored = launch_dstep_wc<8, 2>(h, rtol, prof, kv, kg); break;
-    case 7: stored = launch_dstep_wc<8, 4>(h, rtol, prof, kv, kg); break;
-    case 10: stored = launch_dstep_wc<8, 3>(h, rtol, prof, kv, kg); break;
-    default: stored = launch_dstep_wc<64, 4>(h, rtol, prof, kv, kg); break;
-  }
+  CHECK(with_lane<kLaneStep>(h->step_lane, [&](auto w, auto cpl) {
+    stored = launch_dstep_wc<w(), cpl()>(h, rtol, prof, kv, kg);
+    return NX_OK;
+  }));
   HIPCALL(hipGetLastError());
   h->dstep_epoch += 1;
   h->seq += 1;
@@ -11877,18 +11931,10 @@ int run_dstep(nx_network* h, double rtol, bool prof) {
 }
 
 int launch_direct(nx_network* h, double rtol, int refine, bool prof = false) {
-  switch (h->pc_variant) {
-    case 0: launch_direct_wc<16, 1>(h, rtol, refine, prof); break;
-    case 1: launch_direct_wc<16, 2>(h, rtol, refine, prof); break;
-    case 2: launch_direct_wc<16, 4>(h, rtol, refine, prof); break;
-    case 3: launch_direct_wc<64, 2>(h, rtol, refine, prof); break;
-    case 5: launch_direct_wc<8, 2>(h, rtol, refine, prof); break;
-    case 6: launch_direct_wc<4, 4>(h, rtol, refine, prof); break;
-    case 7: launch_direct_wc<8, 4>(h, rtol, refine, prof); break;
-    case 8: launch_direct_wc<64, 8>(h, rtol, refine, prof); break;
-    case 9: launch_direct_wc<64, 16>(h, rtol, refine, prof); break;
-    default: launch_direct_wc<64, 4>(h, rtol, refine, prof); break;
-  }
+  CHECK(with_lane<kLaneSweep>(h->sweep_lane, [&](auto w, auto cpl) {
+    launch_direct_wc<w(), cpl()>(h, rtol, refine, prof);
+    return NX_OK;
+  }));
   HIPCALL(hipGetLastError());
   return NX_OK;
 }
@@ -12254,8 +12300,7 @@ int xr_link(nx_network* h, const std::vector<XPeer>& peers) {
   h->sched_checked = false;  // (the ranks agree on the exchange in check_schedules)
   return NX_OK;
 }
-bool xr_variant(int v) { return v == 5 || v == 10 || v == 7 || v == 2; }  // <8,2|3|4>, <16,4>
-size_t xr_static_lds(int v);  // the exchange kernels' static LDS (below)
+size_t xr_static_lds(Lane s);  // the exchange kernels' static LDS (below)
 
 // one rank's share of the decision: its tables, its peers linked, the coarse / cut sizes
 // within the exchange's caps, one round of workgroups, the LDS
@@ -12265,8 +12310,8 @@ bool xr_local(const nx_network* h) {
          h->pc_jobs > 0 && h->pc_jobs <= h->n_cu && h->pa.n_coarse > 0 &&
          h->pa.n_coarse <= kCapCoarseLds && h->n_cut >= 0 && h->n_cut <= kCapCoarseLds &&
          h->top_nt > 0 && h->top_nt <= kTopThreads && h->pa.n_top_lvl <= kMaxTopLvl &&
-         xr_variant(h->dstep_variant) &&
-         h->dstep_lds + xr_static_lds(h->dstep_variant) <= 160 * 1024;
+         lane_in(h->step_lane, kLaneXr) &&
+         h->dstep_lds + xr_static_lds(h->step_lane) <= 160 * 1024;
 }
 bool xr_env() {
   const char* e = std::getenv("NXHIP_DIR_XR");  // read per solve: tests switch it
@@ -12279,7 +12324,7 @@ bool xr_on(const Team& t, bool with_asm) {
   if (t.g) {
     int jobs = 0;
     for (int r = 0; r < t.P; ++r) {
-      if (!xr_local(t.hs[r]) || t.hs[r]->dstep_variant != t.hs[0]->dstep_variant) return false;
+      if (!xr_local(t.hs[r]) || t.hs[r]->step_lane != t.hs[0]->step_lane) return false;
       jobs += t.hs[r]->pc_jobs;
     }
     return jobs <= t.hs[0]->n_cu;
@@ -12324,16 +12369,16 @@ DirStep dir_args(nx_network* h, double rtol) {
   return d;
 }
 // the exchange fields of rank h's launch among X ranks (its own mailbox, the peers' table)
-void xr_fill(nx_network* h, DirStep& da, int X) {
+void xr_fill(const nx_network* h, DirStep& da, int X, XPeer self, const XPeer* peers, unsigned tag) {
   da.n_left = h->xr_nleft;
-  da.xpeers = h->d_xpeers;
-  da.xself = xpeer_of(h->xmb, X);
+  da.xpeers = peers;
+  da.xself = self;
   da.xP = X;
   da.xrank = h->rank;
   da.xld1 = kXld1;
   da.xld2 = kXld2;
   da.xK = h->n_cut;
-  da.xtag = h->xtag;
+  da.xtag = tag;
   da.xpoll[0] = h->xpoll[0];
   da.xpoll[1] = h->xpoll[1];
 }
@@ -12359,7 +12404,7 @@ int launch_xr_wc(const Team& t, double rtol) {
     if (h->nranks != X) return fail(NX_ERR_STATE, "exchange step: rank count mismatch");
     h->xtag += 1;  // (the same on every rank: they launch together)
     DirStep da = dir_args(h, rtol);
-    xr_fill(h, da, X);
+    xr_fill(h, da, X, xpeer_of(h->xmb, X), h->d_xpeers, h->xtag);
     das[r] = da;
     goff[r + 1] = goff[r] + h->pc_jobs;
     lds = std::max(lds, h->dstep_lds);
@@ -12377,7 +12422,7 @@ int launch_xr_wc(const Team& t, double rtol) {
     std::memcpy(hb + bp + bd, goff.data(), bo);
     HIPCALL(hipMemcpyAsync(g->xg_dev, g->xg_host, bp + bd + bo, hipMemcpyHostToDevice, g->stream));
     const char* db = static_cast<const char*>(g->xg_dev);
-    const int cap = (int)(160 * 1024 - xr_static_lds(t.hs[0]->dstep_variant));
+    const int cap = (int)(160 * 1024 - xr_static_lds(t.hs[0]->step_lane));
     // one instantiation for every rank's workgroups: superposition only if every rank asks
     // for it (the SUP body ignores da.sup -- a rank with a several-pass job or without the
     // park must not run it); the plain body reads nothing that da.sup guards, and lds is
@@ -12401,7 +12446,7 @@ int launch_xr_wc(const Team& t, double rtol) {
     HIPCALL(hipStreamSynchronize(g->stream));  // (the pinned staging is rewritten next launch)
   } else {
     nx_network* h = t.hs[0];
-    const int cap = (int)(160 * 1024 - xr_static_lds(h->dstep_variant));
+    const int cap = (int)(160 * 1024 - xr_static_lds(h->step_lane));
     const bool prof = h->prof && h->dev[0];  // (events bound to the dispatch: bench.py)
     h->last_sup = sup_launch<CPL>(das[0]);
     if (sup_launch<CPL>(das[0])) {
@@ -12424,31 +12469,28 @@ int launch_xr_wc(const Team& t, double rtol) {
   return NX_OK;
 }
 int launch_xr(const Team& t, double rtol) {
-  switch (t.hs[0]->dstep_variant) {
-    case 5: return launch_xr_wc<8, 2>(t, rtol);
-    case 10: return launch_xr_wc<8, 3>(t, rtol);
-    case 7: return launch_xr_wc<8, 4>(t, rtol);
-    default: return launch_xr_wc<16, 4>(t, rtol);
-  }
+  return with_lane<kLaneXr>(t.hs[0]->step_lane,
+                            [&](auto w, auto cpl) { return launch_xr_wc<w(), cpl()>(t, rtol); });
 }
-size_t xr_static_lds(int v) {
-  static size_t s[4] = {0, 0, 0, 0};
-  const int i = v == 5 ? 0 : v == 7 ? 1 : v == 10 ? 3 : 2;
-  if (!s[i]) {
-    hipFuncAttributes a{};
-    const void* fn = i == 0 ? reinterpret_cast<const void*>(&k_dir_xr<8, 2>)
-                   : i == 1 ? reinterpret_cast<const void*>(&k_dir_xr<8, 4>)
-                   : i == 3 ? reinterpret_cast<const void*>(&k_dir_xr<8, 3>)
-                            : reinterpret_cast<const void*>(&k_dir_xr<16, 4>);
-    s[i] = hipFuncGetAttributes(&a, fn) == hipSuccess ? a.sharedSizeBytes : 64 * 1024;
-    if (i == 0) {  // (and the superposition's instantiation, the larger of the two)
-      hipFuncAttributes b{};
-      const size_t sb = hipFuncGetAttributes(&b, reinterpret_cast<const void*>(&k_dir_xr<8, 2, true>))
-                                == hipSuccess ? b.sharedSizeBytes : 64 * 1024;
-      s[i] = std::max(s[i], sb);
-    }
-  }
-  return s[i];
+// The exchange kernels' static LDS for shape s (with superposition's instantiation where one
+// is compiled, the larger of the two). A shape outside the exchange set never runs the
+// exchange (xr_local); the step's LDS budget of such a handle counts the <16, 4> kernel's.
+size_t xr_static_lds(Lane s) {
+  static size_t cache[kNumLanes] = {};
+  if (!lane_in(s, kLaneXr)) s = Lane::k16x4;
+  size_t& c = cache[(int)s];
+  if (!c)
+    (void)with_lane<kLaneXr>(s, [&](auto w, auto cpl) {
+      auto static_of = [](const void* fn) {
+        hipFuncAttributes a{};
+        return hipFuncGetAttributes(&a, fn) == hipSuccess ? a.sharedSizeBytes : (size_t)64 * 1024;
+      };
+      c = static_of(reinterpret_cast<const void*>(&k_dir_xr<w(), cpl()>));
+      if constexpr (cpl() <= 2)
+        c = std::max(c, static_of(reinterpret_cast<const void*>(&k_dir_xr<w(), cpl(), true>)));
+      return NX_OK;
+    });
+  return c;
 }
 
 // ---- after an exchange step: finished, or the ranks agree what to do ---------------------
@@ -12903,7 +12945,7 @@ void sched_sig(const nx_network* h, int* s) {
   s[1] = h->pc && h->pc_lds;
   s[2] = h->pc ? h->pa.lin : 0;
   s[3] = h->pc ? h->pa.fused : 0;
-  s[4] = h->pc ? h->pc_variant : 0;
+  s[4] = h->pc ? 1 + (int)h->sweep_lane : 0;  // (equal exactly when the sweep shapes are)
   s[5] = h->beta_p2p;
   // the dense top (nx_set_pc_dense, decided per rank from its kMaxNeed fit) drives mdense
   // and with it fuse_pack: who packs the halo and beta^2 -- a per-rank difference would
@@ -14232,18 +14274,10 @@ void batch_sweeps_wc(const SweepCtx& sc, const int* list, int nc, const double* 
 }
 int batch_sweeps(const SweepCtx& sc, const int* list, int nc, const double* in, double* out,
                  const BatchEns* ens = nullptr) {
-  switch (sc.d->pc_variant) {
-    case 0: batch_sweeps_wc<16, 1>(sc, list, nc, in, out, ens); break;
-    case 1: batch_sweeps_wc<16, 2>(sc, list, nc, in, out, ens); break;
-    case 2: batch_sweeps_wc<16, 4>(sc, list, nc, in, out, ens); break;
-    case 3: batch_sweeps_wc<64, 2>(sc, list, nc, in, out, ens); break;
-    case 5: batch_sweeps_wc<8, 2>(sc, list, nc, in, out, ens); break;
-    case 6: batch_sweeps_wc<4, 4>(sc, list, nc, in, out, ens); break;
-    case 7: batch_sweeps_wc<8, 4>(sc, list, nc, in, out, ens); break;
-    case 8: batch_sweeps_wc<64, 8>(sc, list, nc, in, out, ens); break;
-    case 9: batch_sweeps_wc<64, 16>(sc, list, nc, in, out, ens); break;
-    default: batch_sweeps_wc<64, 4>(sc, list, nc, in, out, ens); break;
-  }
+  CHECK(with_lane<kLaneSweep>(sc.d->sweep_lane, [&](auto w, auto cpl) {
+    batch_sweeps_wc<w(), cpl()>(sc, list, nc, in, out, ens);
+    return NX_OK;
+  }));
   HIPCALL(hipGetLastError());
   return NX_OK;
 }
@@ -16663,43 +16697,89 @@ NX_API int nx_bench_spmv_cold(nx_network_t* h, int32_t reps, int32_t* copies_out
 
 namespace {
 void free_cycles(nx_network* h);
-}  // namespace
 
-NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chains,
-                                 const int32_t* chain_edge, const int32_t* chain_flip,
-                                 const int32_t* chain_up, const int32_t* chain_lo, int64_t n_slots,
-                                 const int32_t* slot_lam, const int32_t* slot_pchain,
-                                 const int32_t* slot_parent, const int32_t* slot_dc_off,
-                                 const int32_t* slot_dc, const int32_t* dc_lo,
-                                 const int32_t* slot_plam, int32_t n_jobs,
-                                 const int32_t* job_chain_off, const int32_t* job_lvl_off,
-                                 int32_t n_lvl, const int32_t* lvl_slot_off, int32_t n_top_lvl,
-                                 const int32_t* top_lvl_off) {
-  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
-  if (!h) return fail(NX_ERR_ARG, "null handle");
-  h->sched_checked = false;
-  CHECK(set_device(h));
-  HIPCALL(hipStreamSynchronize(h->stream));
-  CHECK(drop_handle_graphs(h));  // captured launches depend on the preconditioner
-  free_cycles(h);  // (nx_set_cycles belongs to this decomposition: set again after it)
-  if (!enable) {
-    h->pc = false;
-    return NX_OK;
+// ---- nx_set_preconditioner's build ---------------------------------------------------------
+// The caller's decomposition, read only (the API's arrays and sizes under the API's names).
+struct PcView {
+  int N;
+  int64_t n_chains;
+  const int32_t *chain_edge, *chain_flip, *chain_up, *chain_lo;
+  int64_t n_slots;
+  const int32_t *slot_lam, *slot_pchain, *slot_parent, *slot_dc_off, *slot_dc, *dc_lo, *slot_plam;
+  int32_t n_jobs;
+  const int32_t *job_chain_off, *job_lvl_off;
+  int32_t n_lvl;
+  const int32_t* lvl_slot_off;
+  int32_t n_top_lvl;
+  const int32_t* top_lvl_off;
+};
+// One build: the view, what the stages fill (PcArgs, the flags the commit sets, the host
+// tables a later stage reads) and the stages in nx_set_preconditioner's order. The device
+// buffers go into the handle's pc_bufs (pc_release frees them); the handle's other fields of
+// the one-launch step are written as the stages go and mean nothing before the commit.
+struct PcBuild : PcView {
+  nx_network* h;
+  PcArgs pa{};
+  Lane sweep = Lane::k64x4, step = Lane::k64x4;
+  bool lds = false, fres_ok = false, dstep_ok = false, xr_ok = false;
+  std::vector<int> job_of_chain, job_of_slot;  // fres_tables -> post_tables
+  std::vector<int> left;                       // the rows no job's down sweep forms
+  std::vector<int> jw;                         // wave_setup -> step_headers (pa.job_wave's host copy)
+
+  PcBuild(const PcView& v, nx_network* hh) : PcView(v), h(hh) {}
+  bool failed = false;  // an allocation, copy or fill below failed (and returned null)
+  // device memory owned by this preconditioner (pc_bufs): a copy of src, zeros, or as it comes
+  void* dev(size_t bytes, const void* src = nullptr, bool zero = false) {
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) == hipSuccess) {
+      h->pc_bufs.push_back(d);
+      if ((!src || hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) == hipSuccess) &&
+          (!zero || hipMemset(d, 0, bytes) == hipSuccess))
+        return d;
+    }
+    failed = true;
+    return nullptr;
   }
-  if (h->fe)
-    return fail(NX_ERR_STATE, "the tree preconditioner needs the P1/DG0 layout (nx_create)");
-  const int N = h->N;
-  int variant;
-  if (N <= 16) variant = 5;  // 8 lanes x 2 cells: one chain round per job (swept: 16x1 +8%)
-  // (N <= 32 by 8 lanes x 4 cells, 128 chains per pass: slower, 8-rank C4 rehearsal r03o --
-  // team up 50 -> 57 us, down 41 -> 66 us per rank; the lanes' serial work dominates)
-  else if (N <= 32) variant = 1;
-  else if (N <= 64) variant = 2;
-  else if (N <= 128) variant = 3;
-  else if (N <= 256) variant = 4;
-  else if (N <= 512) variant = 8;
-  else if (N <= 1024) variant = 9;
-  else return fail(NX_ERR_ARG, "tree preconditioner supports N <= 1024 cells per edge");
+  const int* up(const int32_t* src, int64_t n) {  // n ints (>= 1)
+    return static_cast<int*>(dev(sizeof(int) * std::max<int64_t>(n, 1), src));
+  }
+  double* scratch(int64_t n) { return static_cast<double*>(dev(sizeof(double) * std::max<int64_t>(n, 1))); }
+  unsigned* zeroed(int n) { return static_cast<unsigned*>(dev(sizeof(unsigned) * n, nullptr, true)); }
+
+  int validate() const;
+  int upload_index();
+  void lds_fit();
+  int fres_tables();
+  void post_tables();
+  void wave_setup();
+  void top_setup();
+  void step_headers();
+  int commit();
+};
+
+// The handle without a preconditioner: its buffers freed, every pointer into them and every
+// flag that says they can be used cleared. nx_set_preconditioner starts a build from here and
+// comes back here when a stage fails.
+void pc_release(nx_network* h) {
+  for (void* p : h->pc_bufs) (void)hipFree(p);
+  h->pc_bufs.clear();
+  h->pc = h->pc_lds = h->fres_ok = h->dstep_ok = h->xr_ok = false;
+  h->pa = PcArgs{};
+  h->d_left = h->d_chain_post = h->d_left_off = h->d_job_hdr = h->d_ci = nullptr;
+  h->d_post = h->d_crec = h->dir_bb = nullptr;
+  h->d_dsync = h->d_tsync = nullptr;
+  h->n_left = h->xr_nleft = 0;
+  h->dstep_epoch = 0;
+  h->dstep_off = false;
+  h->dense_hdr = false;  // (nx_set_pc_dense writes the new headers' dense words)
+  h->g_version = -1;
+  h->geo_version = -1;  // (ensure_chain_geo: a new decomposition's chain order)
+  h->need_r = false;
+}
+
+// Stage 1: the arguments (nothing of the handle is touched: a refused call leaves the
+// previous preconditioner usable).
+int PcBuild::validate() const {
   if (n_chains != h->E) return fail(NX_ERR_ARG, "one chain per local edge expected");
   // one slot per owned multiplier, plus (several ranks) the ghost junctions at the ends of
   // local edges, which are coarse (nx_set_coarse)
@@ -16729,24 +16809,12 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
   if (n_slots > 0 && (int64_t)(n_lvl > 0 ? lvl_slot_off[n_lvl] : 0) +
                              (top_lvl_off[n_top_lvl] - top_lvl_off[0]) != n_slots)
     return fail(NX_ERR_ARG, "levels must cover all slots");
-  for (void* p : h->pc_bufs) (void)hipFree(p);
-  h->pc_bufs.clear();
-  auto up = [&](const int32_t* src, int64_t n) -> const int* {
-    int* d = nullptr;
-    if (n <= 0) n = 1;
-    if (hipMalloc((void**)&d, sizeof(int) * n) != hipSuccess) return nullptr;
-    h->pc_bufs.push_back(d);
-    if (src && hipMemcpy(d, src, sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return d;
-  };
-  auto scratch = [&](int64_t n) -> double* {
-    double* d = nullptr;
-    if (n <= 0) n = 1;
-    if (hipMalloc((void**)&d, sizeof(double) * n) != hipSuccess) return nullptr;
-    h->pc_bufs.push_back(d);
-    return d;
-  };
-  PcArgs pa{};
+  return NX_OK;
+}
+
+// Stage 2: the index arrays and the sweeps' scratch on the device, the Krylov vectors the
+// preconditioned solve needs.
+int PcBuild::upload_index() {
   pa.N = N;
   pa.invN = 1.0 / (double)N;
   pa.chain_edge = up(chain_edge, n_chains);
@@ -16792,25 +16860,12 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
   pa.slot_invD = scratch(n_slots);
   {  // consistent-mass flux block: pivots of T = tridiag(1, 4, 1), 2 at both ends
     const std::vector<double> ti = mass_lu(N);
-    double* d = scratch((int64_t)ti.size());
-    if (d == nullptr || hipMemcpy(d, ti.data(), sizeof(double) * ti.size(), hipMemcpyHostToDevice) !=
-                            hipSuccess)
-      return fail(NX_ERR_HIP, "preconditioner upload failed");
-    pa.Tlu = d;
+    pa.Tlu = static_cast<double*>(dev(sizeof(double) * ti.size(), ti.data()));
     pa.mo_div = 3.0;  // P1 (nx_set_cell_mass: a condensed (k, 0) system)
     h->cond_mass = false;
     pa.exact = 1;  // (nx_set_pc_exact(h, 0): lumped D, P = blockdiag(D, G^T D^{-1} G))
   }
-  for (const void* p : {(const void*)pa.chain_edge, (const void*)pa.chain_flip, (const void*)pa.chain_up,
-                        (const void*)pa.chain_lo, (const void*)pa.slot_lam, (const void*)pa.slot_pchain,
-                        (const void*)pa.slot_parent, (const void*)pa.slot_dc_off, (const void*)pa.slot_dc,
-                        (const void*)pa.job_chain_off, (const void*)pa.job_lvl_off,
-                        (const void*)pa.lvl_slot_off, (const void*)pa.top_lvl_off,
-                        (const void*)pa.chain_T, (const void*)pa.chain_It, (const void*)pa.chain_Ib,
-                        (const void*)pa.slot_D, (const void*)pa.slot_J, (const void*)pa.dc_lo,
-                        (const void*)pa.slot_plam, (const void*)pa.slot_A, (const void*)pa.slot_B,
-                        (const void*)pa.slot_z})
-    if (p == nullptr) return fail(NX_ERR_HIP, "preconditioner upload failed");
+  if (failed) return fail(NX_ERR_HIP, "preconditioner upload failed");  // (any of the above)
   if (!h->z) CHECK(dalloc(&h->z, std::max<int64_t>(h->n_col, 1)));
   if (!h->vv) CHECK(dalloc(&h->vv, std::max<int64_t>(h->n_own, 1)));
   {  // stored Lanczos vectors
@@ -16826,8 +16881,12 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
     h->nB = n_jobs + 1;
     CHECK(dalloc(&h->partB, h->nB));
   }
-  // LDS kernels when every job (and the top part) fits their caps
-  bool lds = (top_lvl_off[n_top_lvl] - top_lvl_off[0]) <= kCapT && n_top_lvl <= kMaxTopLvl;
+  return NX_OK;
+}
+
+// Stage 3: LDS kernels when every job (and the top part) fits their caps
+void PcBuild::lds_fit() {
+  lds = (top_lvl_off[n_top_lvl] - top_lvl_off[0]) <= kCapT && n_top_lvl <= kMaxTopLvl;
   if (lds && n_top_lvl > 0 && top_lvl_off[n_top_lvl] > top_lvl_off[0])
     lds = slot_dc_off[top_lvl_off[n_top_lvl]] - slot_dc_off[top_lvl_off[0]] <= kCapTDC;
   for (int j = 0; lds && j < n_jobs; ++j) {
@@ -16839,173 +16898,159 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
   }
   if (const char* e = std::getenv("NXHIP_PC_GLOBAL")) lds = lds && std::atoi(e) == 0;
   lds = lds && !h->force_global;  // the ranks chose together (nx_set_pc_kernels)
-  // fused residual of the direct solve (one rank, LDS kernels): a junction's multiplier row
-  // is formed by its job's down sweep when its chains -- the parent chain (lo = j) and the
-  // hanging ones (up = j) -- are exactly slot_pchain / slot_dc and all in that job; every
-  // other multiplier row goes to k_dir_publish_fr (the top part's)
+}
+
+// Stage 4 (rloc, left): the
+// fused residual of the direct solve (one rank, LDS kernels): a junction's multiplier row
+// is formed by its job's down sweep when its chains -- the parent chain (lo = j) and the
+// hanging ones (up = j) -- are exactly slot_pchain / slot_dc and all in that job; every
+// other multiplier row goes to k_dir_publish_fr (the top part's)
+int PcBuild::fres_tables() {
   pa.fres = 0;
   pa.edge_x = h->edge_x;
   pa.edge_R = h->edge_R;
-  h->fres_ok = false;
-  h->d_left = nullptr;
-  h->n_left = 0;
-  h->dstep_ok = false;  // (the fused step's buffers were in the freed pc_bufs)
-  h->d_chain_post = h->d_left_off = nullptr;
-  h->d_post = nullptr;
-  h->d_dsync = nullptr;
-  h->d_tsync = nullptr;
-  h->dstep_epoch = 0;
-  h->dstep_off = false;
-  h->dense_hdr = false;  // (nx_set_pc_dense writes the new headers' dense words)
-  h->g_version = -1;
-  h->need_r = false;
-  if (lds && n_jobs > 0) {  // one rank or several (then only owned rows of lower jobs)
-    std::vector<int> job_of_chain(n_chains, -1), job_of_slot(n_slots, -1);
-    for (int jb = 0; jb < n_jobs; ++jb) {
-      for (int c = job_chain_off[jb]; c < job_chain_off[jb + 1]; ++c) job_of_chain[c] = jb;
-      for (int lv = job_lvl_off[jb]; lv < job_lvl_off[jb + 1]; ++lv)
-        for (int j = lvl_slot_off[lv]; j < lvl_slot_off[lv + 1]; ++j) job_of_slot[j] = jb;
+  if (!(lds && n_jobs > 0)) return NX_OK;  // one rank or several (then only owned rows of lower jobs)
+  job_of_chain.assign(n_chains, -1);
+  job_of_slot.assign(n_slots, -1);
+  for (int jb = 0; jb < n_jobs; ++jb) {
+    for (int c = job_chain_off[jb]; c < job_chain_off[jb + 1]; ++c) job_of_chain[c] = jb;
+    for (int lv = job_lvl_off[jb]; lv < job_lvl_off[jb + 1]; ++lv)
+      for (int j = lvl_slot_off[lv]; j < lvl_slot_off[lv + 1]; ++j) job_of_slot[j] = jb;
+  }
+  std::vector<int> n_lo(n_slots, 0), n_up(n_slots, 0);
+  std::vector<char> far(n_slots, 0);  // a chain at this junction lies in another job
+  for (int64_t c = 0; c < n_chains; ++c) {
+    for (int end = 0; end < 2; ++end) {
+      const int j = end ? chain_lo[c] : chain_up[c];
+      if (j < 0) continue;
+      (end ? n_lo : n_up)[j] += 1;
+      if (job_of_chain[c] != job_of_slot[j]) far[j] = 1;
     }
-    std::vector<int> n_lo(n_slots, 0), n_up(n_slots, 0);
-    std::vector<char> far(n_slots, 0);  // a chain at this junction lies in another job
-    for (int64_t c = 0; c < n_chains; ++c) {
+  }
+  std::vector<int> rloc(n_slots, 0);
+  std::vector<char> done_row(h->n_own - h->n_edge_dofs, 0);
+  for (int64_t j = 0; j < n_slots; ++j) {
+    const int pcn = slot_pchain[j];
+    const bool ok = job_of_slot[j] >= 0 && !far[j] && slot_lam[j] < h->n_own &&
+                    n_lo[j] == (pcn >= 0 ? 1 : 0) && (pcn < 0 || chain_lo[pcn] == j) &&
+                    n_up[j] == slot_dc_off[j + 1] - slot_dc_off[j];
+    rloc[j] = ok ? 1 : 0;
+    if (ok) done_row[slot_lam[j] - h->n_edge_dofs] = 1;  // owned: slot_lam < n_own
+  }
+  for (int64_t i = 0; i < (int64_t)done_row.size(); ++i)
+    if (!done_row[i]) left.push_back((int)(h->n_edge_dofs + i));
+  pa.slot_rloc = up(rloc.data(), n_slots);
+  h->d_left = const_cast<int*>(up(left.empty() ? nullptr : left.data(), (int64_t)left.size()));
+  pa.rpart = scratch(2 * (int64_t)n_jobs);
+  h->dir_bb = scratch(1);
+  pa.rres = h->tmp;
+  pa.rhs_b = h->rhs;
+  h->n_left = (int)left.size();
+  fres_ok = pa.slot_rloc && h->d_left && pa.rpart && h->dir_bb && h->tmp;
+  h->d_tsync = zeroed(1);  // k_dir_team_up's arrival counter (its last workgroup resets it)
+  if (const char* e = std::getenv("NXHIP_DIR_FRES")) fres_ok = fres_ok && std::atoi(e) != 0;
+  h->left_host = left;
+  if (h->n_cut >= 0) {
+    const int rc = build_left_cut(h);
+    if (rc != NX_OK) return rc;
+  }
+  return NX_OK;
+}
+
+// Stage 5 (cpost, off, row_of, cut_of_row): the post tables of
+// the fused direct step (one rank, or a rank of several with its cut rows set): every
+// slot a job reads outside itself -- its root's parent, its chains' far ends -- is a top
+// slot (the down sweep takes it from the top values), and the rows no job forms get
+// their flux-end shares posted (chain order per row): the left rows and, with several
+// ranks, every cut bifurcation's row (owned or not: the K entries after the left rows,
+// which the publisher exchanges) instead of the cut rows among the left ones
+void PcBuild::post_tables() {
+  if (!(lds && n_jobs > 0)) return;
+  const bool xr_tables = h->nranks > 1 && h->n_cut >= 0;
+  if (fres_ok && (h->nranks == 1 ? h->n_ghost == 0 : xr_tables)) {
+    const int ts0 = top_lvl_off[0], ts1 = top_lvl_off[n_top_lvl];
+    auto top = [&](int j) { return j >= ts0 && j < ts1; };
+    bool ok = true;
+    for (int64_t c = 0; c < n_chains && ok; ++c)
       for (int end = 0; end < 2; ++end) {
         const int j = end ? chain_lo[c] : chain_up[c];
-        if (j < 0) continue;
-        (end ? n_lo : n_up)[j] += 1;
-        if (job_of_chain[c] != job_of_slot[j]) far[j] = 1;
+        if (j >= 0 && job_of_slot[j] != job_of_chain[c] && !top(j)) ok = false;
       }
+    for (int64_t j = 0; j < n_slots && ok; ++j) {
+      const int p = slot_parent[j];
+      if (job_of_slot[j] >= 0 && p >= 0 && job_of_slot[p] != job_of_slot[j] && !top(p)) ok = false;
     }
-    std::vector<int> rloc(n_slots, 0);
-    std::vector<char> done_row(h->n_own - h->n_edge_dofs, 0);
-    for (int64_t j = 0; j < n_slots; ++j) {
-      const int pcn = slot_pchain[j];
-      const bool ok = job_of_slot[j] >= 0 && !far[j] && slot_lam[j] < h->n_own &&
-                      n_lo[j] == (pcn >= 0 ? 1 : 0) && (pcn < 0 || chain_lo[pcn] == j) &&
-                      n_up[j] == slot_dc_off[j + 1] - slot_dc_off[j];
-      rloc[j] = ok ? 1 : 0;
-      if (ok) done_row[slot_lam[j] - h->n_edge_dofs] = 1;  // owned: slot_lam < n_own
+    const int K = xr_tables ? h->n_cut : 0;
+    std::vector<int> dleft;  // the fused publisher's own rows: left rows that are not cut
+    for (int r : left)
+      if (!(xr_tables && h->lm_cut[r - h->n_edge_dofs] >= 0)) dleft.push_back(r);
+    const int nl = (int)dleft.size();
+    std::vector<int> row_of(h->n_own - h->n_edge_dofs, -1);
+    for (int i = 0; i < nl; ++i) row_of[dleft[i] - h->n_edge_dofs] = i;
+    if (xr_tables)  // owned cut rows: entry nl + k
+      for (int64_t m = 0; m < (int64_t)row_of.size(); ++m)
+        if (h->lm_cut[m] >= 0) row_of[m] = nl + h->lm_cut[m];
+    std::vector<int> cut_of_row;  // a ghost junction's cut index by this rank's flux-end row
+    if (xr_tables) {
+      cut_of_row.assign(h->n_edge_dofs, -1);
+      for (int k = 0; k < K; ++k)
+        for (int e = h->gk_off_host[k]; e < h->gk_off_host[k + 1]; ++e)
+          cut_of_row[h->gk_row_host[e]] = nl + k;
     }
-    std::vector<int> left;
-    for (int64_t i = 0; i < (int64_t)done_row.size(); ++i)
-      if (!done_row[i]) left.push_back((int)(h->n_edge_dofs + i));
-    pa.slot_rloc = up(rloc.data(), n_slots);
-    h->d_left = const_cast<int*>(up(left.empty() ? nullptr : left.data(), (int64_t)left.size()));
-    pa.rpart = scratch(2 * (int64_t)n_jobs);
-    h->dir_bb = scratch(1);
-    pa.rres = h->tmp;
-    pa.rhs_b = h->rhs;
-    h->n_left = (int)left.size();
-    h->fres_ok = pa.slot_rloc && h->d_left && pa.rpart && h->dir_bb && h->tmp;
-    {  // k_dir_team_up's arrival counter (zero; its last workgroup resets it)
-      unsigned* ty = nullptr;
-      if (hipMalloc((void**)&ty, sizeof(unsigned)) == hipSuccess) {
-        h->pc_bufs.push_back(ty);
-        if (hipMemset(ty, 0, sizeof(unsigned)) != hipSuccess) ty = nullptr;
+    const int N2 = 2 * N + 1;
+    // the post group of chain c's end (0 top, 1 bottom) at slot j, or -1
+    auto row_at = [&](int64_t c, int end, int j) {
+      if (j < 0) return -1;
+      const int lam = slot_lam[j];
+      if (lam < h->n_own) return row_of[lam - h->n_edge_dofs];
+      if (!xr_tables) return -1;
+      const int e = chain_edge[c], fl = chain_flip[c];  // the chain's end flux row
+      const bool q0 = (end == 0) != (fl != 0);
+      return cut_of_row[(int64_t)e * N2 + (q0 ? 0 : 2 * N)];
+    };
+    std::vector<int> off(nl + K + 1, 0), fill(nl + K, 0);
+    std::vector<int> cpost(2 * std::max<int64_t>(n_chains, 1), -1);
+    for (int64_t c = 0; c < n_chains; ++c)
+      for (int end = 0; end < 2; ++end) {
+        const int r = row_at(c, end, end ? chain_lo[c] : chain_up[c]);
+        if (r >= 0) off[r + 1] += 1;
       }
-      h->d_tsync = ty;
-    }
-    if (const char* e = std::getenv("NXHIP_DIR_FRES")) h->fres_ok = h->fres_ok && std::atoi(e) != 0;
-    h->left_host = left;
-    if (h->n_cut >= 0) {
-      const int rc = build_left_cut(h);
-      if (rc != NX_OK) return rc;
-    }
-    // the fused direct step (one rank, or a rank of several with its cut rows set): every
-    // slot a job reads outside itself -- its root's parent, its chains' far ends -- is a top
-    // slot (the down sweep takes it from the top values), and the rows no job forms get
-    // their flux-end shares posted (chain order per row): the left rows and, with several
-    // ranks, every cut bifurcation's row (owned or not: the K entries after the left rows,
-    // which the publisher exchanges) instead of the cut rows among the left ones
-    const bool xr_tables = h->nranks > 1 && h->n_cut >= 0;
-    h->xr_ok = false;
-    h->xr_nleft = 0;
-    if (h->fres_ok && (h->nranks == 1 ? h->n_ghost == 0 : xr_tables)) {
-      const int ts0 = top_lvl_off[0], ts1 = top_lvl_off[n_top_lvl];
-      auto top = [&](int j) { return j >= ts0 && j < ts1; };
-      bool ok = true;
+    for (int i = 0; i < nl + K; ++i) off[i + 1] += off[i];
+    for (int64_t c = 0; c < n_chains; ++c)
+      for (int end = 0; end < 2; ++end) {
+        const int r = row_at(c, end, end ? chain_lo[c] : chain_up[c]);
+        if (r >= 0) cpost[2 * c + end] = off[r] + fill[r]++;
+      }
+    if (xr_tables) {  // every ghost junction end must have found its cut row
       for (int64_t c = 0; c < n_chains && ok; ++c)
         for (int end = 0; end < 2; ++end) {
           const int j = end ? chain_lo[c] : chain_up[c];
-          if (j >= 0 && job_of_slot[j] != job_of_chain[c] && !top(j)) ok = false;
+          if (j >= 0 && slot_lam[j] >= h->n_own && cpost[2 * c + end] < 0) ok = false;
         }
-      for (int64_t j = 0; j < n_slots && ok; ++j) {
-        const int p = slot_parent[j];
-        if (job_of_slot[j] >= 0 && p >= 0 && job_of_slot[p] != job_of_slot[j] && !top(p)) ok = false;
-      }
-      const int K = xr_tables ? h->n_cut : 0;
-      std::vector<int> dleft;  // the fused publisher's own rows: left rows that are not cut
-      for (int r : left)
-        if (!(xr_tables && h->lm_cut[r - h->n_edge_dofs] >= 0)) dleft.push_back(r);
-      const int nl = (int)dleft.size();
-      std::vector<int> row_of(h->n_own - h->n_edge_dofs, -1);
-      for (int i = 0; i < nl; ++i) row_of[dleft[i] - h->n_edge_dofs] = i;
-      if (xr_tables)  // owned cut rows: entry nl + k
-        for (int64_t m = 0; m < (int64_t)row_of.size(); ++m)
-          if (h->lm_cut[m] >= 0) row_of[m] = nl + h->lm_cut[m];
-      std::vector<int> cut_of_row;  // a ghost junction's cut index by this rank's flux-end row
-      if (xr_tables) {
-        cut_of_row.assign(h->n_edge_dofs, -1);
-        for (int k = 0; k < K; ++k)
-          for (int e = h->gk_off_host[k]; e < h->gk_off_host[k + 1]; ++e)
-            cut_of_row[h->gk_row_host[e]] = nl + k;
-      }
-      const int N2 = 2 * N + 1;
-      // the post group of chain c's end (0 top, 1 bottom) at slot j, or -1
-      auto row_at = [&](int64_t c, int end, int j) {
-        if (j < 0) return -1;
-        const int lam = slot_lam[j];
-        if (lam < h->n_own) return row_of[lam - h->n_edge_dofs];
-        if (!xr_tables) return -1;
-        const int e = chain_edge[c], fl = chain_flip[c];  // the chain's end flux row
-        const bool q0 = (end == 0) != (fl != 0);
-        return cut_of_row[(int64_t)e * N2 + (q0 ? 0 : 2 * N)];
-      };
-      std::vector<int> off(nl + K + 1, 0), fill(nl + K, 0);
-      std::vector<int> cpost(2 * std::max<int64_t>(n_chains, 1), -1);
-      for (int64_t c = 0; c < n_chains; ++c)
-        for (int end = 0; end < 2; ++end) {
-          const int r = row_at(c, end, end ? chain_lo[c] : chain_up[c]);
-          if (r >= 0) off[r + 1] += 1;
-        }
-      for (int i = 0; i < nl + K; ++i) off[i + 1] += off[i];
-      for (int64_t c = 0; c < n_chains; ++c)
-        for (int end = 0; end < 2; ++end) {
-          const int r = row_at(c, end, end ? chain_lo[c] : chain_up[c]);
-          if (r >= 0) cpost[2 * c + end] = off[r] + fill[r]++;
-        }
-      if (xr_tables) {  // every ghost junction end must have found its cut row
-        for (int64_t c = 0; c < n_chains && ok; ++c)
-          for (int end = 0; end < 2; ++end) {
-            const int j = end ? chain_lo[c] : chain_up[c];
-            if (j >= 0 && slot_lam[j] >= h->n_own && cpost[2 * c + end] < 0) ok = false;
-          }
-        h->xr_nleft = nl;
-      }
-      h->d_chain_post = const_cast<int*>(up(cpost.data(), (int64_t)cpost.size()));
-      h->d_left_off = const_cast<int*>(up(off.data(), (int64_t)off.size()));
-      h->d_post = scratch(std::max(1, off.back()));
-      unsigned* sy = nullptr;
-      if (hipMalloc((void**)&sy, 8 * sizeof(unsigned)) == hipSuccess) {
-        h->pc_bufs.push_back(sy);
-        if (hipMemset(sy, 0, 8 * sizeof(unsigned)) != hipSuccess) sy = nullptr;
-      }
-      h->d_dsync = sy;
-      const bool tables = ok && h->d_chain_post && h->d_left_off && h->d_post && h->d_dsync;
-      if (xr_tables)
-        h->xr_ok = tables;  // (the exchange itself is checked per solve: xr_on)
-      else
-        h->dstep_ok = tables;
+      h->xr_nleft = nl;
     }
+    h->d_chain_post = const_cast<int*>(up(cpost.data(), (int64_t)cpost.size()));
+    h->d_left_off = const_cast<int*>(up(off.data(), (int64_t)off.size()));
+    h->d_post = scratch(std::max(1, off.back()));
+    h->d_dsync = zeroed(8);
+    const bool tables = ok && h->d_chain_post && h->d_left_off && h->d_post && h->d_dsync;
+    if (xr_tables)
+      xr_ok = tables;  // (the exchange itself is checked per solve: xr_on)
+    else
+      dstep_ok = tables;
   }
-  pa.top_reg = 1;
-  // the up sweep's one-wave level set-up (k_pc_up_lds): per eligible job (<= 64 slots, <=
-  // kCapLvl levels, <= kWaveKids junction children per slot) each slot's level, children
-  // (local slot) and their hanging-chain entries (offset from the job's first), packed
+}
+
+// Stage 6 (job_wave / slot_wave):
+// the up sweep's one-wave level set-up (k_pc_up_lds): per eligible job (<= 64 slots, <=
+// kCapLvl levels, <= kWaveKids junction children per slot) each slot's level, children
+// (local slot) and their hanging-chain entries (offset from the job's first), packed
+void PcBuild::wave_setup() {
   pa.job_wave = nullptr;
   pa.slot_wave = nullptr;
   if (lds && n_jobs > 0) {
-    std::vector<int> jw(n_jobs, 0), sw(3 * std::max<int64_t>(1, n_slots), 0);
+    jw.assign(n_jobs, 0);
+    std::vector<int> sw(3 * std::max<int64_t>(1, n_slots), 0);
     int n_wave = 0;
     for (int jb = 0; jb < n_jobs; ++jb) {
       const int lv0 = job_lvl_off[jb], lv1 = job_lvl_off[jb + 1];
@@ -17042,8 +17087,13 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
       pa.slot_wave = up(sw.data(), (int64_t)sw.size());
     }
   }
-  // the top part's register set-up (top_body): every slot's level, junction children (top
-  // position) and their hanging-chain entries, when all have <= kWaveKids and fit
+}
+
+// Stage 7 (top_wave; top_sub, top_lane, top_sub_dep below):
+// the top part's register set-up (top_body): every slot's level, junction children (top
+// position) and their hanging-chain entries, when all have <= kWaveKids and fit
+void PcBuild::top_setup() {
+  pa.top_reg = 1;
   pa.top_wave = nullptr;
   pa.top_sub = pa.top_lane = pa.top_sub_dep = nullptr;
   pa.top_sub_nup = 0;
@@ -17150,12 +17200,11 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
       }
     }
   }
-  // k_dir_step's job headers, stash strides, dynamic LDS and chain records (round 4)
-  h->d_job_hdr = nullptr;
-  h->d_crec = nullptr;
-  h->d_ci = nullptr;
-  h->geo_version = -1;  // (ensure_chain_geo: a new decomposition's chain order)
-  if (h->dstep_ok || h->xr_ok) {
+}
+
+// Stage 8: k_dir_step's job headers, stash strides, dynamic LDS and chain records (round 4)
+void PcBuild::step_headers() {
+  if (dstep_ok || xr_ok) {
     std::vector<int> hdr((size_t)kJobHdr * n_jobs, 0);
     int mlv = 1, mns = 0, mnd = 0, mch = 0;
     for (int jb = 0; jb < n_jobs; ++jb) {
@@ -17177,12 +17226,9 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
       mnd = std::max(mnd, r[7] - r[6]);
       mch = std::max(mch, r[1] - r[0]);
     }
-    if (pa.job_wave) {  // (the one-wave set-up of the up sweep, when the job has it)
-      std::vector<int> jw(n_jobs, 0);
-      HIPCALL(hipMemcpy(jw.data(), pa.job_wave, sizeof(int) * n_jobs, hipMemcpyDeviceToHost));
+    if (pa.job_wave)  // (the one-wave set-up of the up sweep, when the job has it)
       for (int jb = 0; jb < n_jobs; ++jb) hdr[(size_t)kJobHdr * jb + 8] = jw[jb];
-    }
-    const int W = variant_w(N <= 16 ? 5 : N <= 24 ? 10 : N <= 32 ? 7 : variant);  // (dstep's)
+    const int W = lane_info(step).w, CPL = lane_info(step).cpl;  // (the step's)
     h->dstep_multi = mch > kPcThreads / W;
     const int nt = h->top_nt, cdc = std::max(1, pa.top_ndc), ct = nt + 1;
     const int top_ints = 3 * ct + 1 + cdc + n_top_lvl + 1;
@@ -17194,16 +17240,15 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
     h->dstep_lds = 8 * (size_t)(kStashDbl + h->dstep_main + h->dstep_top + kDirLdsSupSlots);
     {  // phase 2 by superposition: its park (2 CPL + 1 doubles per thread), when it fits (with
        // the exchange kernels' static LDS on several ranks)
-      const int dv = N <= 16 ? 5 : N <= 24 ? 10 : N <= 32 ? 7 : variant;
-      const size_t park = 8 * (size_t)(2 * variant_cpl(dv) + 1) * kPcThreads;
+      const size_t park = 8 * (size_t)(2 * CPL + 1) * kPcThreads;
       // (several ranks: the exchange kernels' static LDS comes on top; the rank count is set
       // before the preconditioner -- nx_set_halo refuses to run after it)
-      const size_t cap = h->nranks > 1 ? std::min((size_t)kDirLdsMax, 160 * 1024 - xr_static_lds(dv))
+      const size_t cap = h->nranks > 1 ? std::min((size_t)kDirLdsMax, 160 * 1024 - xr_static_lds(step))
                                        : (size_t)kDirLdsMax;
       h->dstep_park = h->dstep_lds + park <= cap;
       if (h->dstep_park) h->dstep_lds += park;
-      const size_t recs = 8 * ((size_t)kRecLds * (kPcThreads / variant_w(dv)) +
-                               2 * (size_t)variant_cpl(dv) * kPcThreads);
+      const size_t recs = 8 * ((size_t)kRecLds * (kPcThreads / W) +
+                               2 * (size_t)CPL * kPcThreads);
       h->dstep_rec = h->dstep_park && h->dstep_lds + recs <= cap;
       if (h->dstep_rec) h->dstep_lds += recs;
     }
@@ -17212,23 +17257,81 @@ NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chai
     h->d_crec = scratch(10 * std::max<int64_t>(n_chains, 1));
     h->d_ci = const_cast<int*>(up(nullptr, 4 * std::max<int64_t>(n_chains, 1)));
     const bool hdr_ok = h->d_job_hdr && h->d_crec && h->d_ci && fits;
-    // (N > 256, variants <64, 8> / <64, 16>: the lane state spills thousands of VGPRs -- the
-    // separate launches run those; no fused instantiation)
-    h->dstep_ok = h->dstep_ok && hdr_ok && h->dstep_lds <= (size_t)kDirLdsMax &&
-                  (N <= 32 || (variant != 8 && variant != 9));
+    // (a shape without a step instantiation -- N > 256, kLanes -- keeps the separate launches)
+    dstep_ok = dstep_ok && hdr_ok && h->dstep_lds <= (size_t)kDirLdsMax &&
+                  lane_in(step, kLaneStep);
     // (several ranks: the coarse exchange's static LDS comes on top; checked at launch)
-    h->xr_ok = h->xr_ok && hdr_ok;
+    xr_ok = xr_ok && hdr_ok;
   }
+}
+
+// The commit: only now does the handle say it has a preconditioner.
+int PcBuild::commit() {
   h->pc_lds = lds;
   h->pa = pa;
   h->pc_jobs = n_jobs;
-  h->pc_variant = variant;
-  h->dstep_variant = N <= 16 ? 5 : N <= 24 ? 10 : N <= 32 ? 7 : variant;
+  h->sweep_lane = sweep;
+  h->step_lane = step;
   if (h->d_crec) CHECK(chain_rec_refresh(h));
   h->pc_slots = n_slots;
   h->pc_ndc = n_slots > 0 ? slot_dc_off[n_slots] : 0;
+  h->fres_ok = fres_ok;
+  h->dstep_ok = dstep_ok;
+  h->xr_ok = xr_ok;
   h->pc = true;
   return NX_OK;
+}
+}  // namespace
+
+NX_API int nx_set_preconditioner(nx_network_t* h, int32_t enable, int64_t n_chains,
+                                 const int32_t* chain_edge, const int32_t* chain_flip,
+                                 const int32_t* chain_up, const int32_t* chain_lo, int64_t n_slots,
+                                 const int32_t* slot_lam, const int32_t* slot_pchain,
+                                 const int32_t* slot_parent, const int32_t* slot_dc_off,
+                                 const int32_t* slot_dc, const int32_t* dc_lo,
+                                 const int32_t* slot_plam, int32_t n_jobs,
+                                 const int32_t* job_chain_off, const int32_t* job_lvl_off,
+                                 int32_t n_lvl, const int32_t* lvl_slot_off, int32_t n_top_lvl,
+                                 const int32_t* top_lvl_off) {
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  h->sched_checked = false;
+  CHECK(set_device(h));
+  HIPCALL(hipStreamSynchronize(h->stream));
+  CHECK(drop_handle_graphs(h));  // captured launches depend on the preconditioner
+  free_cycles(h);  // (nx_set_cycles belongs to this decomposition: set again after it)
+  if (!enable) {
+    h->pc = false;
+    return NX_OK;
+  }
+  if (h->fe)
+    return fail(NX_ERR_STATE, "the tree preconditioner needs the P1/DG0 layout (nx_create)");
+  const int N = h->N;
+  if (N > kMaxCellsPerEdge)
+    return fail(NX_ERR_ARG, "tree preconditioner supports N <= 1024 cells per edge");
+  PcBuild b(PcView{N, n_chains, chain_edge, chain_flip, chain_up, chain_lo, n_slots, slot_lam,
+                   slot_pchain, slot_parent, slot_dc_off, slot_dc, dc_lo, slot_plam, n_jobs,
+                   job_chain_off, job_lvl_off, n_lvl, lvl_slot_off, n_top_lvl, top_lvl_off},
+            h);
+  b.sweep = sweep_lane_of(N);
+  b.step = step_lane_of(N, b.sweep);
+  CHECK(b.validate());
+  // from here to the commit the handle has no preconditioner: a stage that fails leaves it so
+  pc_release(h);
+  int rc = b.upload_index();
+  if (rc == NX_OK) {
+    b.lds_fit();
+    rc = b.fres_tables();
+  }
+  if (rc == NX_OK) {
+    b.post_tables();
+    b.wave_setup();
+    b.top_setup();
+    b.step_headers();
+    rc = b.commit();
+  }
+  if (rc != NX_OK) pc_release(h);
+  return rc;
 }
 
 NX_API int nx_set_pc_dense(nx_network_t* h, int32_t enable, int32_t n_jobs,
@@ -18009,6 +18112,18 @@ NX_API int nx_get_pc_kernels(nx_network_t* h, int32_t* lds) {
   return NX_OK;
 }
 
+NX_API int nx_get_lane_shapes(nx_network_t* h, int32_t* sweep_w, int32_t* sweep_cpl,
+                              int32_t* step_w, int32_t* step_cpl) {
+  if (!h || !sweep_w || !sweep_cpl || !step_w || !step_cpl) return fail(NX_ERR_ARG, "null argument");
+  if (!h->pc) return fail(NX_ERR_STATE, "nx_set_preconditioner(enable=1) must come first");
+  const bool step = lane_in(h->step_lane, kLaneStep);
+  *sweep_w = lane_info(h->sweep_lane).w;
+  *sweep_cpl = lane_info(h->sweep_lane).cpl;
+  *step_w = step ? lane_info(h->step_lane).w : 0;
+  *step_cpl = step ? lane_info(h->step_lane).cpl : 0;
+  return NX_OK;
+}
+
 NX_API int nx_get_pc_exact(nx_network_t* h, int32_t* enabled) {
   if (!h || !enabled) return fail(NX_ERR_ARG, "null argument");
   *enabled = h->pc ? h->pa.exact : 0;
@@ -18373,21 +18488,11 @@ int xr_rehearse_wc(nx_network* h, int P, double rtol, int reps, float* ms_out) {
   HIPCALL(hipEventCreate(&e1));
   for (const void* fn : {reinterpret_cast<const void*>(&k_dir_xr<W, CPL>),
                          reinterpret_cast<const void*>(&k_dir_xr<W, CPL, CPL <= 2>)})
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(160 * 1024 - xr_static_lds(h->dstep_variant)));
-  (void)hipGetLastError();
+    opt_in_lds(fn, (int)(160 * 1024 - xr_static_lds(h->step_lane)));
   float total = 0.f;
   for (int k = 0; k <= reps && rc == NX_OK; ++k) {  // (launch 0: warm-up, not timed)
     DirStep da = dir_args(h, rtol);
-    da.n_left = h->xr_nleft;
-    da.xpeers = dpeers;
-    da.xself = xpeer_of(rd, P);
-    da.xP = P;
-    da.xrank = h->rank;
-    da.xld1 = kXld1;
-    da.xld2 = kXld2;
-    da.xK = h->n_cut;
-    da.xtag = tag;
+    xr_fill(h, da, P, xpeer_of(rd, P), dpeers, tag);
     if (sup_launch<CPL>(da))
       hipExtLaunchKernelGGL((k_dir_xr<W, CPL, CPL <= 2>), dim3(h->pc_jobs), dim3(kPcThreads),
                             h->dstep_lds, h->stream, e0, e1, 0, h->pa, da);
@@ -18419,18 +18524,14 @@ int xr_rehearse_wc(nx_network* h, int P, double rtol, int reps, float* ms_out) {
 NX_API int nx_debug_xr_rehearse(nx_network_t* h, double rtol, int32_t reps, double* ms) {
   if (!h || !ms) return fail(NX_ERR_ARG, "null argument");
   if (!h->group) return fail(NX_ERR_STATE, "a group member (its graph path solved first)");
-  if (!h->xr_ok || !xr_variant(h->dstep_variant) || h->pa.n_coarse <= 0 || h->n_cut < 0 ||
+  if (!h->xr_ok || !lane_in(h->step_lane, kLaneXr) || h->pa.n_coarse <= 0 || h->n_cut < 0 ||
       h->pa.n_coarse > kCapCoarseLds || h->n_cut > kCapCoarseLds)
     return fail(NX_ERR_STATE, "this rank cannot run the exchange step");
   CHECK(set_device(h));
   float v = 0.f;
-  int rc;
-  switch (h->dstep_variant) {
-    case 5: rc = xr_rehearse_wc<8, 2>(h, h->nranks, rtol, reps, &v); break;
-    case 7: rc = xr_rehearse_wc<8, 4>(h, h->nranks, rtol, reps, &v); break;
-    case 10: rc = xr_rehearse_wc<8, 3>(h, h->nranks, rtol, reps, &v); break;
-    default: rc = xr_rehearse_wc<16, 4>(h, h->nranks, rtol, reps, &v); break;
-  }
+  const int rc = with_lane<kLaneXr>(h->step_lane, [&](auto w, auto cpl) {
+    return xr_rehearse_wc<w(), cpl()>(h, h->nranks, rtol, reps, &v);
+  });
   *ms = v;
   return rc;
 }

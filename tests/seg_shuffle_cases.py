@@ -2,7 +2,7 @@
 file (not a test module).
 
 One small tree, ``make_tree(5, 5, 5)`` (31 edges) split into 8 jobs, per lane shape that a small
-N reaches through ``nx_set_preconditioner``'s variant table:
+N reaches through the lane-shape table (``sweep_lane_of`` / ``step_lane_of`` in csrc/nxhip.hip):
 
 ====  ==================  =====================================
  N    fused step          separate sweeps, MINRES, batch
@@ -13,8 +13,8 @@ N reaches through ``nx_set_preconditioner``'s variant table:
  40   ``<16, 4>``         ``<16, 4>``
 ====  ==================  =====================================
 
-(No N selects a 4-lane shape: ``<4, 4>`` is not in that table.) Every case runs the fused step
-twice (the first stores the CSR values; at N = 15 the second is the values-free
+(No 4-lane shape exists: the table has none, and ``<4, 4>`` is not instantiated.) Every case
+runs the fused step twice (the first stores the CSR values; at N = 15 the second is the values-free
 ``k_dir_step_kv``), the separate launches (``NXHIP_DIR_FUSED=0``), one MINRES solve and one
 batch solve of two columns, and returns solution, rhs, CSR values and the reported residual
 of each.

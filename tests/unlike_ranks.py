@@ -55,8 +55,8 @@ RANK_SUP = {"U1": (True, False), "U2": (False, True), "U3": (True, False, True),
 
 
 def lane_shape(N: int) -> tuple[int, int]:
-    """(W, CPL) of the one-launch step at N cells per edge (csrc/nxhip.hip, launch_xr: variants
-    5, 10, 7)."""
+    """(W, CPL) of the one-launch / exchange step at N <= 64 cells per edge (csrc/nxhip.hip,
+    step_lane_of; tests/test_gpu_lane_shapes.py compares it with ``Handle.lane_shapes``)."""
     return (8, 2) if N <= 16 else (8, 3) if N <= 24 else (8, 4) if N <= 32 else (16, 4)
 
 
