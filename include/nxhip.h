@@ -506,8 +506,8 @@ int nx_get_batch_info(nx_network_t* h, int32_t* launches, int32_t* refined, int3
  *   k_fe_b_condense   b_v - C b_i on the vertex rows, pressure / multiplier rows copied, into
  *                     the auxiliary columns; the auxiliary lumped mass (a + b) R h once per call
  *   k_b_up / k_b_top / k_b_down with the auxiliary handle's decomposition, on this handle's
- *                     stream; with cycles k_b_cyc_w / k_b_cyc_fix with the auxiliary Z / Cinv,
- *                     built first (fe_cyc_build) where the matrix is new
+ *                     stream; with cycles k_cyc_w / k_cyc_fix with the auxiliary Z / Cinv,
+ *                     built first (cyc_build) where the matrix is new
  *   k_fe_b_expand     the (k, 0) solution; added in a refinement pass
  *   k_b_res / k_b_norms   the true residual against this handle's CSR
  *   k_b_gather        when order != 0, then one copy per chunk

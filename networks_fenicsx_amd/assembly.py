@@ -566,7 +566,7 @@ class HydraulicNetworkAssembler:
         mass becomes the condensed ``R h [[a, b], [b, a]]`` (``element.condensed_flux_mass``),
         whose ratios are integers: ``a / b = (-1)^(k+1) (k+1)``. A graph with cycles (one
         rank, up to ``MAX_CYCLES`` cycle chains): the auxiliary tree solve is corrected by the
-        Woodbury step of its dropped couplings (``fe_cyc_build``). Several ranks:
+        Woodbury step of its dropped couplings (``cyc_build``). Several ranks:
         the auxiliary handle is the rank's P1/DG0 handle (its halo, cut rows, coarse step),
         and the ranks attach it only if every rank can run its direct tree solve."""
         mesh, fe = self._network_mesh, self._fe

@@ -7935,44 +7935,74 @@ __global__ void k_dir_publish_red(const double* __restrict__ rb, double rtol, in
   mr_publish(s, ini);
 }
 
-// ---- graphs with cycles (one rank, nx_set_cycles). The tree solve inverts A_g = A minus
-// the couplings a = A[q, lam] = A[lam, q] of the m/2 cycle-closing chains' grounded ends
-// (U = the unit columns of those rows, A = A_g + U C U^T, C = blocks [[0, a], [a, 0]]), so
+// ---- graphs with cycles: the Woodbury correction of the cycle chains. The
+// tree solve inverts A_g = A minus the couplings a = A[q, lam] = A[lam, q] of the m/2
+// cycle-closing chains' grounded ends (U = the unit columns of those rows, A = A_g + U C U^T,
+// C = blocks [[0, a], [a, 0]]), so
 //   A^{-1} b = x_g - Z Cinv U^T x_g,  x_g = A_g^{-1} b,  Z = A_g^{-1} U,
 //   Cinv = (C^{-1} + U^T Z)^{-1}                                   (Woodbury),
-// with Z (m columns) and Cinv built once per assembled matrix (cyc_build).
-// cycle-closing chains (m = 2 kMaxCyc columns; round 6: the capacitance matrix is inverted on
-// the device, cyc_invert, and the correction's kernels hold U^T x in dynamic LDS -- was 128)
-constexpr int kMaxCyc = 2048;
+// with Z (m columns) and Cinv built once per assembled matrix (cyc_build; Cinv by cyc_invert
+// on the device) and applied after the sweeps of every solve (cyc_before / cyc_after; the
+// batch: batch_sweeps). The kernels hold U^T x in dynamic LDS (m doubles). Its callers: one
+// rank (nx_set_cycles), several ranks (nx_set_cycles_team: U's m rows spread over the ranks --
+// a cycle chain's flux end lives with the chain, its multiplier row with the bifurcation's
+// owner -- every rank's share of U^T Z and of the couplings summed over the ranks per matrix,
+// U^T x per solve, one all-reduce each), the (k, 0) route's auxiliary handle in either form,
+// and the batched solves on one rank.
+constexpr int kMaxCyc = 2048;  // cycle-closing chains (m = 2 kMaxCyc columns)
 
-// The m x m matrix U^T Z and the couplings a (row q of the CSR, column lam).
-__global__ __launch_bounds__(256) void k_cyc_cap(Csr A, const double* __restrict__ Z, int64_t ldz,
-                                                 const int* __restrict__ rows, int m,
-                                                 double* __restrict__ cap, double* __restrict__ acoef) {
+// This rank's share of the m x m matrix U^T Z (own[i]: its row of U's column i, or -1; one
+// rank owns every row) and of the couplings a of the cycle chains it holds: pair k's flux end
+// row q and multiplier column lam are qloc[k], lcol[k] (-1: another rank's chain; lam maybe a
+// ghost column), or own[2k], own[2k + 1] where qloc is null (one rank). P1 = false: the CSR's
+// entry (q, lam). P1 = true (an auxiliary handle holds no assembled CSR): by q's position in
+// the P1 layout -- its edge's q_0 (-1 at the source multiplier) or q_N (+1 at the target's),
+// k_pattern's entries; anything else 0, which cyc_invert refuses.
+template <bool P1>
+__global__ __launch_bounds__(256) void k_cyc_cap(Csr A, int N, const double* __restrict__ Z,
+                                                 int64_t ldz, const int* __restrict__ own, int m,
+                                                 const int* __restrict__ qloc,
+                                                 const int* __restrict__ lcol,
+                                                 double* __restrict__ cap,
+                                                 double* __restrict__ acoef) {
   for (int i = threadIdx.x; i < m * m; i += 256) {
     const int r = i / m, c = i % m;
-    cap[i] = Z[(int64_t)c * ldz + rows[r]];
+    cap[i] = own[r] >= 0 ? Z[(int64_t)c * ldz + own[r]] : 0.0;
   }
   for (int k = threadIdx.x; 2 * k < m; k += 256) {
-    const int q = rows[2 * k], lam = rows[2 * k + 1];
+    const int q = qloc ? qloc[k] : own[2 * k];
     double a = 0.0;
-    for (int p = A.rowptr[q]; p < A.rowptr[q + 1]; ++p)
-      if (A.col[p] == lam) a = A.val[p];
-    acoef[k] = a;
+    if (q >= 0) {
+      if (P1) {
+        const int loc = q % (2 * N + 1);
+        a = loc == 0 ? -1.0 : (loc == 2 * N ? 1.0 : 0.0);
+      } else {
+        const int lam = lcol ? lcol[k] : own[2 * k + 1];
+        for (int p = A.rowptr[q]; p < A.rowptr[q + 1]; ++p)
+          if (A.col[p] == lam) a = A.val[p];
+      }
+    }
+    acoef[k] = a;  // (several ranks: summed over them, one rank holds each chain)
   }
 }
 
-// w = Cinv (U^T x - prev) (prev: U^T x before a refinement pass added its correction, or
-// null); save: U^T x is stored there instead (before a refinement pass). One workgroup.
-// Cinv is stored transposed (cinvT[j m + i] = Cinv[i][j]: a row per thread, coalesced); one
-// row of w per thread over ceil(m / 256) blocks (cyc_w_launch), U^T x in dynamic LDS (m doubles).
-__global__ __launch_bounds__(256) void k_cyc_w(const double* __restrict__ x, const int* __restrict__ rows,
-                                               int m, const double* __restrict__ cinvT,
-                                               const double* __restrict__ prev, double* __restrict__ w,
-                                               double* __restrict__ save) {
+// w = Cinv (g - prev) per column of X (blockIdx.y, through list where given; a single solve
+// is one column), g = U^T x: gathered through rows, or x itself where rows is null (a team's
+// U^T x, already summed over the ranks). prev: g before a refinement pass added its
+// correction, or null; save: g is stored there instead (before a refinement pass) -- both of
+// a single column. Cinv is stored transposed (cinvT[j m + i] = Cinv[i][j]: a row per thread,
+// coalesced); one row of w per thread over ceil(m / 256) blocks, g in dynamic LDS (m doubles).
+__global__ __launch_bounds__(256) void k_cyc_w(const double* __restrict__ X, int64_t ld,
+                                               const int* __restrict__ list,
+                                               const int* __restrict__ rows, int m,
+                                               const double* __restrict__ cinvT,
+                                               const double* __restrict__ prev,
+                                               double* __restrict__ w, double* __restrict__ save) {
   extern __shared__ double g[];
+  const int col = list ? list[blockIdx.y] : blockIdx.y;
+  const double* x = X + col * ld;
   for (int i = threadIdx.x; i < m; i += 256) {
-    const double v = x[rows[i]];
+    const double v = x[rows ? rows[i] : i];
     if (save && blockIdx.x == 0) save[i] = v;
     g[i] = prev ? v - prev[i] : v;
   }
@@ -7982,18 +8012,22 @@ __global__ __launch_bounds__(256) void k_cyc_w(const double* __restrict__ x, con
   if (i >= m) return;
   double s = 0.0;
   for (int j = 0; j < m; ++j) s += cinvT[(int64_t)j * m + i] * g[j];
-  w[i] = s;
+  w[(int64_t)col * m + i] = s;
 }
 
-// x -= Z w, one row per thread (the m columns in order).
-__global__ __launch_bounds__(kBlock) void k_cyc_fix(double* __restrict__ x, const double* __restrict__ Z,
-                                                    int64_t ldz, const double* __restrict__ w, int m,
+// x -= Z w per column, one row per thread (the m columns of Z in order).
+__global__ __launch_bounds__(kBlock) void k_cyc_fix(double* __restrict__ X, int64_t ld,
+                                                    const int* __restrict__ list,
+                                                    const double* __restrict__ Z, int64_t ldz,
+                                                    const double* __restrict__ w, int m,
                                                     int64_t n) {
+  const int col = list ? list[blockIdx.y] : blockIdx.y;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
+  const double* wc = w + (int64_t)col * m;
   double s = 0.0;
-  for (int j = 0; j < m; ++j) s += Z[(int64_t)j * ldz + i] * w[j];
-  x[i] -= s;
+  for (int j = 0; j < m; ++j) s += Z[(int64_t)j * ldz + i] * wc[j];
+  X[col * ld + i] -= s;
 }
 
 // b = e_row: the right-hand side of one column of Z (b zeroed before; several ranks: only
@@ -8002,53 +8036,11 @@ __global__ void k_cyc_unit(double* __restrict__ b, const int* __restrict__ rows,
   if (rows[j] >= 0) b[rows[j]] = 1.0;
 }
 
-// ---- graphs with cycles, several ranks (nx_set_cycles_team): the same Woodbury correction
-// with U's m rows spread over the ranks (a cycle chain's flux end lives with the chain, its
-// multiplier row with the bifurcation's owner). own[i]: this rank's row of U's column i,
-// or -1. Per assembled matrix every rank's share of U^T Z and of the couplings is summed over
-// the ranks (one all-reduce); per solve U^T x is (one all-reduce of m).
-
-// u_i = x[own_i] on this rank's rows, 0 elsewhere (summed over the ranks next)
+// Several ranks: u_i = x[own_i] on this rank's rows, 0 elsewhere (summed over the ranks next)
 __global__ __launch_bounds__(256) void k_cyc_gather(const double* __restrict__ x,
                                                     const int* __restrict__ own, int m,
                                                     double* __restrict__ u) {
   for (int i = threadIdx.x; i < m; i += 256) u[i] = own[i] >= 0 ? x[own[i]] : 0.0;
-}
-
-// This rank's share of U^T Z (rows of U it owns) and of the couplings a (the cycle chains it
-// holds: row q, column lam -- maybe a ghost column -- of its CSR).
-__global__ __launch_bounds__(256) void k_cyc_cap_team(Csr A, const double* __restrict__ Z, int64_t ldz,
-                                                      const int* __restrict__ own, int m,
-                                                      const int* __restrict__ qloc,
-                                                      const int* __restrict__ lcol,
-                                                      double* __restrict__ cap,
-                                                      double* __restrict__ acoef) {
-  for (int i = threadIdx.x; i < m * m; i += 256) {
-    const int r = i / m, c = i % m;
-    cap[i] = own[r] >= 0 ? Z[(int64_t)c * ldz + own[r]] : 0.0;
-  }
-  for (int k = threadIdx.x; 2 * k < m; k += 256) {
-    double a = 0.0;
-    if (qloc[k] >= 0)
-      for (int p = A.rowptr[qloc[k]]; p < A.rowptr[qloc[k] + 1]; ++p)
-        if (A.col[p] == lcol[k]) a = A.val[p];
-    acoef[k] = a;
-  }
-}
-
-// w = Cinv (u - prev) from the summed u (prev: U^T x before a refinement pass, or null).
-__global__ __launch_bounds__(256) void k_cyc_w_team(const double* __restrict__ u, int m,
-                                                    const double* __restrict__ cinvT,
-                                                    const double* __restrict__ prev,
-                                                    double* __restrict__ w) {
-  extern __shared__ double g[];
-  for (int i = threadIdx.x; i < m; i += 256) g[i] = prev ? u[i] - prev[i] : u[i];
-  __syncthreads();
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= m) return;
-  double s = 0.0;
-  for (int j = 0; j < m; ++j) s += cinvT[(int64_t)j * m + i] * g[j];
-  w[i] = s;
 }
 
 // ---- the capacitance matrix's inverse on the device (cyc_invert): Gauss-Jordan with partial
@@ -8623,7 +8615,7 @@ struct nx_network {
   double* cyc_gj = nullptr;    // cyc_invert's [A | I] (2 m^2) and its status word
   double* cyc_prev = nullptr;  // m
   double* cyc_w = nullptr;     // m
-  bool cyc_raw = false;        // cyc_build's solves: the tree solve alone
+  bool cyc_raw = false;        // cyc_build's solves: the tree solve alone (CycRawScope only)
   // several ranks (nx_set_cycles_team): per U column this rank's row or -1 (d_cyc_rows),
   // per pair the flux end row and the multiplier's column when the chain is here, else -1
   bool cyc_team = false;
@@ -11666,6 +11658,26 @@ LeanGraphs& lean_of(const Team& t) { return t.g ? t.g->lean : t.hs[0]->lean; }
 // r = b - A x as the previous pass's residual check left it in tmp. Both end with the true
 // residual (r kept in tmp again) published.
 
+// The cycle correction around a solve's sweeps, on one handle's rows and stream (k_cyc_*).
+// Several ranks read U^T x from cyc_u, summed over them first (cyc_gather_team).
+// Before a refinement pass's sweeps add to x: U^T x kept in cyc_prev (one rank's form).
+void cyc_before(const nx_network* h) {
+  const int m = 2 * h->n_cyc;
+  hipLaunchKernelGGL(k_cyc_w, dim3(grid_of(m, 256)), dim3(256), sizeof(double) * m, h->stream,
+                     h->x, 0, nullptr, h->d_cyc_rows, m, h->cyc_cinv, nullptr, h->cyc_w,
+                     h->cyc_prev);
+}
+// After the sweeps: x -= Z Cinv U^T (x - x_before), the couplings the tree solve dropped.
+void cyc_after(const nx_network* h, bool refine) {
+  const int m = 2 * h->n_cyc;
+  hipLaunchKernelGGL(k_cyc_w, dim3(grid_of(m, 256)), dim3(256), sizeof(double) * m, h->stream,
+                     h->cyc_team ? h->cyc_u : h->x, 0, nullptr,
+                     h->cyc_team ? nullptr : h->d_cyc_rows, m, h->cyc_cinv,
+                     refine ? h->cyc_prev : nullptr, h->cyc_w, nullptr);
+  hipLaunchKernelGGL(k_cyc_fix, dim3(grid_of(h->n_own, kBlock)), dim3(kBlock), 0, h->stream, h->x,
+                     0, nullptr, h->cyc_z, h->n_col, h->cyc_w, m, h->n_own);
+}
+
 // One rank, direct: the top part in every down workgroup (pa.topdown) -- only when the jobs
 // run in one round (every workgroup repeats the top part; C4 on one GPU, 4 rounds, measured
 // 0.524 vs 0.488 ms/step with the top kernel)
@@ -11687,10 +11699,7 @@ void launch_direct_wc(nx_network* h, double rtol, int refine, bool prof) {
   // refine: the previous pass's residual check left r = b - A x in tmp
   const double* bin = refine ? h->tmp : h->rhs;
   const bool cyc = h->n_cyc > 0 && !h->cyc_raw;  // graphs with cycles: Woodbury after the sweeps
-  const int m = 2 * h->n_cyc;
-  if (cyc && refine)  // U^T x before the sweeps add the tree solve's correction
-    hipLaunchKernelGGL(k_cyc_w, dim3(grid_of(m, 256)), dim3(256), sizeof(double) * m, h->stream, h->x, h->d_cyc_rows, m,
-                       h->cyc_cinv, nullptr, h->cyc_w, h->cyc_prev);
+  if (cyc && refine) cyc_before(h);  // U^T x before the sweeps add the tree solve's correction
   {  // the LDS sweeps in mode kModeDirect (direct_local: pc_lds)
     h->pa.accum = refine ? 1 : 0;  // refinement: the sweeps add the correction to x
     h->pa.fres = h->fres_ok ? 1 : 0;  // and the down sweep the residual check
@@ -11713,12 +11722,7 @@ void launch_direct_wc(nx_network* h, double rtol, int refine, bool prof) {
     }
   }
   if (h->cond_mass) return;  // an auxiliary solve: the (k, 0) handle checks its own residual
-  if (cyc) {  // x -= Z Cinv U^T (x - x_before): the couplings the tree solve dropped
-    hipLaunchKernelGGL(k_cyc_w, dim3(grid_of(m, 256)), dim3(256), sizeof(double) * m, h->stream, h->x, h->d_cyc_rows, m,
-                       h->cyc_cinv, refine ? h->cyc_prev : nullptr, h->cyc_w, nullptr);
-    hipLaunchKernelGGL(k_cyc_fix, dim3(grid_of(h->n_own, kBlock)), dim3(kBlock), 0, h->stream,
-                       h->x, h->cyc_z, h->n_col, h->cyc_w, m, h->n_own);
-  }
+  if (cyc) cyc_after(h, refine);  // the couplings the tree solve dropped
   const int nrb = grid_of(h->n_own, kRowsPerBlock * res_chunks(h->n_own));
   hipExtLaunchKernelGGL(k_residual_ck, dim3(nrb), dim3(kBlock), 0, h->stream,
                         prof ? h->dev[6] : nullptr, prof ? h->dev[7] : nullptr, 0, csr_of(h), h->x,
@@ -11985,36 +11989,6 @@ int cyc_build_launches(const nx_network* h) {
   return m * (1 + sweeps) + 1 + (1 + 2 * m + 1);
 }
 
-// Graphs with cycles: Z = A_g^{-1} U column by column (the tree solve of a unit right-hand
-// side, accumulated into a zeroed x), then C^{-1} + U^T Z inverted on the host (m <= 256,
-// Gauss-Jordan with partial pivoting). Once per assembled matrix.
-int cyc_build(nx_network* h) {
-  const int m = 2 * h->n_cyc;
-  CHECK(ensure_dq(h));
-  h->cyc_raw = true;
-  h->need_r = false;
-  for (int j = 0; j < m; ++j) {
-    HIPCALL(hipMemsetAsync(h->tmp, 0, sizeof(double) * h->n_col, h->stream));
-    HIPCALL(hipMemsetAsync(h->x, 0, sizeof(double) * h->n_col, h->stream));
-    hipLaunchKernelGGL(k_cyc_unit, dim3(1), dim3(1), 0, h->stream, h->tmp, h->d_cyc_rows, j);
-    const int rc = launch_direct(h, 0.0, 1);
-    if (rc != NX_OK) {
-      h->cyc_raw = false;
-      return rc;
-    }
-    h->seq += 1;
-    CHECK(wait_published(h));
-    HIPCALL(hipMemcpyAsync(h->cyc_z + (int64_t)j * h->n_col, h->x, sizeof(double) * h->n_col,
-                           hipMemcpyDeviceToDevice, h->stream));
-  }
-  h->cyc_raw = false;
-  hipLaunchKernelGGL(k_cyc_cap, dim3(1), dim3(256), 0, h->stream, csr_of(h), h->cyc_z, h->n_col,
-                     h->d_cyc_rows, m, h->cyc_cap, h->cyc_cap + (int64_t)m * m);
-  CHECK(cyc_invert(h));
-  h->cyc_version = h->lhs_version;
-  return NX_OK;
-}
-
 // Exact on this handle: one rank (no communicator, no group), the exact Schur-complement
 // preconditioner (consistent mass) on a decomposition without grounded cycle chains.
 // This rank can run the direct solve exactly: the exact Schur-complement preconditioner
@@ -12169,15 +12143,8 @@ int cyc_gather_team(const Team& t, bool prev) {
 // residual of A (the halo of x, every owned row from the CSR, the two sums over the ranks)
 // published -- r kept in tmp for a refinement pass.
 int cyc_fix_team(const Team& t, double rtol, bool refine) {
-  const int m = 2 * t.hs[0]->n_cyc;
   CHECK(cyc_gather_team(t, false));
-  for (int r = 0; r < t.P; ++r) {
-    nx_network* h = t.hs[r];
-    hipLaunchKernelGGL(k_cyc_w_team, dim3(grid_of(m, 256)), dim3(256), sizeof(double) * m, h->stream, h->cyc_u, m, h->cyc_cinv,
-                       refine ? h->cyc_prev : nullptr, h->cyc_w);
-    hipLaunchKernelGGL(k_cyc_fix, dim3(grid_of(h->n_own, kBlock)), dim3(kBlock), 0, h->stream,
-                       h->x, h->cyc_z, h->n_col, h->cyc_w, m, h->n_own);
-  }
+  for (int r = 0; r < t.P; ++r) cyc_after(t.hs[r], refine);
   HIPCALL(hipGetLastError());
   CHECK(team_halo(t, VS_X, 0));
   for (int r = 0; r < t.P; ++r) {
@@ -12201,50 +12168,110 @@ int cyc_fix_team(const Team& t, double rtol, bool refine) {
   return NX_OK;
 }
 
-// Z = A_g^{-1} U over the ranks (2K team tree solves of a unit right-hand side set by the
-// row's owner, accumulated into zeroed x -- a refinement pass's shape), then every rank's
-// share of U^T Z and of the couplings, summed over the ranks, and the same Cinv on every
-// rank. Once per assembled matrix.
-int cyc_build_team(const Team& t) {
-  const int m = 2 * t.hs[0]->n_cyc;
-  for (int r = 0; r < t.P; ++r) {
-    CHECK(ensure_dq(t.hs[r]));
-    t.hs[r]->cyc_raw = true;
+// ---- the correction's build, once per assembled matrix, for every caller -------------------
+// cyc_raw on a build's handles while its unit solves run (the tree solve alone), cleared on
+// every way out: a failed build leaves no handle solving without its correction, and the stale
+// cyc_version has the next solve build again.
+struct CycRawScope {
+  const Team& t;
+  const bool on;
+  CycRawScope(const Team& team, bool set) : t(team), on(set) {
+    for (int r = 0; on && r < t.P; ++r) t.hs[r]->cyc_raw = true;
   }
-  int rc = NX_OK;
-  for (int j = 0; j < m && rc == NX_OK; ++j) {
+  ~CycRawScope() {
+    for (int r = 0; on && r < t.P; ++r) t.hs[r]->cyc_raw = false;
+  }
+  CycRawScope(const CycRawScope&) = delete;
+  CycRawScope& operator=(const CycRawScope&) = delete;
+};
+
+// An auxiliary handle's launches on its (k, 0) handle's stream (no cross-queue hand-offs),
+// its own stream back on every way out.
+struct StreamLoan {
+  nx_network* a;
+  const hipStream_t own;
+  StreamLoan(nx_network* aux, hipStream_t s) : a(aux), own(aux->stream) { a->stream = s; }
+  ~StreamLoan() { a->stream = own; }
+  StreamLoan(const StreamLoan&) = delete;
+  StreamLoan& operator=(const StreamLoan&) = delete;
+};
+
+// Is the correction of t's handles another matrix's? of: the (k, 0) handle whose matrix an
+// auxiliary handle's correction belongs to (its condensed mass is R h [[a, b], [b, a]]);
+// null: every handle's own.
+bool cyc_stale(const Team& t, const nx_network* of) {
+  for (int r = 0; r < t.P; ++r)
+    if (t.hs[r]->cyc_version != (of ? of : t.hs[r])->lhs_version) return true;
+  return false;
+}
+
+// Z = A_g^{-1} U column by column -- the tree solve of a unit right-hand side set by the
+// row's owner, accumulated into zeroed x (a refinement pass's shape) -- then every rank's share
+// of U^T Z and of the couplings (k_cyc_cap; several ranks: summed over them) and the same
+// Cinv on every rank (cyc_invert). The flavours:
+//   t's handles solve their own CSR (of null): their lumped mass current (ensure_dq), the
+//     couplings the CSR's entries, every unit solve published and waited for;
+//   t is one auxiliary handle of the (k, 0) handle `of`: on of's stream, the lumped mass as
+//     k_fe_condense just wrote it, the couplings by position in the P1 layout, the sweeps
+//     only. (One rank's sweeps run without cyc_raw: launch_direct_wc returns after them on an
+//     auxiliary handle, and its refinement form stores U^T x first -- a launch per column that
+//     fe_cyc_build_launches counts.)
+// One rank (no cyc_team) solves by launch_direct, several by launch_direct_team.
+int cyc_build(const Team& t, const nx_network* of) {
+  nx_network* h0 = t.hs[0];
+  const int m = 2 * h0->n_cyc;
+  const bool aux = of != nullptr, team = h0->cyc_team;
+  if (!aux)
+    for (int r = 0; r < t.P; ++r) CHECK(ensure_dq(t.hs[r]));
+  const CycRawScope raw(t, !aux || team);
+  for (int r = 0; r < t.P; ++r) t.hs[r]->need_r = false;
+  for (int j = 0; j < m; ++j) {
     for (int r = 0; r < t.P; ++r) {
       nx_network* h = t.hs[r];
       HIPCALL(hipMemsetAsync(h->tmp, 0, sizeof(double) * h->n_col, h->stream));
       HIPCALL(hipMemsetAsync(h->x, 0, sizeof(double) * h->n_col, h->stream));
       hipLaunchKernelGGL(k_cyc_unit, dim3(1), dim3(1), 0, h->stream, h->tmp, h->d_cyc_rows, j);
     }
-    rc = launch_direct_team(t, 0.0, 1, false);
-    for (int r = 0; r < t.P && rc == NX_OK; ++r) {
+    if (team)
+      CHECK(launch_direct_team(t, 0.0, 1, false, !aux));
+    else
+      CHECK(launch_direct(h0, 0.0, 1));
+    for (int r = 0; r < t.P; ++r) {
       nx_network* h = t.hs[r];
-      h->seq += 1;
-      rc = wait_published(h);
-      if (rc == NX_OK && hipMemcpyAsync(h->cyc_z + (int64_t)j * h->n_col, h->x,
-                                        sizeof(double) * h->n_col, hipMemcpyDeviceToDevice,
-                                        h->stream) != hipSuccess)
-        rc = fail(NX_ERR_HIP, "cycle correction: copying a column of Z failed");
+      if (!aux) {
+        h->seq += 1;
+        CHECK(wait_published(h));
+      }
+      HIPCALL(hipMemcpyAsync(h->cyc_z + (int64_t)j * h->n_col, h->x, sizeof(double) * h->n_col,
+                             hipMemcpyDeviceToDevice, h->stream));
     }
   }
-  for (int r = 0; r < t.P; ++r) t.hs[r]->cyc_raw = false;
-  CHECK(rc);
   for (int r = 0; r < t.P; ++r) {
     nx_network* h = t.hs[r];
-    hipLaunchKernelGGL(k_cyc_cap_team, dim3(1), dim3(256), 0, h->stream, csr_of(h), h->cyc_z,
-                       h->n_col, h->d_cyc_rows, m, h->d_cyc_qloc, h->d_cyc_lcol, h->cyc_cap,
-                       h->cyc_cap + (int64_t)m * m);
+    double* acoef = h->cyc_cap + (int64_t)m * m;
+    if (aux)
+      hipLaunchKernelGGL(k_cyc_cap<true>, dim3(1), dim3(256), 0, h->stream, Csr{}, (int)h->N,
+                         h->cyc_z, h->n_col, h->d_cyc_rows, m, h->d_cyc_qloc, nullptr, h->cyc_cap,
+                         acoef);
+    else
+      hipLaunchKernelGGL(k_cyc_cap<false>, dim3(1), dim3(256), 0, h->stream, csr_of(h), 0,
+                         h->cyc_z, h->n_col, h->d_cyc_rows, m, h->d_cyc_qloc, h->d_cyc_lcol,
+                         h->cyc_cap, acoef);
   }
   HIPCALL(hipGetLastError());
-  CHECK(team_allreduce(t, -4, m * m + m / 2));
+  if (team) CHECK(team_allreduce(t, -4, m * m + m / 2));
   for (int r = 0; r < t.P; ++r) {
     CHECK(cyc_invert(t.hs[r]));
-    t.hs[r]->cyc_version = t.hs[r]->lhs_version;
+    t.hs[r]->cyc_version = (of ? of : t.hs[r])->lhs_version;
   }
   return NX_OK;
+}
+
+// The correction of another matrix is built for this one first (built: whether it was).
+int cyc_make_current(const Team& t, const nx_network* of = nullptr, bool* built = nullptr) {
+  const bool stale = cyc_stale(t, of);
+  if (built) *built = stale;
+  return stale ? cyc_build(t, of) : NX_OK;
 }
 
 // The direct solve of a team (one rank, a group or an RCCL rank): one graph -- on one rank
@@ -12668,16 +12695,9 @@ int solve_direct(const Team& t, double rtol, int32_t* iters, double* relres,
   const bool prof1 = !multi && h->prof;  // events bound to the dispatches (profiling)
   if (prof1 && !h->dev[0])
     for (auto& e : h->dev) HIPCALL(hipEventCreate(&e));
-  if (!multi && h->n_cyc > 0) {  // cycles: the correction of this matrix first
-    CHECK(flush_assembly(h));
-    if (h->cyc_version != h->lhs_version) CHECK(cyc_build(h));
-  } else if (multi && h->cyc_team && h->n_cyc > 0) {  // (several ranks: built together)
-    bool stale = false;
-    for (int r = 0; r < t.P; ++r) {
-      CHECK(flush_assembly(t.hs[r]));
-      stale = stale || t.hs[r]->cyc_version != t.hs[r]->lhs_version;
-    }
-    if (stale) CHECK(cyc_build_team(t));
+  if (h->n_cyc > 0 && (!multi || h->cyc_team)) {  // cycles: the correction of this matrix first
+    for (int r = 0; r < t.P; ++r) CHECK(flush_assembly(t.hs[r]));  // (several ranks: together)
+    CHECK(cyc_make_current(t));
   }
   // the deferred assembly heads the solve (every rank's, several ranks)
   bool with_asm = true;
@@ -13028,120 +13048,6 @@ int fe_true_residual_team(nx_network* h, double rtol, int nrb) {
   HIPCALL(hipGetLastError());
   return NX_OK;
 }
-// The couplings a = A[q, lam] of the cycle chains' grounded ends from the P1 layout's rows
-// (the auxiliary handle holds no assembled CSR): a flux end q is its edge's q_0 (-1 at the
-// source multiplier) or q_N (+1 at the target's) -- k_pattern's entries; then U^T Z as
-// k_cyc_cap forms it.
-__global__ __launch_bounds__(256) void k_cyc_cap_p1(const double* __restrict__ Z, int64_t ldz,
-                                                    const int* __restrict__ rows, int m, int N,
-                                                    double* __restrict__ cap,
-                                                    double* __restrict__ acoef) {
-  for (int i = threadIdx.x; i < m * m; i += 256) {
-    const int r = i / m, c = i % m;
-    cap[i] = Z[(int64_t)c * ldz + rows[r]];
-  }
-  for (int k = threadIdx.x; 2 * k < m; k += 256) {
-    const int loc = rows[2 * k] % (2 * N + 1);
-    acoef[k] = loc == 0 ? -1.0 : (loc == 2 * N ? 1.0 : 0.0);  // (0: cyc_invert refuses it)
-  }
-}
-
-// Several ranks: this rank's share of U^T Z (the rows of U it owns) and the couplings of the
-// cycle chains it holds, by the flux end's position in the P1 layout (k_cyc_cap_team's, with
-// no CSR values: the auxiliary handle holds none)
-__global__ __launch_bounds__(256) void k_cyc_cap_team_p1(const double* __restrict__ Z, int64_t ldz,
-                                                         const int* __restrict__ own, int m,
-                                                         const int* __restrict__ qloc, int N,
-                                                         double* __restrict__ cap,
-                                                         double* __restrict__ acoef) {
-  for (int i = threadIdx.x; i < m * m; i += 256) {
-    const int r = i / m, c = i % m;
-    cap[i] = own[r] >= 0 ? Z[(int64_t)c * ldz + own[r]] : 0.0;
-  }
-  for (int k = threadIdx.x; 2 * k < m; k += 256) {
-    double a = 0.0;
-    if (qloc[k] >= 0) {
-      const int loc = qloc[k] % (2 * N + 1);
-      a = loc == 0 ? -1.0 : (loc == 2 * N ? 1.0 : 0.0);
-    }
-    acoef[k] = a;  // (summed over the ranks: one rank holds each chain)
-  }
-}
-
-// Several ranks: the auxiliary handle's team Woodbury correction (nx_set_cycles_team on it):
-// Z by the ranks' tree solves of unit right-hand sides (sweeps only, the coarse all-reduce
-// between their halves), U^T Z and the couplings summed over the ranks, Cinv on every rank
-int fe_cyc_build_team(nx_network* h, nx_network* a) {
-  const int m = 2 * a->n_cyc;
-  const hipStream_t as = a->stream;
-  a->stream = h->stream;
-  a->need_r = false;
-  a->cyc_raw = true;
-  nx_network* ah[1] = {a};
-  const Team t{ah, 1, nullptr};
-  int rc = NX_OK;
-  for (int j = 0; j < m && rc == NX_OK; ++j) {
-    if (hipMemsetAsync(a->tmp, 0, sizeof(double) * a->n_col, a->stream) != hipSuccess ||
-        hipMemsetAsync(a->x, 0, sizeof(double) * a->n_col, a->stream) != hipSuccess) {
-      rc = fail(NX_ERR_HIP, "fe_cyc_build_team: memset");
-      break;
-    }
-    hipLaunchKernelGGL(k_cyc_unit, dim3(1), dim3(1), 0, a->stream, a->tmp, a->d_cyc_rows, j);
-    rc = launch_direct_team(t, 0.0, 1, false, false);
-    if (rc == NX_OK &&
-        hipMemcpyAsync(a->cyc_z + (int64_t)j * a->n_col, a->x, sizeof(double) * a->n_col,
-                       hipMemcpyDeviceToDevice, a->stream) != hipSuccess)
-      rc = fail(NX_ERR_HIP, "fe_cyc_build_team: copy");
-  }
-  a->cyc_raw = false;
-  if (rc == NX_OK) {
-    hipLaunchKernelGGL(k_cyc_cap_team_p1, dim3(1), dim3(256), 0, a->stream, a->cyc_z, a->n_col,
-                       a->d_cyc_rows, m, a->d_cyc_qloc, (int)a->N, a->cyc_cap,
-                       a->cyc_cap + (int64_t)m * m);
-    rc = team_allreduce(t, -4, m * m + m / 2);
-  }
-  if (rc == NX_OK) rc = cyc_invert(a);
-  a->stream = as;
-  CHECK(rc);
-  a->cyc_version = h->lhs_version;
-  return NX_OK;
-}
-
-// (k, 0) on a graph with cycles (one rank): the auxiliary handle's Woodbury correction for
-// the condensed system (nx_set_cycles on the auxiliary handle): Z = A_g^{-1} U by its tree
-// solves of unit right-hand sides (the condensed lumped mass just written by k_fe_condense),
-// U^T Z and the couplings, Cinv on the host. On this handle's stream; once per assembled
-// matrix of h (its coefficients: the condensed mass is R h [[a, b], [b, a]]).
-int fe_cyc_build(nx_network* h, nx_network* a) {
-  const int m = 2 * a->n_cyc;
-  const hipStream_t as = a->stream;
-  a->stream = h->stream;
-  a->need_r = false;
-  int rc = NX_OK;
-  for (int j = 0; j < m && rc == NX_OK; ++j) {
-    if (hipMemsetAsync(a->tmp, 0, sizeof(double) * a->n_col, a->stream) != hipSuccess ||
-        hipMemsetAsync(a->x, 0, sizeof(double) * a->n_col, a->stream) != hipSuccess) {
-      rc = fail(NX_ERR_HIP, "fe_cyc_build: memset");
-      break;
-    }
-    hipLaunchKernelGGL(k_cyc_unit, dim3(1), dim3(1), 0, a->stream, a->tmp, a->d_cyc_rows, j);
-    rc = launch_direct(a, 0.0, 1);  // (refinement form: x += A_g^{-1} tmp; sweeps only)
-    if (rc == NX_OK &&
-        hipMemcpyAsync(a->cyc_z + (int64_t)j * a->n_col, a->x, sizeof(double) * a->n_col,
-                       hipMemcpyDeviceToDevice, a->stream) != hipSuccess)
-      rc = fail(NX_ERR_HIP, "fe_cyc_build: copy");
-  }
-  if (rc == NX_OK) {
-    hipLaunchKernelGGL(k_cyc_cap_p1, dim3(1), dim3(256), 0, a->stream, a->cyc_z, a->n_col,
-                       a->d_cyc_rows, m, (int)a->N, a->cyc_cap, a->cyc_cap + (int64_t)m * m);
-    rc = cyc_invert(a);
-  }
-  a->stream = as;
-  CHECK(rc);
-  a->cyc_version = h->lhs_version;
-  return NX_OK;
-}
-
 int fe_solve_direct(nx_network* h, double rtol, int32_t* iters, double* relres,
                     int32_t* converged) {
   nx_network* a = h->fe_aux;
@@ -13165,38 +13071,19 @@ int fe_solve_direct(nx_network* h, double rtol, int32_t* iters, double* relres,
     const double* b = pass ? h->tmp : h->rhs;  // refinement: the residual the check kept
     hipLaunchKernelGGL(k_fe_condense, dim3(grid_of(n0, kBlock)), dim3(kBlock), 0, h->stream, c,
                        b, pass ? nullptr : a->dq, a->rhs);
-    // a graph with cycles: Woodbury (one rank; several: the team's, a->cyc_team)
-    const int mcyc = (!ranks || a->cyc_team) ? 2 * a->n_cyc : 0;
-    if (mcyc && pass == 0 && a->cyc_version != h->lhs_version)
-      CHECK(ranks ? fe_cyc_build_team(h, a) : fe_cyc_build(h, a));
     {  // the auxiliary tree solve on this handle's stream (no cross-queue hand-offs)
-      const hipStream_t as = a->stream;
-      a->stream = h->stream;
+      const StreamLoan loan(a, h->stream);
       nx_network* ah[1] = {a};
-      const int rc = ranks ? launch_direct_team(Team{ah, 1, nullptr}, 0.0, 0, false, false)
-                           : launch_direct(a, 0.0, 0);
-      a->stream = as;
-      CHECK(rc);
-    }
-    if (mcyc && !ranks) {  // x_aux -= Z Cinv U^T x_aux: the couplings the tree solve dropped
-      hipLaunchKernelGGL(k_cyc_w, dim3(grid_of(mcyc, 256)), dim3(256), sizeof(double) * mcyc, h->stream, a->x, a->d_cyc_rows, mcyc,
-                         a->cyc_cinv, nullptr, a->cyc_w, nullptr);
-      hipLaunchKernelGGL(k_cyc_fix, dim3(grid_of(a->n_own, kBlock)), dim3(kBlock), 0, h->stream,
-                         a->x, a->cyc_z, a->n_col, a->cyc_w, mcyc, a->n_own);
-    } else if (mcyc) {  // several ranks: U^T x_aux summed over them first
-      const hipStream_t as = a->stream;
-      a->stream = h->stream;
-      nx_network* ah[1] = {a};
-      const int rc = cyc_gather_team(Team{ah, 1, nullptr}, false);
-      if (rc == NX_OK) {
-        hipLaunchKernelGGL(k_cyc_w_team, dim3(grid_of(mcyc, 256)), dim3(256),
-                           sizeof(double) * mcyc, h->stream, a->cyc_u, mcyc, a->cyc_cinv, nullptr,
-                           a->cyc_w);
-        hipLaunchKernelGGL(k_cyc_fix, dim3(grid_of(a->n_own, kBlock)), dim3(kBlock), 0,
-                           h->stream, a->x, a->cyc_z, a->n_col, a->cyc_w, mcyc, a->n_own);
+      const Team ta{ah, 1, nullptr};
+      // a graph with cycles: Woodbury (one rank; several: the team's, a->cyc_team), its
+      // correction built from the condensed mass of this matrix
+      const bool cyc = a->n_cyc > 0 && (!ranks || a->cyc_team);
+      if (cyc && pass == 0) CHECK(cyc_make_current(ta, h));
+      CHECK(ranks ? launch_direct_team(ta, 0.0, 0, false, false) : launch_direct(a, 0.0, 0));
+      if (cyc) {  // x_aux -= Z Cinv U^T x_aux: the couplings the tree solve dropped
+        if (a->cyc_team) CHECK(cyc_gather_team(ta, false));
+        cyc_after(a, false);
       }
-      a->stream = as;
-      CHECK(rc);
     }
     hipLaunchKernelGGL(k_fe_expand, dim3(grid_of(n0 + np, kBlock)), dim3(kBlock), 0, h->stream,
                        c, a->x, b, h->x, pass);
@@ -13668,40 +13555,6 @@ NX_API int nx_solve(nx_network_t* h, double rtol, int32_t maxit, int32_t check_e
 // ---- nx_batch_solve: many boundary / source scenarios against the handle's matrix ----------
 namespace {
 
-// Batched forms of the cycle correction x -= Z Cinv U^T x (k_cyc_w / k_cyc_fix, the same
-// sums in the same order) on the listed columns: w = Cinv U^T x per column (U^T x in dynamic
-// LDS, m doubles), then x -= Z w.
-__global__ __launch_bounds__(256) void k_b_cyc_w(const double* __restrict__ X, int64_t ld,
-                                                 const int* __restrict__ list,
-                                                 const int* __restrict__ rows, int m,
-                                                 const double* __restrict__ cinvT,
-                                                 double* __restrict__ w) {
-  extern __shared__ double g[];
-  const int col = list ? list[blockIdx.y] : blockIdx.y;
-  const double* x = X + col * ld;
-  for (int i = threadIdx.x; i < m; i += 256) g[i] = x[rows[i]];
-  __syncthreads();
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= m) return;
-  double s = 0.0;
-  for (int j = 0; j < m; ++j) s += cinvT[(int64_t)j * m + i] * g[j];
-  w[(int64_t)col * m + i] = s;
-}
-
-__global__ __launch_bounds__(kBlock) void k_b_cyc_fix(double* __restrict__ X, int64_t ld,
-                                                      const int* __restrict__ list,
-                                                      const double* __restrict__ Z, int64_t ldz,
-                                                      const double* __restrict__ w, int m,
-                                                      int64_t n) {
-  const int col = list ? list[blockIdx.y] : blockIdx.y;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const double* wc = w + (int64_t)col * m;
-  double s = 0.0;
-  for (int j = 0; j < m; ++j) s += Z[(int64_t)j * ldz + i] * wc[j];
-  X[col * ld + i] -= s;
-}
-
 // ---- ensembles on graphs with cycles (nx_set_ensemble_cycles). The handle's
 // Z and Cinv belong to the resident R, so every scenario j gets a correction of its own in the
 // solve-again form:
@@ -13852,7 +13705,7 @@ __global__ __launch_bounds__(kEnsFacThreads) void k_e_cyc_factor(Csr A,
 }
 
 // Per listed column: w = K_j^{-1} U^T x_g with the column's factors (U^T x_g in dynamic LDS, m
-// doubles, as k_b_cyc_w; the row swaps, the unit lower and the upper substitution, one entry per
+// doubles, as k_cyc_w; the row swaps, the unit lower and the upper substitution, one entry per
 // thread and step), then the second right-hand side b - U w patched into the input column in
 // place: its m entries are saved first (save, m per column) and k_e_cyc_restore puts them
 // back bit for bit after the second sweep. A flagged scenario: w = 0.
@@ -14265,9 +14118,10 @@ void batch_sweeps_wc(const SweepCtx& sc, const int* list, int nc, const double* 
     *sc.launches += 1;
   } else if (h->n_cyc > 0) {
     const int m = 2 * h->n_cyc;
-    hipLaunchKernelGGL(k_b_cyc_w, dim3(grid_of(m, 256), nc), dim3(256), sizeof(double) * m,
-                       sc.stream, out, bc.ld, list, h->d_cyc_rows, m, h->cyc_cinv, sc.cw);
-    hipLaunchKernelGGL(k_b_cyc_fix, dim3(grid_of(h->n_own, kBlock), nc), dim3(kBlock), 0,
+    hipLaunchKernelGGL(k_cyc_w, dim3(grid_of(m, 256), nc), dim3(256), sizeof(double) * m,
+                       sc.stream, out, bc.ld, list, h->d_cyc_rows, m, h->cyc_cinv, nullptr, sc.cw,
+                       nullptr);
+    hipLaunchKernelGGL(k_cyc_fix, dim3(grid_of(h->n_own, kBlock), nc), dim3(kBlock), 0,
                        sc.stream, out, bc.ld, list, h->cyc_z, h->n_col, sc.cw, m, h->n_own);
     *sc.launches += 2;
   }
@@ -14521,10 +14375,12 @@ int batch_solve_p1(nx_network* h, const BatchWs& ws, int nc, const double* Bv, d
 // its solves borrow the handle's x, tmp and published state, put back afterwards).
 int batch_make_current(nx_network* h, const BatchWs& ws) {
   CHECK(ensure_dq(h));
-  if (h->n_cyc > 0 && h->cyc_version != h->lhs_version) {
+  nx_network* hs[1] = {h};
+  const Team t{hs, 1, nullptr};
+  if (h->n_cyc > 0 && cyc_stale(t, nullptr)) {
     BatchSaved sv{};
     CHECK(batch_save(h, ws, &sv, false));
-    const int rc = cyc_build(h);
+    const int rc = cyc_build(t, nullptr);
     CHECK(batch_restore(h, ws, sv, false));
     CHECK(rc);
     h->b_launches += cyc_build_launches(h);
@@ -15000,9 +14856,9 @@ int fe_batch_rhs_chunk(nx_network* h, const BatchWs& ws, int c0, int nc, const d
   return NX_OK;
 }
 
-// The kernel launches of one fe_cyc_build: per column of Z the unit right-hand side, the
-// refinement form's k_cyc_w and the auxiliary sweeps (launch_direct_wc returns after them on
-// an auxiliary handle), then k_cyc_cap_p1 and cyc_invert.
+// The kernel launches of one cyc_build on the auxiliary handle (one rank): per column of Z the
+// unit right-hand side, the refinement form's k_cyc_w and the auxiliary sweeps
+// (launch_direct_wc returns after them on an auxiliary handle), then k_cyc_cap and cyc_invert.
 int fe_cyc_build_launches(const nx_network* a) {
   const int m = 2 * a->n_cyc;
   const int sweeps = (a->pc_jobs > 0 ? 2 : 0) + (top_down_on(a) ? 0 : 1);
@@ -15013,7 +14869,7 @@ int fe_cyc_build_launches(const nx_network* a) {
 // auxiliary sweeps with the cycle correction, expand. The auxiliary handle lends its PcArgs,
 // decomposition and Z / Cinv; its stream is this handle's for the launches. dq (first pass of
 // a call): the auxiliary lumped mass is written by the condensation, and the correction is
-// built after it where the matrix is new (fe_cyc_build reads that lumped mass).
+// built after it where the matrix is new (cyc_build reads that lumped mass).
 int fe_batch_apply(nx_network* h, const BatchWs& ws, const FeAuxWs& wa, const int* list, int nc,
                    const double* Bv, double* Xv, int accum, bool dq) {
   const FeCond c = fe_cond_of(h);
@@ -15022,10 +14878,13 @@ int fe_batch_apply(nx_network* h, const BatchWs& ws, const FeAuxWs& wa, const in
                      Bv, ws.cols.ld, wa.B, wa.cols.ld, list, nc, dq ? h->fe_aux->dq : nullptr);
   HIPCALL(hipGetLastError());
   h->b_launches += 1;
-  if (dq && h->fe_aux->n_cyc > 0 && h->fe_aux->cyc_version != h->lhs_version) {
+  if (dq && h->fe_aux->n_cyc > 0) {
     // (the one place a batched call writes the auxiliary handle: its correction, per matrix)
-    CHECK(fe_cyc_build(h, h->fe_aux));
-    h->b_launches += fe_cyc_build_launches(h->fe_aux);
+    const StreamLoan loan(h->fe_aux, h->stream);
+    nx_network* ah[1] = {h->fe_aux};
+    bool built = false;
+    CHECK(cyc_make_current(Team{ah, 1, nullptr}, h, &built));
+    if (built) h->b_launches += fe_cyc_build_launches(h->fe_aux);
   }
   const nx_network* a = h->fe_aux;  // lent read-only: the sweeps run on this handle's stream
   const SweepCtx sc{a, h->stream, &h->b_launches, wa.cols, wa.cw, nullptr, nullptr, nullptr,
@@ -17474,6 +17333,38 @@ void free_cycles(nx_network* h) {
   h->n_cyc = 0;
   h->cyc_version = -1;
 }
+// The correction's buffers for K cycle chains and its tables uploaded: own (2 K rows of U's
+// columns); several ranks also qloc and lcol (K each) and the summed U^T x.
+int fill_cycles(nx_network* h, int K, const int32_t* own, const int32_t* qloc,
+                const int32_t* lcol) {
+  const size_t m = 2 * (size_t)K;
+  HIPCALL(hipMalloc((void**)&h->d_cyc_rows, sizeof(int) * m));
+  HIPCALL(hipMalloc((void**)&h->cyc_z, sizeof(double) * m * h->n_col));
+  HIPCALL(hipMalloc((void**)&h->cyc_cinv, sizeof(double) * m * m));
+  HIPCALL(hipMalloc((void**)&h->cyc_cap, sizeof(double) * (m * m + K)));
+  HIPCALL(hipMalloc((void**)&h->cyc_prev, sizeof(double) * m));
+  HIPCALL(hipMalloc((void**)&h->cyc_w, sizeof(double) * m));
+  HIPCALL(hipMemcpy(h->d_cyc_rows, own, sizeof(int) * m, hipMemcpyHostToDevice));
+  if (!qloc) return NX_OK;
+  HIPCALL(hipMalloc((void**)&h->d_cyc_qloc, sizeof(int) * K));
+  HIPCALL(hipMalloc((void**)&h->d_cyc_lcol, sizeof(int) * K));
+  HIPCALL(hipMalloc((void**)&h->cyc_u, sizeof(double) * m));
+  HIPCALL(hipMemcpy(h->d_cyc_qloc, qloc, sizeof(int) * K, hipMemcpyHostToDevice));
+  HIPCALL(hipMemcpy(h->d_cyc_lcol, lcol, sizeof(int) * K, hipMemcpyHostToDevice));
+  return NX_OK;
+}
+// A failure midway leaves the handle with no correction (free_cycles ran, n_cyc == 0).
+int alloc_cycles(nx_network* h, int K, const int32_t* own, const int32_t* qloc,
+                 const int32_t* lcol) {
+  const int rc = fill_cycles(h, K, own, qloc, lcol);
+  if (rc != NX_OK) {
+    free_cycles(h);
+    return rc;
+  }
+  h->n_cyc = K;
+  h->cyc_team = qloc != nullptr;
+  return NX_OK;
+}
 }  // namespace
 
 NX_API int nx_set_cycles(nx_network_t* h, int32_t n, const int32_t* rows) {
@@ -17491,15 +17382,7 @@ NX_API int nx_set_cycles(nx_network_t* h, int32_t n, const int32_t* rows) {
   CHECK(drop_handle_graphs(h));
   free_cycles(h);
   if (n == 0) return NX_OK;
-  const int m = 2 * n;
-  HIPCALL(hipMalloc((void**)&h->d_cyc_rows, sizeof(int) * m));
-  HIPCALL(hipMalloc((void**)&h->cyc_z, sizeof(double) * m * h->n_col));
-  HIPCALL(hipMalloc((void**)&h->cyc_cinv, sizeof(double) * m * m));
-  HIPCALL(hipMalloc((void**)&h->cyc_cap, sizeof(double) * (m * m + n)));
-  HIPCALL(hipMalloc((void**)&h->cyc_prev, sizeof(double) * m));
-  HIPCALL(hipMalloc((void**)&h->cyc_w, sizeof(double) * m));
-  HIPCALL(hipMemcpy(h->d_cyc_rows, rows, sizeof(int) * m, hipMemcpyHostToDevice));
-  h->n_cyc = n;
+  CHECK(alloc_cycles(h, n, rows, nullptr, nullptr));
   // the residual check of the corrected x is the CSR's (the sweeps' fused one is A_g's), so
   // neither the fused residual nor the fused step run
   h->fres_ok = false;
@@ -17532,22 +17415,7 @@ NX_API int nx_set_cycles_team(nx_network_t* h, int32_t K, const int32_t* own,
   free_cycles(h);
   h->sched_checked = false;
   if (K == 0) return NX_OK;
-  const int m = 2 * K;
-  HIPCALL(hipMalloc((void**)&h->d_cyc_rows, sizeof(int) * m));
-  HIPCALL(hipMalloc((void**)&h->d_cyc_qloc, sizeof(int) * K));
-  HIPCALL(hipMalloc((void**)&h->d_cyc_lcol, sizeof(int) * K));
-  HIPCALL(hipMalloc((void**)&h->cyc_z, sizeof(double) * m * h->n_col));
-  HIPCALL(hipMalloc((void**)&h->cyc_cinv, sizeof(double) * m * m));
-  HIPCALL(hipMalloc((void**)&h->cyc_cap, sizeof(double) * (m * m + K)));
-  HIPCALL(hipMalloc((void**)&h->cyc_prev, sizeof(double) * m));
-  HIPCALL(hipMalloc((void**)&h->cyc_w, sizeof(double) * m));
-  HIPCALL(hipMalloc((void**)&h->cyc_u, sizeof(double) * m));
-  HIPCALL(hipMemcpy(h->d_cyc_rows, own, sizeof(int) * m, hipMemcpyHostToDevice));
-  HIPCALL(hipMemcpy(h->d_cyc_qloc, qloc, sizeof(int) * K, hipMemcpyHostToDevice));
-  HIPCALL(hipMemcpy(h->d_cyc_lcol, lcol, sizeof(int) * K, hipMemcpyHostToDevice));
-  h->n_cyc = K;
-  h->cyc_team = true;
-  return NX_OK;
+  return alloc_cycles(h, K, own, qloc, lcol);
 }
 
 NX_API int nx_set_cell_mass(nx_network_t* h, double ratio, double mo_div) {

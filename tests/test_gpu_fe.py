@@ -234,7 +234,7 @@ def test_fe_direct_cycles(case, k):
     """A graph with cycles (the reference's edge-info graph, two lattices with 12 / 25
     cycles): the (k, 0) direct solve through the condensed system runs -- the auxiliary tree
     solve corrected by the Woodbury step of the cycle chains' dropped couplings, built from
-    the condensed mass (fe_cyc_build) -- within SOL_TOL of the oracle's LU, its reported
+    the condensed mass (cyc_build) -- within SOL_TOL of the oracle's LU, its reported
     residual the true one; new coefficients rebuild the correction."""
     from cases import CYCLIC
 
