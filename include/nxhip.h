@@ -314,8 +314,9 @@ int nx_set_cycles_team(nx_network_t* h, int32_t K, const int32_t* own, const int
  *   slot[e] = aux edge of h's edge e; v_fe / v_aux (E (N+1)) the vertex-flux rows, edge-major;
  *   i_fe (E N (k-1)) the interior-flux rows, cell-major; p_fe / p_aux (E N) pressure rows;
  *   l_fe / l_aux (n_lm) multiplier rows; cst = C (2 x (k-1)) | K ((k-1) x 2) | M_ii^{-1}
- *   ((k-1)^2), row-major; ab = a + b. aux = NULL detaches. With nx_set_solver(h, 1, 1),
- *   nx_solve condenses, solves on aux, expands, checks h's true residual and refines up to
+ *   ((k-1)^2) | the reference flux mass ((k+1)^2, node order along the cell; what
+ *   nx_fe_batch_gradient contracts with), row-major; ab = a + b. aux = NULL detaches.
+ *   With nx_set_solver(h, 1, 1), nx_solve condenses, solves on aux, expands, checks h's true residual and refines up to
  *   twice (iters = passes), MINRES when that still misses rtol. layout_fe.build_fe_aux_maps
  *   builds the maps. Replaces MUMPS' LU of the (k, 0) system (solver.py:58-65).
  *   Several ranks: h (n_ghost > 0) and aux (the rank's P1/DG0 handle with its halo, cut rows
@@ -647,6 +648,54 @@ int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
                       int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
                       const double* obs_d, double* value, double* grad_R, double* grad_bc,
                       double* grad_f, int32_t* iters, double* relres, int32_t* converged);
+
+/*
+ * nx_fe_batch_gradient: nx_batch_gradient for flux degree k >= 2 with DG0 pressure, on the
+ * (k, 0) handle's batched condensed solve (nx_fe_batch_solve's operator: condense, the
+ * auxiliary sweeps with their cycle correction, expand). The (k, 0) device matrix is symmetric
+ * too, so the adjoint is the same solve with k_b_obs's right-hand side. Objectives, arguments,
+ * outputs, status arrays (2 x n_cols: forward, then adjoint), the once-per-call adjoint column
+ * of kind 0 and the exact zeros of a zero right-hand side are nx_batch_gradient's; maxit caps
+ * the MINRES of a column's single-column fallback, as in nx_fe_batch_solve, whose per-column
+ * policy both passes follow. obs_rows are device rows of the (k, 0) handle: any flux node
+ * (vertex or interior), pressure or multiplier row. With mu = A^{-1} c and x the forward
+ * solution, per edge over its N cells c (length h_c; x_c, mu_c the cell's k + 1 flux node
+ * values, left vertex, interior, right vertex; M the (k+1) x (k+1) reference mass):
+ *   grad_R[j, e]     = -sum_c h_c mu_c^T M x_c     (-mu^T (dA/dR_e) x: A is affine in R and only
+ *                      its flux-flux block depends on it)
+ *   grad_f[j, e]     = sum_c (h_c v) mu[p_c], v the source term of the pressure row p_c in the
+ *                      rhs tables (DG0: v = -1, so -sum_c h_c mu[p_c])
+ *   grad_bc[j, e, .] = mu at the edge's first / last flux vertex row
+ * k_fe_b_edge_form forms them per (column, edge), addressing rows through nx_fe_set_direct's
+ * maps, in k_b_edge_form's lane shapes; M is part of the handle's constants (nx_fe_set_direct)
+ * and staged in LDS per workgroup. Fixed-order sums, no contraction: a column's bits do not
+ * depend on the other columns, its position, n_cols or the chunk size.
+ * Supported exactly where nx_fe_batch_supported says 1, else NX_ERR_STATE; NX_ERR_STATE too
+ * where the matrix has not been assembled for the resident coefficients. NX_ERR_ARG:
+ * nx_batch_gradient's cases, and maxit < 1. The workspace is nx_fe_batch_solve's with the
+ * gradient's part (two more vectors and 4 E + 1 outputs per (k, 0) column); a workspace that an
+ * earlier nx_fe_batch_solve allocated without it is allocated again with it, and keeps it.
+ * The first pass of a call writes the auxiliary lumped mass and makes the auxiliary cycle
+ * correction current (kind 0: the one adjoint column's pass, which runs before any forward
+ * pass). The handle's coefficients, rhs, x, tmp, published state and snapshots are left as
+ * they were. Not served: continuous pressure (m >= 1), Hessian-vector products, ensembles (a
+ * resistance field per scenario) and several ranks.
+ *
+ * Launches (nx_get_batch_info reports the call; refined: forward plus adjoint columns). Let P
+ * be the launches of one solve pass without rhs and gather -- condense, s sweeps, expand,
+ * residual, norms -- with s = 3 where the auxiliary decomposition has subtree jobs, else 1:
+ * P = s + 4, and s + 6 with cycles (the correction's two kernels). Steady, nothing refined:
+ *   kind 1   per chunk  1 (rhs) + P + 1 (k_b_obs) + P + 1 (k_fe_b_edge_form)
+ *   kind 0   per call   1 (k_b_obs) + P;  per chunk  1 + P + 1 + 1
+ * A refinement pass adds P, what it adds in nx_fe_batch_solve (7, 5 without jobs; 9, 7 with
+ * cycles). What the call had to make current is counted as there: 1 for a flushed
+ * assembly and the whole build of the cycle correction.
+ */
+int nx_fe_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                         const double* edge_f, const double* f_const, double rtol, int32_t maxit,
+                         int32_t kind, int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
+                         const double* obs_d, double* value, double* grad_R, double* grad_bc,
+                         double* grad_f, int32_t* iters, double* relres, int32_t* converged);
 
 /*
  * Ensembles: many resistance fields in one batched pass -- scenario j solves A(R_j) x_j = b_j,

@@ -65,6 +65,8 @@ _SIGS = {
     "nx_cp_batch_rhs": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd]),
     "nx_batch_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd, _pd,
                                     _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
+    "nx_fe_batch_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _i32, _pi32, _pd,
+                                       _pd, _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
     "nx_ensemble_supported": (C.c_int, [_h, _pi32]),
     "nx_ensemble_solve": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd, _f64, _i32, _pd, _pi32, _pd,
                                     _pi32]),
@@ -539,9 +541,20 @@ class Handle:
         distinct device rows; ``data`` None: the linear objective, else ``(B, n_obs)``."""
         return self._gradient_call(None, edge_bc, edge_f, f_const, rtol, rows, weights, data, True)
 
+    def fe_batch_gradient(self, edge_bc, edge_f=None, f_const=None, rtol: float = 1e-12,
+                          maxit: int = 50000, *, rows, weights, data=None):
+        """``nx_fe_batch_gradient``: :meth:`batch_gradient` for a (k, 0) handle with its
+        auxiliary handle attached (the same return tuple); ``rows``: distinct device rows of the
+        (k, 0) layout -- vertex or interior flux nodes, pressure or multiplier rows; ``maxit``
+        caps the MINRES of a column's single-column fallback. Not served: continuous pressure,
+        Hessian-vector products, ensembles (R per scenario), several ranks."""
+        return self._gradient_call(None, edge_bc, edge_f, f_const, rtol, rows, weights, data, True,
+                                   fe_maxit=int(maxit))
+
     def _gradient_call(self, edge_R, edge_bc, edge_f, f_const, rtol, rows, weights, data,
-                       derivatives):
-        """``nx_batch_gradient`` (``edge_R`` None) or ``nx_ensemble_gradient``."""
+                       derivatives, fe_maxit=None):
+        """``nx_batch_gradient`` (``edge_R`` None), ``nx_ensemble_gradient``, or
+        ``nx_fe_batch_gradient`` (``fe_maxit``: its ``maxit``, which follows ``rtol``)."""
         B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
         eR = None if edge_R is None else self._ensemble_R(edge_R, B)
         rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
@@ -568,7 +581,8 @@ class Handle:
         it = np.zeros((2, B), dtype=np.int32)
         rr = np.zeros((2, B), dtype=np.float64)
         cv = np.zeros((2, B), dtype=np.int32)
-        tail = (float(rtol), 0 if d is None else 1, int(rows.size), _ptr(rows, C.c_int32),
+        tail = (float(rtol),) + (() if fe_maxit is None else (fe_maxit,))
+        tail += (0 if d is None else 1, int(rows.size), _ptr(rows, C.c_int32),
                 _ptr(w, C.c_double), _ptr(d, C.c_double), _ptr(value, C.c_double),
                 _ptr(gR if derivatives else None, C.c_double), _ptr(gbc, C.c_double),
                 _ptr(gf, C.c_double), _ptr(it, C.c_int32), _ptr(rr, C.c_double),
@@ -576,6 +590,8 @@ class Handle:
         head = (self.ptr, B) + (() if eR is None else (_ptr(eR, C.c_double),))
         head += (_ptr(bc, C.c_double), _ptr(ef, C.c_double), _ptr(fc, C.c_double))
         fn = lib().nx_batch_gradient if eR is None else lib().nx_ensemble_gradient
+        if fe_maxit is not None:
+            fn = lib().nx_fe_batch_gradient
         check(fn(*head, *tail))
         if not derivatives:  # the objective alone: the forward solve's figures
             return value, None, None, None, it[:1].T.copy(), rr[:1].T.copy(), cv[:1].T.astype(bool)

@@ -35,7 +35,7 @@ import numpy as np
 from . import _lib
 from .comm import MIN, GroupRankComm
 from .fem import Constant, Function, FunctionSpace
-from .element import condensed_flux_mass, stable_pair
+from .element import condensed_flux_mass, element_tensors, stable_pair
 from .layout import (LocalProblem, build_local_problem, cycle_pairs_global, partition_edges,
                      team_cycle_tables)
 from .layout_fe import (FeLayout, build_cp_rank_tables, build_cp_tables, build_fe_aux_maps,
@@ -610,7 +610,9 @@ class HydraulicNetworkAssembler:
             aux.set_cell_mass(float(ratio), float(ratio + 1))
             aux.set_solver(True, True)  # (its sweeps invert an exact forest decomposition)
             maps = build_fe_aux_maps(fe, lp)
-            cst = np.concatenate([C.ravel(), K.ravel(), Mii.ravel()])
+            # (behind them the reference mass: nx_fe_batch_gradient's contraction)
+            cst = np.concatenate([C.ravel(), K.ravel(), Mii.ravel(),
+                                  element_tensors(k, 0)[0].ravel()])
             try:
                 self._handle.fe_set_direct(aux, k, fe_aux_slots(fe, lp), maps, cst, alpha + beta)
             except _lib.NxError:

@@ -14399,17 +14399,17 @@ int batch_zero_cols(nx_network* h, double* Xv, int64_t ld, int nc,
 }
 
 // One launch of an edge-kernel family on nc columns: a 16- or 32-lane segment per edge where N
-// allows it, a wave per edge otherwise.
+// allows it, a wave per edge otherwise. lds: the family's dynamic LDS per workgroup.
 template <class Args, void (*Seg16)(Args), void (*Seg32)(Args), void (*Wave)(Args)>
-int batch_edge_launch(nx_network* h, int nc, const Args& a) {
+int batch_edge_launch(nx_network* h, int nc, const Args& a, size_t lds = 0) {
   const int64_t E = h->E;
   constexpr int wpb = kBlock / 64;
   if (h->N < 16)
-    hipLaunchKernelGGL(Seg16, dim3(grid_of(E, wpb * 4), nc), dim3(kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(Seg16, dim3(grid_of(E, wpb * 4), nc), dim3(kBlock), lds, h->stream, a);
   else if (h->N < 32)
-    hipLaunchKernelGGL(Seg32, dim3(grid_of(E, wpb * 2), nc), dim3(kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(Seg32, dim3(grid_of(E, wpb * 2), nc), dim3(kBlock), lds, h->stream, a);
   else
-    hipLaunchKernelGGL(Wave, dim3(grid_of(E, wpb), nc), dim3(kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(Wave, dim3(grid_of(E, wpb), nc), dim3(kBlock), lds, h->stream, a);
   HIPCALL(hipGetLastError());
   h->b_launches += 1;
   return NX_OK;
@@ -14763,6 +14763,135 @@ __global__ __launch_bounds__(kBlock) void k_fe_b_expand(FeCond c, const double* 
   }
 }
 
+// k_fe_b_edge_form: k_b_edge_form for the (k, 0) device layout (nx_fe_batch_gradient), grid =
+// (edge blocks, columns), the same lane shapes (lane = cell) and output layout. The rows come
+// from the maps of nx_fe_set_direct (vfe, ife, pfe), the cell lengths from cellh, the
+// (k+1) x (k+1) reference mass M from the handle's constants (behind C | K | Mii), staged in
+// LDS per workgroup:
+//   gR[e]  = -sum_c h_c t_c,  t_c = sum_i l_i (sum_j M[i][j] x_j)
+//            (x, l the cell's k + 1 flux node values, left vertex, interior 1..k-1, right
+//            vertex: -l^T (dA/dR_e) x, only the flux-flux block depends on R),
+//   gf[e]  = sum_c g_c l[p_c],  g_c = sum over the source terms of row p_c of h_c v
+//            (the rhs tables k_fe_b_rhs evaluates: its (f h) v per unit f; DG0: v = -1),
+//   gbc[e] = l at the edge's first and last vertex row.
+// A lane loads its cell's k + 1 values of X once into its own LDS slots (node-major, so no
+// bank conflicts and no register array over k) and L once, in the order of the outer sum. Sums:
+// j inside i from 0.0, left to right, no contraction; then the segment butterfly / wave_sum,
+// chunks in order -- a column's bits do not depend on the other columns or the chunking.
+struct FeFormArgs {
+  FeCond c;
+  const int *b_ptr, *b_idx, *b_ent, *kind;  // the rhs gather tables (FeArgs)
+  const double* tval;
+  const double* X;
+  const double* L;
+  int64_t ld, l_ld;
+  double *gR, *gf, *gbc;
+};
+size_t fe_form_lds(int k) { return sizeof(double) * (size_t)(k + 1) * (size_t)(k + 1 + kBlock); }
+
+// The workgroup's copy of M (before any wave leaves: every thread of the block calls this).
+__device__ __forceinline__ void fe_form_stage(const FeFormArgs& a, double* sM) {
+  const int nq = a.c.km + 2;
+  const double* M = a.c.cst + 4 * a.c.km + a.c.km * a.c.km;
+  for (int i = threadIdx.x; i < nq * nq; i += kBlock) sM[i] = M[i];
+  __syncthreads();
+}
+
+// One cell's terms: tR = h_c t_c and tf = g_c l[p_c]. sx: this thread's LDS slots, stride kBlock.
+__device__ __forceinline__ void fe_form_cell(const FeFormArgs& a, const double* sM, double* sx,
+                                             const double* __restrict__ x,
+                                             const double* __restrict__ l, int64_t e, int cl,
+                                             double* tR, double* tf) {
+#pragma clang fp contract(off)
+  const int N = a.c.N, km = a.c.km, nq = km + 2;
+  const int64_t cell = e * N + cl;
+  const int* vr = a.c.vfe + e * (N + 1) + cl;
+  const int* ir = a.c.ife + cell * km;
+  const double h = a.c.cellh[cell];
+  sx[0] = x[vr[0]];
+  for (int j = 0; j < km; ++j) sx[(j + 1) * kBlock] = x[ir[j]];
+  sx[(km + 1) * kBlock] = x[vr[1]];
+  double t = 0.0;
+  for (int i = 0; i < nq; ++i) {
+    const double li = l[i == 0 ? vr[0] : i == km + 1 ? vr[1] : ir[i - 1]];
+    double s = 0.0;
+    for (int j = 0; j < nq; ++j) s += sM[i * nq + j] * sx[j * kBlock];
+    t += li * s;
+  }
+  *tR = h * t;
+  const int prow = a.c.pfe[cell];
+  double g = 0.0;
+  for (int p = a.b_ptr[prow]; p < a.b_ptr[prow + 1]; ++p) {
+    const int ent = a.b_ent[p];
+    if (a.kind[ent] == kFeSource) g += a.c.cellh[a.b_idx[p]] * a.tval[ent];
+  }
+  *tf = g * l[prow];
+}
+
+template <int S>
+__global__ __launch_bounds__(kBlock) void k_fe_b_edge_form_seg(FeFormArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ double fe_form_sm[];
+  const int nq = a.c.km + 2;
+  fe_form_stage(a, fe_form_sm);
+  double* sx = fe_form_sm + nq * nq + threadIdx.x;
+  constexpr int EPW = 64 / S;
+  const int lane = threadIdx.x & 63;
+  const int sub = lane / S, cl = lane % S;
+  const int64_t E = a.c.E;
+  const int64_t e0 = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * EPW;
+  if (e0 >= E) return;  // wave-uniform
+  const int ne = (int)min<int64_t>(EPW, E - e0);
+  const int64_t e = e0 + min(sub, ne - 1);  // idle segments shadow the last edge
+  const bool mine = sub < ne;
+  const int N = a.c.N;
+  const int col = blockIdx.y;
+  const double* x = a.X + col * a.ld;
+  const double* l = a.L + col * a.l_ld;
+  double tR = 0.0, tf = 0.0;
+  if (mine && cl < N) fe_form_cell(a, fe_form_sm, sx, x, l, e, cl, &tR, &tf);
+#pragma unroll
+  for (int o = S / 2; o > 0; o >>= 1) {
+    tR += __shfl_xor(tR, o, 64);
+    tf += __shfl_xor(tf, o, 64);
+  }
+  if (mine && cl == 0) {
+    a.gR[col * E + e] = -tR;
+    a.gf[col * E + e] = tf;
+    a.gbc[(col * E + e) * 2] = l[a.c.vfe[e * (N + 1)]];
+    a.gbc[(col * E + e) * 2 + 1] = l[a.c.vfe[e * (N + 1) + N]];
+  }
+}
+
+// N >= 32: one wave per edge, the cells in chunks of 64 taken in order.
+__global__ __launch_bounds__(kBlock) void k_fe_b_edge_form(FeFormArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ double fe_form_sm[];
+  const int nq = a.c.km + 2;
+  fe_form_stage(a, fe_form_sm);
+  double* sx = fe_form_sm + nq * nq + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const int64_t E = a.c.E;
+  const int64_t e = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (e >= E) return;  // wave-uniform
+  const int N = a.c.N;
+  const int col = blockIdx.y;
+  const double* x = a.X + col * a.ld;
+  const double* l = a.L + col * a.l_ld;
+  double accR = 0.0, accf = 0.0;
+  for (int c0 = 0; c0 < N; c0 += 64) {
+    double tR = 0.0, tf = 0.0;
+    if (c0 + lane < N) fe_form_cell(a, fe_form_sm, sx, x, l, e, c0 + lane, &tR, &tf);
+    accR += wave_sum(tR);
+    accf += wave_sum(tf);
+  }
+  if (lane == 0) {
+    a.gR[col * E + e] = -accR;
+    a.gf[col * E + e] = accf;
+    a.gbc[(col * E + e) * 2] = l[a.c.vfe[e * (N + 1)]];
+    a.gbc[(col * E + e) * 2 + 1] = l[a.c.vfe[e * (N + 1) + N]];
+  }
+}
 
 // The auxiliary handle can serve batched columns: batch_ok's conditions but for cond_mass
 // (direct_local refuses an auxiliary handle: its CSR is not the system its sweeps invert,
@@ -14799,16 +14928,20 @@ FeAuxWs fe_aux_layout(const nx_network* a, int cap, void* base) {
 size_t fe_aux_bytes(const nx_network* a, int cap) { return fe_aux_layout(a, cap, nullptr).bytes; }
 // (the allocated bytes are checked, as in batch_fits: the auxiliary decomposition's slots and
 // cycle chains may have changed since the allocation)
-bool fe_batch_fits(const nx_network* h, int cap) {
-  return batch_fits(h, cap, BatchParts{}) && h->fe_bws != nullptr && cap <= h->fe_bws_cap &&
+bool fe_batch_fits(const nx_network* h, int cap, BatchParts parts) {
+  return batch_fits(h, cap, parts) && h->fe_bws != nullptr && cap <= h->fe_bws_cap &&
          fe_aux_bytes(h->fe_aux, h->fe_bws_cap) <= h->fe_bws_bytes &&
          h->fe_bws_cap == h->bws_cap;
 }
 
 // batch_workspace for the two parts together (batch_chunk_rule: the chunk's two parts fit the
-// share of the free memory; a failed allocation of either part halves it).
-int fe_batch_workspace(nx_network* h, int n_cols, int* chunk_out) {
+// share of the free memory; a failed allocation of either part halves it). ask: what the call
+// needs beside what the workspace already carries (nx_fe_batch_gradient: kGrad, behind the
+// solve's fields on the (k, 0) side; the auxiliary part has no such fields) -- a workspace that
+// lacks a part is released and allocated again with it, and keeps it for the calls after.
+int fe_batch_workspace(nx_network* h, int n_cols, int* chunk_out, BatchParts ask = BatchParts{}) {
   const nx_network* a = h->fe_aux;
+  const BatchParts parts = ask | h->bws_parts;
   auto release = [&]() {
     batch_free(h);
     if (h->fe_bws) (void)hipFree(h->fe_bws);
@@ -14817,7 +14950,7 @@ int fe_batch_workspace(nx_network* h, int n_cols, int* chunk_out) {
     h->fe_bws_bytes = 0;
   };
   auto alloc = [&](int cap) {
-    if (!batch_alloc(h, cap, BatchParts{})) return false;
+    if (!batch_alloc(h, cap, parts)) return false;
     const size_t bytes = fe_aux_bytes(a, cap);
     if (hipMalloc(&h->fe_bws, bytes) != hipSuccess) {
       h->fe_bws = nullptr;
@@ -14829,8 +14962,8 @@ int fe_batch_workspace(nx_network* h, int n_cols, int* chunk_out) {
     return true;
   };
   return batch_chunk_rule(
-      h, n_cols, false, "nx_fe_batch_solve", [&](int cap) { return fe_batch_fits(h, cap); },
-      [&](int cap) { return batch_bytes(h, cap, BatchParts{}) + fe_aux_bytes(a, cap); }, release,
+      h, n_cols, false, "nx_fe_batch_solve", [&](int cap) { return fe_batch_fits(h, cap, parts); },
+      [&](int cap) { return batch_bytes(h, cap, parts) + fe_aux_bytes(a, cap); }, release,
       alloc, chunk_out);
 }
 
@@ -15795,10 +15928,20 @@ struct AdjointRun {
   int32_t a_it = 1, a_cv = 1;
   double a_rr = 0.0;
   std::vector<double> stats;
-  // Xv = A^{-1} Bv on nc columns by the per-column policy; b = 0: x = 0 exactly
-  int solve(int nc, const double* Bv, double* Xv, BatchStatus st) {
-    CHECK(batch_solve_p1(h, ws, nc, Bv, Xv, rtol, st, stats, ens ? &be : nullptr));
+  // Xv = A^{-1} Bv on nc columns by the per-column policy; b = 0: x = 0 exactly. The policy
+  // with its operator is the caller's: pass(nc, Bv, Xv, st, stats) -- batch_solve_cols with the
+  // handle's sweeps (solve) or with another operator (nx_fe_batch_gradient: fe_batch_apply).
+  template <class Pass>
+  int solve_by(int nc, const double* Bv, double* Xv, BatchStatus st, Pass pass) {
+    CHECK(pass(nc, Bv, Xv, st, stats));
     return batch_zero_cols(h, Xv, ws.cols.ld, nc, stats);
+  }
+  int solve(int nc, const double* Bv, double* Xv, BatchStatus st) {
+    return solve_by(nc, Bv, Xv, st,
+                    [&](int ncs, const double* Bs, double* Xs, BatchStatus s,
+                        std::vector<double>& stt) {
+                      return batch_solve_p1(h, ws, ncs, Bs, Xs, rtol, s, stt, ens ? &be : nullptr);
+                    });
   }
   // k_b_obs on nc columns of X: the objective into J and / or the adjoint's right-hand side
   // into C (either may be null; C: one block per slice of rows)
@@ -16063,6 +16206,109 @@ NX_API int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge
   return batch_gradient_run(h, n_cols, nullptr, edge_bc, edge_f, f_const, rtol, kind, n_obs,
                             obs_rows, obs_w, obs_d, value, grad_R, grad_bc, grad_f, iters, relres,
                             converged);
+}
+
+// ---- nx_fe_batch_gradient: nx_batch_gradient on a (k, 0) handle. The device
+// matrix is symmetric, so the adjoint is the forward solve with k_b_obs's right-hand side;
+// both go through batch_solve_cols with fe_batch_apply as operator, as nx_fe_batch_solve.
+namespace {
+
+int fe_batch_edge_form(nx_network* h, const BatchWs& ws, int nc, int64_t l_ld) {
+  const FeFormArgs fa{fe_cond_of(h), h->fe_bptr, h->fe_bidx, h->fe_bent, h->fe_kind, h->fe_tval,
+                      ws.X, ws.L, ws.cols.ld, l_ld, ws.gR, ws.gf, ws.gbc};
+  return batch_edge_launch<FeFormArgs, k_fe_b_edge_form_seg<16>, k_fe_b_edge_form_seg<32>,
+                           k_fe_b_edge_form>(h, nc, fa, fe_form_lds(h->fe_k));
+}
+
+}  // namespace
+
+NX_API int nx_fe_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                                const double* edge_f, const double* f_const, double rtol,
+                                int32_t maxit, int32_t kind, int32_t n_obs,
+                                const int32_t* obs_rows, const double* obs_w, const double* obs_d,
+                                double* value, double* grad_R, double* grad_bc, double* grad_f,
+                                int32_t* iters, double* relres, int32_t* converged) {
+  const int made_current = batch_pending(h);
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  CHECK(batch_adjoint_args(h, n_cols, edge_bc && value && grad_R,
+                           "edge_bc / value / grad_R is NULL", kind, n_obs, obs_rows, obs_w,
+                           obs_d));
+  if (maxit < 1) return fail(NX_ERR_ARG, "maxit must be >= 1");
+  CHECK(fe_batch_state(h, "nx_fe_batch_gradient"));
+  if (!h->have_lhs || h->asm_coef_version != h->coef_version)
+    return fail(NX_ERR_STATE, "nx_fe_batch_gradient: assemble the matrix for the resident "
+                              "coefficients first");
+  CHECK(batch_obs_rows_check(h->n_own, n_obs, obs_rows));
+  CHECK(set_device(h));
+  nx_network* a = h->fe_aux;
+  const bool apend = a->pend_lhs || a->pend_rhs;
+  CHECK(flush_assembly(a));
+  if (apend) {  // (the auxiliary handle's own assembly ran on its stream)
+    HIPCALL(hipEventRecord(h->fe_ev[1], a->stream));
+    HIPCALL(hipStreamWaitEvent(h->stream, h->fe_ev[1], 0));
+  }
+  h->b_refined = h->b_fallback = 0;
+  h->b_launches = made_current;
+  AdjointRun r;
+  CHECK(fe_batch_workspace(h, n_cols, &r.chunk, BatchParts{BatchParts::kGrad}));
+  h->b_chunk = r.chunk;
+  r.h = h;
+  r.rtol = rtol;
+  r.n_obs = n_obs;
+  r.ws = batch_carve(h);
+  r.ens = false;
+  r.be = BatchEns{};
+  r.one_adj = kind == 0;
+  const BatchWs& ws = r.ws;
+  const FeAuxWs wa = fe_aux_layout(h->fe_aux, h->fe_bws_cap, h->fe_bws);
+  CHECK(batch_obs_upload(h, n_obs, r.chunk, obs_rows, obs_w, &r.od));
+  // Make-current: the auxiliary lumped mass and cycle correction depend on the resident R
+  // alone, not on the column, and fe_batch_apply writes / builds them in the pass that carries
+  // dq = true. `first` hands that to whichever pass the call runs first -- the one adjoint
+  // column of the linear objective (solved before any forward pass), else chunk 0's forward
+  // pass -- and every later pass, its refinements included, finds them current.
+  bool first = true;
+  auto pass = [&](int nc, const double* Bv, double* Xv, BatchStatus st,
+                  std::vector<double>& stats) {
+    return batch_solve_cols(
+        h, ws, nc, Bv, Xv, rtol, st, stats,
+        [&](int ncs) {
+          const bool dq = first;
+          first = false;
+          return fe_batch_apply(h, ws, wa, nullptr, ncs, Bv, Xv, 0, dq);
+        },
+        [&](const int* list, int nr) {
+          return fe_batch_apply(h, ws, wa, list, nr, ws.R, Xv, 1, false);
+        },
+        BatchFallback{BatchFallback::kKeep, maxit});
+  };
+  if (r.one_adj) {
+    CHECK(r.observe(1, nullptr, 0, ws.C, nullptr));
+    CHECK(r.solve_by(1, ws.C, ws.L, BatchStatus{&r.a_it, &r.a_rr, &r.a_cv}, pass));
+  }
+  const BatchStatus st{iters, relres, converged};
+  const int64_t E = h->E, ld = ws.cols.ld;
+  for (int c0 = 0; c0 < n_cols; c0 += r.chunk) {
+    const int nc = std::min(r.chunk, n_cols - c0);
+    CHECK(fe_batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
+    CHECK(r.solve_by(nc, ws.B, ws.X, st.at(c0), pass));
+    const BatchStatus adj = st.at((int64_t)n_cols + c0);
+    if (!r.one_adj) {
+      CHECK(r.upload_data(obs_d, c0, nc));
+      CHECK(r.observe(nc, ws.X, 1, ws.C, ws.gJ));
+      CHECK(r.solve_by(nc, ws.C, ws.L, adj, pass));
+    } else {
+      CHECK(r.observe(nc, ws.X, 0, nullptr, ws.gJ));
+      for (int c = 0; c < nc; ++c) adj.set(c, r.a_it, r.a_rr, r.a_cv);
+    }
+    CHECK(fe_batch_edge_form(h, ws, nc, r.one_adj ? 0 : ld));
+    HIPCALL(r.out(value, ws.gJ, 1, c0, nc));
+    HIPCALL(r.out(grad_R, ws.gR, E, c0, nc));
+    HIPCALL(r.out(grad_f, ws.gf, E, c0, nc));
+    HIPCALL(r.out(grad_bc, ws.gbc, 2 * E, c0, nc));
+    HIPCALL(hipStreamSynchronize(h->stream));
+  }
+  return NX_OK;
 }
 
 // ---- ensembles: a resistance field per scenario ---------------------------
@@ -17917,7 +18163,8 @@ NX_API int nx_fe_set_direct(nx_network_t* h, nx_network_t* aux, int32_t k, int64
       (rc = upload(&h->fe_paux, p_aux, np, h->stream)) ||
       (rc = upload(&h->fe_lfe, l_fe, n_lm, h->stream)) ||
       (rc = upload(&h->fe_laux, l_aux, n_lm, h->stream)) ||
-      (rc = upload(&h->fe_cst, cst, 4 * km + km * km, h->stream)))
+      // (C | K | Mii, then the reference mass that k_fe_b_edge_form contracts with)
+      (rc = upload(&h->fe_cst, cst, 4 * km + km * km + (km + 2) * (km + 2), h->stream)))
     return rc;
   for (auto& e : h->fe_ev)
     if (!e) HIPCALL(hipEventCreateWithFlags(&e, hipEventDisableTiming));

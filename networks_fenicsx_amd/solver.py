@@ -213,7 +213,9 @@ class Solver:
             condensation, the auxiliary tree sweeps and the expansion with a column dimension).
             ``None`` reads ``NXHIP_FE_BATCH`` (``"1"`` on; off when unset). Off, these degrees
             take the per-scenario loop, whose columns are bit-equal to single solves; the
-            batched columns agree with them to rounding.
+            batched columns agree with them to rounding. The option
+            also lets :meth:`gradient` serve these degrees (``nx_fe_batch_gradient``, DESIGN.md
+            section 3k); off, it raises ``NotImplementedError`` there.
         batch_continuous: let :meth:`solve_many` (and ``terminal_conductance``) take the
             batched path for continuous pressure (k > m >= 1) on a forest
             (``nx_cp_batch_solve``: the node-condensed direct solve factored once per call,
@@ -526,6 +528,13 @@ class Solver:
         raises ``NotImplementedError`` (there is no host fallback). The reference has no
         counterpart.
 
+        With ``batch_degrees`` it also serves flux degree k >= 2 with DG0 pressure where
+        ``nx_fe_batch_supported`` holds (``nx_fe_batch_gradient``: both solves through the
+        batched condensed solve, the contraction with the degree-k element mass); ``rows`` then
+        index the (k, 0) system's block order, interior flux nodes included. Not served on
+        these degrees: ``R=`` (ensembles), :meth:`hessian_vector`, continuous pressure
+        (m >= 1) and several ranks -- ``NotImplementedError``, as without the option.
+
         ``R`` (``(B, num_edges)`` or ``(B,)`` constants, as :meth:`solve_ensemble`): scenario j
         is evaluated at ``R[j]`` instead of the last ``compute_forms``' R
         (``nx_ensemble_gradient``; a forest, or a graph with cycles under
@@ -541,7 +550,7 @@ class Solver:
             raise RuntimeError("compute_forms() must be called before gradient()")
         if R is None and not derivatives:
             raise NotImplementedError("derivatives=False needs R (the ensemble call)")
-        self._adjoint_supported("gradient")
+        fe = self._adjoint_supported("gradient", ensemble=R is not None)
         if R is None:
             edge_R = None
             edge_bc, edge_f, f_const = asm.scenario_coefficients(p_bc, f)
@@ -550,8 +559,12 @@ class Solver:
         B = edge_bc.shape[0]
         h = asm.handle
         rows, w, data = self._observations(rows, weights, data, B)
-        dev_rows = self._adjoint_ready("gradient", rows, edge_R is not None)
-        if edge_R is not None:
+        dev_rows = self._adjoint_ready("gradient", rows, edge_R is not None, fe)
+        if fe:
+            value, gR, gbc, gf, it, rr, conv = h.fe_batch_gradient(
+                edge_bc, edge_f, f_const, self._rtol, self._maxit, rows=dev_rows, weights=w,
+                data=data)
+        elif edge_R is not None:
             value, gR, gbc, gf, it, rr, conv = h.ensemble_gradient(
                 edge_R, edge_bc, edge_f, f_const, self._rtol, rows=dev_rows, weights=w,
                 data=data, derivatives=derivatives)
@@ -581,14 +594,26 @@ class Solver:
                 f"{rr[bad].tolist()} > rtol {self._rtol:.1e})")
         return res
 
-    def _adjoint_supported(self, what: str) -> None:
-        """The options under which :meth:`gradient` and :meth:`hessian_vector` run."""
+    def _adjoint_supported(self, what: str, ensemble: bool = False) -> bool:
+        """The options under which :meth:`gradient` and :meth:`hessian_vector` run. True: the
+        call is :meth:`gradient` on degrees (k, 0), k >= 2, under ``batch_degrees``
+        (``nx_fe_batch_gradient``)."""
         asm = self.assembler
         if getattr(asm, "_nranks", 1) > 1:
             raise NotImplementedError(f"{what} runs on one rank")
-        if tuple(asm.degrees) != (1, 0):
+        deg = tuple(asm.degrees)
+        k0 = len(deg) == 2 and deg[0] >= 2 and deg[1] == 0
+        fe = k0 and what == "gradient" and self._fe_batch
+        if deg != (1, 0) and not fe:
+            hint = ""
+            if k0 and what == "gradient":
+                hint = ("; Solver(..., batch_degrees=True) (or NXHIP_FE_BATCH=1) serves gradient "
+                        "on flux degree k >= 2 with DG0 pressure")
             raise NotImplementedError(
-                f"{what} needs the P1/DG0 discretisation, not degrees {tuple(asm.degrees)}")
+                f"{what} needs the P1/DG0 discretisation, not degrees {deg}{hint}")
+        if fe and ensemble:
+            raise NotImplementedError(
+                f"{what}(R=...): the ensemble route serves P1/DG0 only, not degrees {deg}")
         if not self._direct:
             raise NotImplementedError(f"{what} needs the direct solve (ksp_type='preonly'), "
                                       "not MINRES")
@@ -597,6 +622,7 @@ class Solver:
         if not self._pc_exact:
             raise NotImplementedError(f"{what} needs the consistent mass (pc_mass='lumped' "
                                       "is not exact)")
+        return fe
 
     def _observations(self, rows, weights, data, B: int):
         """The observed rows, weights and data of B scenarios, checked and normalised."""
@@ -619,14 +645,19 @@ class Solver:
                 raise ValueError(f"data must be ({B}, {rows.size}) or ({rows.size},)")
         return rows, w, data
 
-    def _adjoint_ready(self, what: str, rows, ensemble: bool) -> np.ndarray:
-        """The handle configured, its matrix current and the batched path checked; returns the
-        observed rows as device rows."""
+    def _adjoint_ready(self, what: str, rows, ensemble: bool, fe: bool = False) -> np.ndarray:
+        """The handle configured, its matrix current and the batched path checked (``fe``: the
+        (k, 0) one); returns the observed rows as device rows."""
         asm = self.assembler
         h = asm.handle
         self._configure()
         if not asm.lhs_current:  # the matrix of the last compute_forms (its R), values only
             asm.assemble(assemble_lhs=True, assemble_rhs=False)
+        if fe:
+            if not h.fe_batch_supported():
+                raise NotImplementedError(f"{what}: the batched condensed solve does not apply "
+                                          "to this handle (nx_fe_batch_supported)")
+            return asm.block_order_rows()[rows]
         if not h.batch_supported():
             raise NotImplementedError(f"{what}: the batched direct solve does not apply to this "
                                       "handle (nx_batch_supported)")
