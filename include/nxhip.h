@@ -341,7 +341,10 @@ int nx_fe_set_direct(nx_network_t* h, nx_network_t* aux, int32_t k, int64_t n_lm
  * (negative definite, 2 unknowns per node) is eliminated leaf to root by one workgroup;
  * then every edge back-substitutes. The true residual comes from the CSR, with up to two
  * refinement passes; nx_get_direct_path reports 4.
- *   nI = (k-1)+(m-1); cst = Kh (16) | Ch (4 nI) | Eh (4 nI) | Fh (nI nI); tI[nI] (+1 flux,
+ *   nI = (k-1)+(m-1); cst = Kh (16) | Ch (4 nI) | Eh (4 nI) | Fh (nI nI) | the reference flux
+ *   mass ((k+1)^2, node order along the cell, row-major) | the m + 1 source weights of a cell's
+ *   pressure rows per unit f h, the layout's sign included (the last two are what
+ *   nx_cp_batch_gradient contracts with); tI[nI] (+1 flux,
  *   -1 pressure interior node); n_nodes border nodes, nrow[2n] (pressure row, multiplier row
  *   or -1); eb[4E] (source node, target node, the q_0 - lam_source and q_N - lam_target
  *   couplings: 0 or +-1); the node forest: n_lev levels (lev_off, order), every node's
@@ -678,8 +681,8 @@ int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
  * The first pass of a call writes the auxiliary lumped mass and makes the auxiliary cycle
  * correction current (kind 0: the one adjoint column's pass, which runs before any forward
  * pass). The handle's coefficients, rhs, x, tmp, published state and snapshots are left as
- * they were. Not served: continuous pressure (m >= 1), Hessian-vector products, ensembles (a
- * resistance field per scenario) and several ranks.
+ * they were. Not served: Hessian-vector products, ensembles (a resistance field per scenario)
+ * and several ranks; continuous pressure (m >= 1) has its own entry, nx_cp_batch_gradient.
  *
  * Launches (nx_get_batch_info reports the call; refined: forward plus adjoint columns). Let P
  * be the launches of one solve pass without rhs and gather -- condense, s sweeps, expand,
@@ -692,6 +695,57 @@ int nx_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
  * assembly and the whole build of the cycle correction.
  */
 int nx_fe_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                         const double* edge_f, const double* f_const, double rtol, int32_t maxit,
+                         int32_t kind, int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
+                         const double* obs_d, double* value, double* grad_R, double* grad_bc,
+                         double* grad_f, int32_t* iters, double* relres, int32_t* converged);
+
+/*
+ * nx_cp_batch_gradient: nx_batch_gradient for continuous pressure (k > m >= 1) on a forest, on
+ * the handle's batched node-condensed solve (nx_cp_batch_solve's factor stage and operator).
+ * The device matrix of every general-degree layout is symmetric (pressure rows negated), so the
+ * adjoint is the same solve with k_b_obs's right-hand side. Objectives, arguments, outputs,
+ * status arrays (2 x n_cols: forward, then adjoint), the once-per-call adjoint column of kind 0
+ * and the exact zeros of a zero right-hand side are nx_batch_gradient's; maxit caps the MINRES
+ * of a column's single-column fallback, as in nx_cp_batch_solve, whose per-column policy both
+ * passes follow. obs_rows are device rows of the (k, m) handle: any flux node, edge-interior
+ * pressure node, node pressure or multiplier row. With mu = A^{-1} c and x the forward
+ * solution, per edge over its N cells c (length h_c):
+ *   grad_R[j, e]     = -sum_c h_c mu_c^T M x_c   (x_c, mu_c the cell's k + 1 flux node values,
+ *                      local rows k c .. k c + k; M the (k+1) x (k+1) reference mass: A is
+ *                      affine in R and only its flux-flux block depends on it)
+ *   grad_f[j, e]     = sum_c h_c sum_{i=0..m} s_i mu[p_{c,i}]   (p_{c,i} the cell's m + 1 pressure
+ *                      rows, the first of cell 0 and the last of cell N - 1 being the node rows
+ *                      of the edge's end nodes -- a node row shared by several edges counts this
+ *                      edge's cells only; s_i what k_fe_b_rhs puts into that row per unit f h_c)
+ *   grad_bc[j, e, .] = mu at the edge's first / last flux row (local rows 0 and k N)
+ * k_cp_b_edge_form forms them per (column, edge) in k_b_edge_form's lane shapes; the rows are in
+ * closed form (edge e's block starts at e ((k + m) N), flux node j is local row j, interior
+ * pressure node j local row k N + j, the end nodes' pressure rows nrow[2 u] / nrow[2 v]); M and
+ * s are part of the handle's constants (nx_fe_set_cp, behind Fh) and staged in LDS per
+ * workgroup. Fixed-order sums, no contraction: a column's bits do not depend on the other
+ * columns, its position, n_cols or the chunk size.
+ * Supported exactly where nx_cp_batch_supported says 1, else NX_ERR_STATE; NX_ERR_STATE too
+ * where the matrix has not been assembled for the resident coefficients. NX_ERR_ARG:
+ * nx_batch_gradient's cases, and maxit < 1. Once per call the factor stage of nx_cp_batch_solve
+ * runs (it depends on the resident R alone) and serves the forward pass, the adjoint pass and
+ * their refinements; kind 0 then solves its one adjoint column, before any forward pass. The
+ * workspace is nx_cp_batch_solve's with the gradient's part (two more vectors and 4 E + 1
+ * outputs per column); a workspace that an earlier nx_cp_batch_solve allocated without it is
+ * allocated again with it, and keeps it. The handle's own factors, coefficients, rhs, x, tmp,
+ * published state and snapshots are left as they were. Not served: Hessian-vector products,
+ * ensembles (a resistance field per scenario), graphs with cycles and several ranks.
+ *
+ * Launches (nx_get_batch_info reports the call; refined: forward plus adjoint columns). With
+ * U / D the launches of the node forest's up / down pass (nx_cp_batch_solve), the factor stage
+ * is F = 1 + U and one solve pass without rhs and gather -- forward, up, down, back, residual,
+ * norms -- is P = 4 + U + D. Steady, nothing refined:
+ *   kind 1   per chunk  1 (rhs) + P + 1 (k_b_obs) + P + 1 (k_cp_b_edge_form)
+ *   kind 0   per call   F + 1 (k_b_obs) + P;  per chunk  1 + P + 1 + 1
+ *   kind 1   per call   F
+ * A refinement pass adds P; a flushed assembly adds 1.
+ */
+int nx_cp_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
                          const double* edge_f, const double* f_const, double rtol, int32_t maxit,
                          int32_t kind, int32_t n_obs, const int32_t* obs_rows, const double* obs_w,
                          const double* obs_d, double* value, double* grad_R, double* grad_bc,

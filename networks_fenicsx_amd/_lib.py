@@ -67,6 +67,8 @@ _SIGS = {
                                     _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
     "nx_fe_batch_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _i32, _pi32, _pd,
                                        _pd, _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
+    "nx_cp_batch_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _i32, _pi32, _pd,
+                                       _pd, _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
     "nx_ensemble_supported": (C.c_int, [_h, _pi32]),
     "nx_ensemble_solve": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd, _f64, _i32, _pd, _pi32, _pd,
                                     _pi32]),
@@ -546,15 +548,28 @@ class Handle:
         """``nx_fe_batch_gradient``: :meth:`batch_gradient` for a (k, 0) handle with its
         auxiliary handle attached (the same return tuple); ``rows``: distinct device rows of the
         (k, 0) layout -- vertex or interior flux nodes, pressure or multiplier rows; ``maxit``
-        caps the MINRES of a column's single-column fallback. Not served: continuous pressure,
-        Hessian-vector products, ensembles (R per scenario), several ranks."""
+        caps the MINRES of a column's single-column fallback. Not served: Hessian-vector
+        products, ensembles (R per scenario), several ranks; continuous pressure is
+        :meth:`cp_batch_gradient`'s."""
         return self._gradient_call(None, edge_bc, edge_f, f_const, rtol, rows, weights, data, True,
                                    fe_maxit=int(maxit))
 
+    def cp_batch_gradient(self, edge_bc, edge_f=None, f_const=None, rtol: float = 1e-12,
+                          maxit: int = 50000, *, rows, weights, data=None):
+        """``nx_cp_batch_gradient``: :meth:`batch_gradient` for a continuous-pressure handle
+        (k > m >= 1) with its node-condensed solve attached, on a forest (the same return
+        tuple); ``rows``: distinct device rows of the (k, m) layout -- flux nodes,
+        edge-interior pressure nodes, node pressures or multiplier rows; ``maxit`` caps the
+        MINRES of a column's single-column fallback. Not served: Hessian-vector products,
+        ensembles (R per scenario), graphs with cycles, several ranks."""
+        return self._gradient_call(None, edge_bc, edge_f, f_const, rtol, rows, weights, data, True,
+                                   fe_maxit=int(maxit), entry="nx_cp_batch_gradient")
+
     def _gradient_call(self, edge_R, edge_bc, edge_f, f_const, rtol, rows, weights, data,
-                       derivatives, fe_maxit=None):
-        """``nx_batch_gradient`` (``edge_R`` None), ``nx_ensemble_gradient``, or
-        ``nx_fe_batch_gradient`` (``fe_maxit``: its ``maxit``, which follows ``rtol``)."""
+                       derivatives, fe_maxit=None, entry="nx_fe_batch_gradient"):
+        """``nx_batch_gradient`` (``edge_R`` None), ``nx_ensemble_gradient``, or a
+        general-degree ``entry`` -- ``nx_fe_batch_gradient`` / ``nx_cp_batch_gradient``
+        (``fe_maxit``: its ``maxit``, which follows ``rtol``)."""
         B, bc, ef, fc = self._batch_inputs(edge_bc, edge_f, f_const)
         eR = None if edge_R is None else self._ensemble_R(edge_R, B)
         rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
@@ -591,7 +606,7 @@ class Handle:
         head += (_ptr(bc, C.c_double), _ptr(ef, C.c_double), _ptr(fc, C.c_double))
         fn = lib().nx_batch_gradient if eR is None else lib().nx_ensemble_gradient
         if fe_maxit is not None:
-            fn = lib().nx_fe_batch_gradient
+            fn = getattr(lib(), entry)
         check(fn(*head, *tail))
         if not derivatives:  # the objective alone: the forward solve's figures
             return value, None, None, None, it[:1].T.copy(), rr[:1].T.copy(), cv[:1].T.astype(bool)

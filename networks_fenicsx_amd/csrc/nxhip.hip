@@ -15668,6 +15668,146 @@ __global__ __launch_bounds__(64) void k_cp_b_back(CpBatch p, const int* __restri
   }
 }
 
+// k_cp_b_edge_form: k_b_edge_form / k_fe_b_edge_form for the continuous-pressure layout
+// (nx_cp_batch_gradient), grid = (edge blocks, columns), the same lane shapes (lane = cell) and
+// output layout. The rows are in closed form (k_cp_b_back's): edge e's block starts at e per,
+// per = (k N + 1) + (m N - 1); flux node j along the edge is local row j, interior pressure
+// node j (1 <= j <= m N - 1) local row k N + j, the pressure at the end nodes u / v row
+// nrow[2 u] / nrow[2 v]. The (k+1) x (k+1) reference mass M and the m + 1 source weights s
+// (what k_fe_b_rhs puts into a cell's pressure rows per unit f h: the rhs tables' source
+// entries, sign included) sit behind Fh in the handle's constants, staged in LDS per workgroup:
+//   gR[e]  = -sum_c h_c t_c,  t_c = sum_i l_i (sum_j M[i][j] x_j)
+//            (x, l the cell's k + 1 flux node values, local rows k c .. k c + k),
+//   gf[e]  = sum_c h_c g_c,   g_c = sum_i s_i l[p_{c,i}]  (p_{c,i}: the cell's m + 1 pressure
+//            rows; the first of cell 0 and the last of cell N - 1 are the node rows of u and v,
+//            so a node row shared by several edges counts this edge's cells only),
+//   gbc[e] = l at the edge's first and last flux row (local rows 0 and k N).
+// A lane loads its cell's k + 1 values of X once into its own LDS slots (node-major: no bank
+// conflicts, no register array over k). Sums: j inside i from 0.0, left to right, no
+// contraction; then the segment butterfly / wave_sum, chunks in order -- a column's bits do not
+// depend on the other columns or the chunking.
+struct CpFormArgs {
+  int N, k, m;
+  int64_t E;
+  const double* cellh;
+  const double* Ms;  // M ((k+1)^2) | s (m + 1)
+  const int *eb, *nrow;
+  const double* X;
+  const double* L;
+  int64_t ld, l_ld;
+  double *gR, *gf, *gbc;
+};
+size_t cp_form_lds(int k, int m) {
+  return sizeof(double) * ((size_t)(k + 1) * (size_t)(k + 1 + kBlock) + (size_t)(m + 1));
+}
+
+// The workgroup's copy of M | s (before any wave leaves: every thread of the block calls this).
+__device__ __forceinline__ void cp_form_stage(const CpFormArgs& a, double* sM) {
+  const int n = (a.k + 1) * (a.k + 1) + a.m + 1;
+  for (int i = threadIdx.x; i < n; i += kBlock) sM[i] = a.Ms[i];
+  __syncthreads();
+}
+
+// One cell's terms: tR = h_c t_c and tf = h_c g_c. sx: this thread's LDS slots, stride kBlock.
+__device__ __forceinline__ void cp_form_cell(const CpFormArgs& a, const double* sM, double* sx,
+                                             const double* __restrict__ x,
+                                             const double* __restrict__ l, int64_t e, int cl,
+                                             double* tR, double* tf) {
+#pragma clang fp contract(off)
+  const int N = a.N, k = a.k, m = a.m, nq = k + 1;
+  const int nf = k * N + 1, per = nf + m * N - 1;
+  const int64_t base = e * (int64_t)per;
+  const double h = a.cellh[e * N + cl];
+  const double* xq = x + base + k * cl;
+  const double* lq = l + base + k * cl;
+  for (int j = 0; j < nq; ++j) sx[j * kBlock] = xq[j];
+  double t = 0.0;
+  for (int i = 0; i < nq; ++i) {
+    const double li = lq[i];
+    double s = 0.0;
+    for (int j = 0; j < nq; ++j) s += sM[i * nq + j] * sx[j * kBlock];
+    t += li * s;
+  }
+  *tR = h * t;
+  const double* sS = sM + nq * nq;
+  double g = 0.0;
+  for (int i = 0; i <= m; ++i) {
+    const int pos = m * cl + i;  // the pressure node along the edge, 0 .. m N
+    const int64_t row = pos == 0       ? (int64_t)a.nrow[2 * a.eb[4 * e]]
+                        : pos == m * N ? (int64_t)a.nrow[2 * a.eb[4 * e + 1]]
+                                       : base + nf + pos - 1;
+    g += sS[i] * l[row];
+  }
+  *tf = h * g;
+}
+
+template <int S>
+__global__ __launch_bounds__(kBlock) void k_cp_b_edge_form_seg(CpFormArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ double cp_form_sm[];
+  const int nq = a.k + 1;
+  cp_form_stage(a, cp_form_sm);
+  double* sx = cp_form_sm + nq * nq + a.m + 1 + threadIdx.x;
+  constexpr int EPW = 64 / S;
+  const int lane = threadIdx.x & 63;
+  const int sub = lane / S, cl = lane % S;
+  const int64_t E = a.E;
+  const int64_t e0 = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * EPW;
+  if (e0 >= E) return;  // wave-uniform
+  const int ne = (int)min<int64_t>(EPW, E - e0);
+  const int64_t e = e0 + min(sub, ne - 1);  // idle segments shadow the last edge
+  const bool mine = sub < ne;
+  const int N = a.N;
+  const int col = blockIdx.y;
+  const double* x = a.X + col * a.ld;
+  const double* l = a.L + col * a.l_ld;
+  double tR = 0.0, tf = 0.0;
+  if (mine && cl < N) cp_form_cell(a, cp_form_sm, sx, x, l, e, cl, &tR, &tf);
+#pragma unroll
+  for (int o = S / 2; o > 0; o >>= 1) {
+    tR += __shfl_xor(tR, o, 64);
+    tf += __shfl_xor(tf, o, 64);
+  }
+  if (mine && cl == 0) {
+    const int64_t base = e * (int64_t)((a.k + a.m) * N);
+    a.gR[col * E + e] = -tR;
+    a.gf[col * E + e] = tf;
+    a.gbc[(col * E + e) * 2] = l[base];
+    a.gbc[(col * E + e) * 2 + 1] = l[base + a.k * N];
+  }
+}
+
+// N >= 32: one wave per edge, the cells in chunks of 64 taken in order.
+__global__ __launch_bounds__(kBlock) void k_cp_b_edge_form(CpFormArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ double cp_form_sm[];
+  const int nq = a.k + 1;
+  cp_form_stage(a, cp_form_sm);
+  double* sx = cp_form_sm + nq * nq + a.m + 1 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const int64_t E = a.E;
+  const int64_t e = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (e >= E) return;  // wave-uniform
+  const int N = a.N;
+  const int col = blockIdx.y;
+  const double* x = a.X + col * a.ld;
+  const double* l = a.L + col * a.l_ld;
+  double accR = 0.0, accf = 0.0;
+  for (int c0 = 0; c0 < N; c0 += 64) {
+    double tR = 0.0, tf = 0.0;
+    if (c0 + lane < N) cp_form_cell(a, cp_form_sm, sx, x, l, e, c0 + lane, &tR, &tf);
+    accR += wave_sum(tR);
+    accf += wave_sum(tf);
+  }
+  if (lane == 0) {
+    const int64_t base = e * (int64_t)((a.k + a.m) * N);
+    a.gR[col * E + e] = -accR;
+    a.gf[col * E + e] = accf;
+    a.gbc[(col * E + e) * 2] = l[base];
+    a.gbc[(col * E + e) * 2 + 1] = l[base + a.k * N];
+  }
+}
+
 bool cp_batch_ok(const nx_network* h) {
   return h && h->fe && h->fe_cp && h->solver == 1 && !proc_rank(h) && h->group == nullptr &&
          h->nranks == 1 && h->n_ghost == 0 && h->cp_Eg == 0 && h->cpc_ns == 0 && h->E > 0;
@@ -15700,19 +15840,23 @@ CpWs cp_layout(const nx_network* h, int cap, void* base) {
   return w;
 }
 size_t cp_bytes(const nx_network* h, int cap) { return cp_layout(h, cap, nullptr).bytes; }
-bool cp_batch_fits(const nx_network* h, int cap) {
-  return batch_fits(h, cap, BatchParts{}) && h->cp_bws != nullptr && cap <= h->cp_bws_cap &&
+bool cp_batch_fits(const nx_network* h, int cap, BatchParts parts) {
+  return batch_fits(h, cap, parts) && h->cp_bws != nullptr && cap <= h->cp_bws_cap &&
          cp_bytes(h, h->cp_bws_cap) <= h->cp_bws_bytes && h->cp_bws_cap == h->bws_cap;
 }
 
-// batch_workspace for the two parts together, as fe_batch_workspace.
-int cp_batch_workspace(nx_network* h, int n_cols, int* chunk_out) {
+// batch_workspace for the two parts together, as fe_batch_workspace. ask: what the call needs
+// beside what the workspace already carries (nx_cp_batch_gradient: kGrad, behind the solve's
+// fields on the handle's side; the continuous-pressure part has no such fields) -- a workspace
+// that lacks a part is released and allocated again with it, and keeps it for the calls after.
+int cp_batch_workspace(nx_network* h, int n_cols, int* chunk_out, BatchParts ask = BatchParts{}) {
+  const BatchParts parts = ask | h->bws_parts;
   auto release = [&]() {
     batch_free(h);
     cp_batch_free(h);
   };
   auto alloc = [&](int cap) {
-    if (!batch_alloc(h, cap, BatchParts{})) return false;
+    if (!batch_alloc(h, cap, parts)) return false;
     const size_t bytes = cp_bytes(h, cap);
     if (hipMalloc(&h->cp_bws, bytes) != hipSuccess) {
       h->cp_bws = nullptr;
@@ -15724,8 +15868,9 @@ int cp_batch_workspace(nx_network* h, int n_cols, int* chunk_out) {
     return true;
   };
   return batch_chunk_rule(
-      h, n_cols, false, "nx_cp_batch_solve", [&](int cap) { return cp_batch_fits(h, cap); },
-      [&](int cap) { return batch_bytes(h, cap, BatchParts{}) + cp_bytes(h, cap); }, release,
+      h, n_cols, false, "nx_cp_batch_solve",
+      [&](int cap) { return cp_batch_fits(h, cap, parts); },
+      [&](int cap) { return batch_bytes(h, cap, parts) + cp_bytes(h, cap); }, release,
       alloc, chunk_out);
 }
 
@@ -16302,6 +16447,99 @@ NX_API int nx_fe_batch_gradient(nx_network_t* h, int32_t n_cols, const double* e
       for (int c = 0; c < nc; ++c) adj.set(c, r.a_it, r.a_rr, r.a_cv);
     }
     CHECK(fe_batch_edge_form(h, ws, nc, r.one_adj ? 0 : ld));
+    HIPCALL(r.out(value, ws.gJ, 1, c0, nc));
+    HIPCALL(r.out(grad_R, ws.gR, E, c0, nc));
+    HIPCALL(r.out(grad_f, ws.gf, E, c0, nc));
+    HIPCALL(r.out(grad_bc, ws.gbc, 2 * E, c0, nc));
+    HIPCALL(hipStreamSynchronize(h->stream));
+  }
+  return NX_OK;
+}
+
+// ---- nx_cp_batch_gradient: nx_batch_gradient on a continuous-pressure handle.
+// The device matrix is symmetric, so the adjoint is the forward solve with k_b_obs's right-hand
+// side; both go through batch_solve_cols with cp_batch_apply as operator on the factors of one
+// cp_batch_factor per call, as nx_cp_batch_solve.
+namespace {
+
+int cp_batch_edge_form(nx_network* h, const BatchWs& ws, int nc, int64_t l_ld) {
+  const int64_t nI = h->cp_nI;
+  const CpFormArgs fa{(int)h->N, h->cp_k, h->cp_m, h->E, h->fe_cellh,
+                      h->cp_cst + 16 + 8 * nI + nI * nI, h->cp_eb, h->cp_nrow, ws.X, ws.L,
+                      ws.cols.ld, l_ld, ws.gR, ws.gf, ws.gbc};
+  return batch_edge_launch<CpFormArgs, k_cp_b_edge_form_seg<16>, k_cp_b_edge_form_seg<32>,
+                           k_cp_b_edge_form>(h, nc, fa, cp_form_lds(h->cp_k, h->cp_m));
+}
+
+}  // namespace
+
+NX_API int nx_cp_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
+                                const double* edge_f, const double* f_const, double rtol,
+                                int32_t maxit, int32_t kind, int32_t n_obs,
+                                const int32_t* obs_rows, const double* obs_w, const double* obs_d,
+                                double* value, double* grad_R, double* grad_bc, double* grad_f,
+                                int32_t* iters, double* relres, int32_t* converged) {
+  const int made_current = batch_pending(h);
+  CHECK(flush_assembly(h));  // a deferred nx_assemble goes first
+  CHECK(batch_adjoint_args(h, n_cols, edge_bc && value && grad_R,
+                           "edge_bc / value / grad_R is NULL", kind, n_obs, obs_rows, obs_w,
+                           obs_d));
+  if (maxit < 1) return fail(NX_ERR_ARG, "maxit must be >= 1");
+  CHECK(cp_batch_state(h, "nx_cp_batch_gradient"));
+  if (!h->have_lhs || h->asm_coef_version != h->coef_version)
+    return fail(NX_ERR_STATE, "nx_cp_batch_gradient: assemble the matrix for the resident "
+                              "coefficients first");
+  if (cp_form_lds(h->cp_k, h->cp_m) > 64 * 1024)
+    return fail(NX_ERR_STATE, "nx_cp_batch_gradient: the flux degree is too high for the "
+                              "contraction's LDS staging");
+  CHECK(batch_obs_rows_check(h->n_own, n_obs, obs_rows));
+  CHECK(set_device(h));
+  h->b_refined = h->b_fallback = 0;
+  h->b_launches = made_current;
+  AdjointRun r;
+  CHECK(cp_batch_workspace(h, n_cols, &r.chunk, BatchParts{BatchParts::kGrad}));
+  h->b_chunk = r.chunk;
+  r.h = h;
+  r.rtol = rtol;
+  r.n_obs = n_obs;
+  r.ws = batch_carve(h);
+  r.ens = false;
+  r.be = BatchEns{};
+  r.one_adj = kind == 0;
+  const BatchWs& ws = r.ws;
+  const CpWs wc = cp_layout(h, h->cp_bws_cap, h->cp_bws);
+  CHECK(batch_obs_upload(h, n_obs, r.chunk, obs_rows, obs_w, &r.od));
+  // the factor stage depends on the resident R alone: once per call, for the forward pass, the
+  // adjoint pass and their refinements
+  CHECK(cp_batch_factor(h, wc));
+  auto pass = [&](int nc, const double* Bv, double* Xv, BatchStatus st,
+                  std::vector<double>& stats) {
+    return batch_solve_cols(
+        h, ws, nc, Bv, Xv, rtol, st, stats,
+        [&](int ncs) { return cp_batch_apply(h, ws, wc, nullptr, ncs, Bv, Xv, 0); },
+        [&](const int* list, int nr) { return cp_batch_apply(h, ws, wc, list, nr, ws.R, Xv, 1); },
+        BatchFallback{BatchFallback::kKeep, maxit});
+  };
+  if (r.one_adj) {
+    CHECK(r.observe(1, nullptr, 0, ws.C, nullptr));
+    CHECK(r.solve_by(1, ws.C, ws.L, BatchStatus{&r.a_it, &r.a_rr, &r.a_cv}, pass));
+  }
+  const BatchStatus st{iters, relres, converged};
+  const int64_t E = h->E, ld = ws.cols.ld;
+  for (int c0 = 0; c0 < n_cols; c0 += r.chunk) {
+    const int nc = std::min(r.chunk, n_cols - c0);
+    CHECK(fe_batch_rhs_chunk(h, ws, c0, nc, edge_bc, edge_f, f_const));
+    CHECK(r.solve_by(nc, ws.B, ws.X, st.at(c0), pass));
+    const BatchStatus adj = st.at((int64_t)n_cols + c0);
+    if (!r.one_adj) {
+      CHECK(r.upload_data(obs_d, c0, nc));
+      CHECK(r.observe(nc, ws.X, 1, ws.C, ws.gJ));
+      CHECK(r.solve_by(nc, ws.C, ws.L, adj, pass));
+    } else {
+      CHECK(r.observe(nc, ws.X, 0, nullptr, ws.gJ));
+      for (int c = 0; c < nc; ++c) adj.set(c, r.a_it, r.a_rr, r.a_cv);
+    }
+    CHECK(cp_batch_edge_form(h, ws, nc, r.one_adj ? 0 : ld));
     HIPCALL(r.out(value, ws.gJ, 1, c0, nc));
     HIPCALL(r.out(grad_R, ws.gR, E, c0, nc));
     HIPCALL(r.out(grad_f, ws.gf, E, c0, nc));
@@ -17940,7 +18178,9 @@ NX_API int nx_fe_set_cp(nx_network_t* h, int32_t k, int32_t m, int32_t nI, const
       return fail(NX_ERR_ARG, "continuous pressure: incidence");
   for (int64_t j = 0; j < child_off[n]; ++j)
     if (child[j] < 0 || child[j] >= n) return fail(NX_ERR_ARG, "continuous pressure: children");
-  const int64_t ncst = 16 + 8 * (int64_t)nI + (int64_t)nI * nI;
+  // (Kh | Ch | Eh | Fh, then the reference flux mass and the source weights that
+  // k_cp_b_edge_form contracts with)
+  const int64_t ncst = 16 + 8 * (int64_t)nI + (int64_t)nI * nI + (int64_t)(k + 1) * (k + 1) + m + 1;
   CHECK(upload(&h->cp_cst, cst, ncst, h->stream));
   if (nI > 0) CHECK(upload(&h->cp_tI, tI, nI, h->stream));
   CHECK(upload(&h->cp_nrow, nrow, 2 * n, h->stream));

@@ -544,7 +544,7 @@ class CpTables:
     k: int
     m: int
     nI: int
-    cst: np.ndarray  # Kh | Ch | Eh | Fh
+    cst: np.ndarray  # Kh | Ch | Eh | Fh | reference flux mass (k+1)^2 | source weights (m+1)
     tI: np.ndarray
     n_nodes: int
     nrow: np.ndarray  # (n, 2) pressure row, multiplier row or -1
@@ -637,7 +637,11 @@ def build_cp_tables(lay: FeLayout, src: np.ndarray, dst: np.ndarray,
     np.cumsum(np.bincount(ch_par, minlength=n), out=child_off[1:])
     nown = inc[inc_off[:-1], 0]
     Kh, Ch, Eh, Fh, tI = condensed_cell_blocks(lay.k, lay.m)
-    cst = np.concatenate([Kh.ravel(), Ch.ravel(), Eh.ravel(), Fh.ravel()])
+    # (behind them the reference mass and a cell's source weights, from the term tables the rhs
+    # kernel evaluates: nx_cp_batch_gradient's contraction)
+    _, tval, ent, _, _ = _tables(lay.k, lay.m)
+    cst = np.concatenate([Kh.ravel(), Ch.ravel(), Eh.ravel(), Fh.ravel(),
+                          tval[ent["mass"]].ravel(), tval[ent["src"]]])
     i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()  # noqa: E731
     tab = CpTables(lay.k, lay.m, int(tI.size), cst, i32(tI), int(n), i32(nrow), i32(eb),
                    i32(lev_off), i32(order), i32(inc_off), i32(inc), i32(parent),
@@ -712,7 +716,7 @@ def cp_model(lay: FeLayout, tab: CpTables, val: np.ndarray, b: np.ndarray, R: np
     Kh = tab.cst[:16].reshape(4, 4)
     Ch = tab.cst[16:16 + 4 * nI].reshape(4, nI)
     Eh = tab.cst[16 + 4 * nI:16 + 8 * nI].reshape(nI, 4)
-    Fh = tab.cst[16 + 8 * nI:].reshape(nI, nI)
+    Fh = tab.cst[16 + 8 * nI:16 + 8 * nI + nI * nI].reshape(nI, nI)
     tI = tab.tI.astype(np.int64)
     tV = np.array([1, -1, 1, -1])
     eb = tab.eb.reshape(-1, 4)
@@ -1022,7 +1026,8 @@ def cp_apply_model(lay: FeLayout, tab: CpTables, fm: dict, Bm: np.ndarray, R: np
     per = nf + m * N - 1
     Ch = np.asarray(tab.cst[16:16 + 4 * nI], dtype=np.float64).reshape(4, nI)
     Eh = np.asarray(tab.cst[16 + 4 * nI:16 + 8 * nI], dtype=np.float64).reshape(nI, 4)
-    Fh = np.asarray(tab.cst[16 + 8 * nI:], dtype=np.float64).reshape(nI, nI)
+    Fh = np.asarray(tab.cst[16 + 8 * nI:16 + 8 * nI + nI * nI],
+                    dtype=np.float64).reshape(nI, nI)
     tI = [int(t) for t in tab.tI]
     eb = tab.eb.reshape(-1, 4)
     nrow = tab.nrow.reshape(-1, 2)
@@ -1155,3 +1160,54 @@ def cp_apply_model(lay: FeLayout, tab: CpTables, fm: dict, Bm: np.ndarray, R: np
                     X[:, base + lrow(i, j)] = val
             yn = [y0, y1]
     return X
+
+
+def cp_edge_form_model(lay: FeLayout, tab: CpTables, x: np.ndarray, mu: np.ndarray,
+                       cell_h: np.ndarray):
+    """numpy restatement of ``k_cp_b_edge_form`` (``nx_cp_batch_gradient``'s contraction) from
+    the tables the device gets: ``x`` the forward and ``mu`` the adjoint column (device rows);
+    returns ``(gR (E,), gf (E,), gbc (E, 2))`` with, per edge over its cells c,
+
+    * ``gR[e] = -sum_c h_c mu_c^T M x_c`` -- the cell's k + 1 flux nodes, local rows
+      ``k c .. k c + k``; ``M`` the reference mass behind ``Fh`` in ``tab.cst``;
+    * ``gf[e] = sum_c h_c sum_i s_i mu[p_ci]`` -- the cell's m + 1 pressure rows (the first of
+      cell 0 and the last of cell N - 1 are the end nodes' rows ``nrow[u, 0]`` / ``nrow[v, 0]``),
+      ``s`` the source weights behind ``M``;
+    * ``gbc[e] = mu`` at the edge's first and last flux row.
+
+    Sums in the kernel's order per cell (j inside i, from 0.0); the cells are added in order
+    where the kernel adds them by a butterfly, so the two agree to rounding, not in bits."""
+    N, k, m, nI, E = lay.N, lay.k, lay.m, tab.nI, lay.E
+    nq = k + 1
+    nf = k * N + 1
+    per = nf + m * N - 1
+    off = 16 + 8 * nI + nI * nI
+    M = np.asarray(tab.cst[off:off + nq * nq], dtype=np.float64).reshape(nq, nq)
+    s = np.asarray(tab.cst[off + nq * nq:off + nq * nq + m + 1], dtype=np.float64)
+    eb = tab.eb.reshape(-1, 4)
+    nrow = tab.nrow.reshape(-1, 2)
+    h = np.asarray(cell_h, dtype=np.float64).reshape(E, N)
+    x = np.asarray(x, dtype=np.float64)
+    mu = np.asarray(mu, dtype=np.float64)
+    gR, gf, gbc = np.zeros(E), np.zeros(E), np.zeros((E, 2))
+    for e in range(E):
+        base = e * per
+        aR = af = 0.0
+        for c in range(N):
+            t = 0.0
+            for i in range(nq):
+                sm = 0.0
+                for j in range(nq):
+                    sm += float(M[i, j]) * float(x[base + k * c + j])
+                t += float(mu[base + k * c + i]) * sm
+            aR += float(h[e, c]) * t
+            g = 0.0
+            for i in range(m + 1):
+                pos = m * c + i
+                row = (nrow[eb[e, 0], 0] if pos == 0 else nrow[eb[e, 1], 0] if pos == m * N
+                       else base + nf + pos - 1)
+                g += float(s[i]) * float(mu[row])
+            af += float(h[e, c]) * g
+        gR[e], gf[e] = -aR, af
+        gbc[e] = mu[base], mu[base + k * N]
+    return gR, gf, gbc

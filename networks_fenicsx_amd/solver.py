@@ -224,7 +224,9 @@ class Solver:
             (``cycle_direct``), with several ranks or with ``ksp_type="minres"`` -- these
             degrees take the per-scenario loop, whose columns are bit-equal to single solves;
             the batched columns agree with them to rounding (with the
-            measurements).
+            measurements). The option also lets :meth:`gradient` serve these degrees on a
+            forest (``nx_cp_batch_gradient``); off, it raises
+            ``NotImplementedError`` there.
     """
 
     def __init__(
@@ -532,8 +534,15 @@ class Solver:
         ``nx_fe_batch_supported`` holds (``nx_fe_batch_gradient``: both solves through the
         batched condensed solve, the contraction with the degree-k element mass); ``rows`` then
         index the (k, 0) system's block order, interior flux nodes included. Not served on
-        these degrees: ``R=`` (ensembles), :meth:`hessian_vector`, continuous pressure
-        (m >= 1) and several ranks -- ``NotImplementedError``, as without the option.
+        these degrees: ``R=`` (ensembles), :meth:`hessian_vector` and several ranks --
+        ``NotImplementedError``, as without the option.
+
+        With ``batch_continuous`` it serves continuous pressure (k > m >= 1) on a forest, where
+        ``nx_cp_batch_supported`` holds (``nx_cp_batch_gradient``: one factor stage of the
+        node-condensed solve per call, both solves on its factors, the contraction over the
+        (k, m) rows); ``rows`` then index the (k, m) system's block order. ``batch_degrees``
+        alone does not switch it on. Not served on these degrees: ``R=``,
+        :meth:`hessian_vector`, graphs with cycles and several ranks.
 
         ``R`` (``(B, num_edges)`` or ``(B,)`` constants, as :meth:`solve_ensemble`): scenario j
         is evaluated at ``R[j]`` instead of the last ``compute_forms``' R
@@ -561,7 +570,8 @@ class Solver:
         rows, w, data = self._observations(rows, weights, data, B)
         dev_rows = self._adjoint_ready("gradient", rows, edge_R is not None, fe)
         if fe:
-            value, gR, gbc, gf, it, rr, conv = h.fe_batch_gradient(
+            call = h.cp_batch_gradient if fe == "cp" else h.fe_batch_gradient
+            value, gR, gbc, gf, it, rr, conv = call(
                 edge_bc, edge_f, f_const, self._rtol, self._maxit, rows=dev_rows, weights=w,
                 data=data)
         elif edge_R is not None:
@@ -594,21 +604,29 @@ class Solver:
                 f"{rr[bad].tolist()} > rtol {self._rtol:.1e})")
         return res
 
-    def _adjoint_supported(self, what: str, ensemble: bool = False) -> bool:
-        """The options under which :meth:`gradient` and :meth:`hessian_vector` run. True: the
-        call is :meth:`gradient` on degrees (k, 0), k >= 2, under ``batch_degrees``
-        (``nx_fe_batch_gradient``)."""
+    def _adjoint_supported(self, what: str, ensemble: bool = False) -> str:
+        """The options under which :meth:`gradient` and :meth:`hessian_vector` run. Returns the
+        general-degree route of the call, or "" (P1/DG0): "fe" -- :meth:`gradient` on degrees
+        (k, 0), k >= 2, under ``batch_degrees`` (``nx_fe_batch_gradient``); "cp" -- on
+        continuous pressure, k > m >= 1, under ``batch_continuous``
+        (``nx_cp_batch_gradient``)."""
         asm = self.assembler
         if getattr(asm, "_nranks", 1) > 1:
             raise NotImplementedError(f"{what} runs on one rank")
         deg = tuple(asm.degrees)
         k0 = len(deg) == 2 and deg[0] >= 2 and deg[1] == 0
-        fe = k0 and what == "gradient" and self._fe_batch
+        km = len(deg) == 2 and deg[0] > deg[1] >= 1
+        fe = ""
+        if what == "gradient":
+            fe = "fe" if k0 and self._fe_batch else "cp" if km and self._cp_batch else ""
         if deg != (1, 0) and not fe:
             hint = ""
             if k0 and what == "gradient":
                 hint = ("; Solver(..., batch_degrees=True) (or NXHIP_FE_BATCH=1) serves gradient "
                         "on flux degree k >= 2 with DG0 pressure")
+            if km and what == "gradient":
+                hint = ("; Solver(..., batch_continuous=True) (or NXHIP_CP_BATCH=1) serves "
+                        "gradient on continuous pressure (k > m >= 1) on a forest")
             raise NotImplementedError(
                 f"{what} needs the P1/DG0 discretisation, not degrees {deg}{hint}")
         if fe and ensemble:
@@ -645,14 +663,20 @@ class Solver:
                 raise ValueError(f"data must be ({B}, {rows.size}) or ({rows.size},)")
         return rows, w, data
 
-    def _adjoint_ready(self, what: str, rows, ensemble: bool, fe: bool = False) -> np.ndarray:
+    def _adjoint_ready(self, what: str, rows, ensemble: bool, fe: str = "") -> np.ndarray:
         """The handle configured, its matrix current and the batched path checked (``fe``: the
-        (k, 0) one); returns the observed rows as device rows."""
+        general-degree route of :meth:`_adjoint_supported`); returns the observed rows as
+        device rows."""
         asm = self.assembler
         h = asm.handle
         self._configure()
         if not asm.lhs_current:  # the matrix of the last compute_forms (its R), values only
             asm.assemble(assemble_lhs=True, assemble_rhs=False)
+        if fe == "cp":
+            if not h.cp_batch_supported():
+                raise NotImplementedError(f"{what}: the batched node-condensed solve does not "
+                                          "apply to this handle (nx_cp_batch_supported)")
+            return asm.block_order_rows()[rows]
         if fe:
             if not h.fe_batch_supported():
                 raise NotImplementedError(f"{what}: the batched condensed solve does not apply "
