@@ -7,7 +7,10 @@ the device gets) is then held against the general-degree CPU adjoint of
 tests/gradient_ref_fe.py: value, dR, df and dp_bc to 1e-10 relative -- two solves at the
 oracle's bar, exact host arithmetic otherwise. demo_tree_N1 has one cell per edge (no interior
 pressure row: both pressure rows of the cell are node rows), linear_alt_N3 alternating edge
-orientation.
+orientation; hub5, broom33, cat70, hubhub5x5 and rand200_s1 (tests/tree_shapes.py, N <= 6) put
+nodes past the record caps, edges pointing into their parent at junctions of degree 3 to 19 and
+the seeded R = 10^U(-1, 1) under the same bar -- before tests/test_gpu_fe_shapes.py runs the
+device there, so that a failure on the device is the kernel's, not the model's or the oracle's.
 
 Part 2, the route: the C ABI's new entry (header and ctypes table) and ``Solver.gradient``'s
 routing with the handle stubbed -- the new route engages only with ``batch_continuous`` (or
@@ -29,11 +32,16 @@ from networks_fenicsx_amd.layout_fe import (build_cp_tables, build_fe_layout, cp
                                             cp_factor_model, evaluate_terms)
 from oracle import nx_oracle as O
 from oracle import nx_oracle_fe as OF
+from tree_shapes import (FE_N_CAP, SHAPES, coefficients, cp_record_facts, p_xy,
+                         reversed_edges)
 
 HEADER = Path(__file__).resolve().parent.parent / "include" / "nxhip.h"
 PAIRS = [(2, 1), (3, 1), (3, 2), (4, 3)]
 MODEL_CASES = [("Y_N4", km) for km in PAIRS] + [("demo_tree_N1", (2, 1)),
                                                  ("linear_alt_N3", (2, 1))]
+# forests that are not binary (tests/tree_shapes.py), the degrees of tests/test_gpu_fe_shapes.py
+SHAPE_MODEL_CASES = [(n, km) for n in ("hub5", "broom33", "cat70", "hubhub5x5", "rand200_s1")
+                     for km in ((2, 1), (3, 2))]
 BAR = 1e-10
 
 
@@ -42,7 +50,11 @@ class _Model:
     reference block order to device rows, and one scenario of tests/test_gpu_cp_gradient.py."""
 
     def __init__(self, case, k, m):
-        make, N, strategy, pbc = CASES[case]
+        if case in SHAPES:  # tests/tree_shapes.py: p_xy, the shape's own R (none: R = 1)
+            make, N, _ = SHAPES[case]
+            N, strategy, pbc = min(N, FE_N_CAP), None, p_xy
+        else:
+            make, N, strategy, pbc = CASES[case]
         self.mesh = mesh = NetworkMesh(make(), N=N, color_strategy=strategy)
         src, dst = mesh.edges
         pos = np.asarray(mesh.node_coordinates, dtype=np.float64)
@@ -52,7 +64,10 @@ class _Model:
         self.F = F = OF.build_problem_fe(pos, src, dst, N, k, m, mesh.edge_colors)
         assert F.n_dofs == lay.n_rows
         E = self.E = mesh.num_edges
-        self.R = 0.5 + (np.arange(E) % 3) / 2.0
+        if case in SHAPES:
+            self.R = np.asarray(coefficients(case, E).get("R", np.ones(E)), dtype=np.float64)
+        else:
+            self.R = 0.5 + (np.arange(E) % 3) / 2.0
         self.f = 0.1 + 0.02 * (np.arange(E) % 5)
         self.pb = np.asarray(pbc(F.base.pos3.T.copy()), dtype=np.float64)
         _, self.h = O.cell_geometry(F.base)
@@ -79,7 +94,7 @@ def test_device_matrix_is_symmetric(km):
     assert abs(s.A).max() > 0
 
 
-@pytest.mark.parametrize("case,km", MODEL_CASES)
+@pytest.mark.parametrize("case,km", MODEL_CASES + SHAPE_MODEL_CASES)
 @pytest.mark.parametrize("kind", ["linear", "lsq"])
 def test_model_matches_cpu_adjoint(case, km, kind):
     from networks_fenicsx_amd.layout_fe import cp_edge_form_model
@@ -88,6 +103,13 @@ def test_model_matches_cpu_adjoint(case, km, kind):
     lay, tab, F = s.lay, s.tab, s.F
     if case == "demo_tree_N1":
         assert lay.N == 1 and km[1] * lay.N - 1 == 0  # no interior pressure row
+    if case in SHAPES:  # what the shape is there for: nodes past the record caps (the lists),
+        # edges pointing into their parent at junctions, the seeded two-decade R
+        rec = cp_record_facts(tab)
+        rev = reversed_edges(*s.mesh.edges, s.mesh.degrees)
+        assert rec["over"] >= 1 or case == "cat70", rec
+        assert (rev >= 3).sum() >= 20 or case in ("hub5", "broom33"), rev
+        assert (s.R.max() / s.R.min() > 30.0) == (case in ("hubhub5x5", "rand200_s1"))
     rng = np.random.default_rng(11)
     rows = rng.choice(F.n_dofs, size=min(12, F.n_dofs), replace=False)
     assert (rows < F.p_offset).any() and (rows >= F.p_offset).any()

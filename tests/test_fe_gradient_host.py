@@ -1,15 +1,28 @@
 """Host side of the (k, 0) adjoint gradient: the C ABI's new entry (header and ctypes table) and
 ``Solver.gradient``'s routing with the handle stubbed (no device) -- the new route engages only
 with ``batch_degrees`` on degrees (k, 0), k >= 2, and everything it does not serve still raises
-``NotImplementedError``."""
+``NotImplementedError``. Before it, the contraction's model: a numpy restatement of
+``k_fe_b_edge_form`` through the row maps the device gets, held to the general-degree CPU adjoint
+on a binary tree and on the forests of tests/tree_shapes.py (``test_model_matches_cpu_adjoint``)."""
 
 import re
 from pathlib import Path
 
 import numpy as np
 import pytest
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
 
-from networks_fenicsx_amd import Solver, _lib
+from cases import CASES
+from gradient_ref_fe import AdjointRefFe
+from networks_fenicsx_amd import NetworkMesh, Solver, _lib
+from networks_fenicsx_amd.assembly import batch_coefficients, edge_boundary_rhs_adjoint
+from networks_fenicsx_amd.element import element_tensors
+from networks_fenicsx_amd.layout import build_local_problem
+from networks_fenicsx_amd.layout_fe import build_fe_aux_maps, build_fe_layout, evaluate_terms
+from oracle import nx_oracle as O
+from oracle import nx_oracle_fe as OF
+from tree_shapes import FE_N_CAP, SHAPES, coefficients, p_xy, reversed_edges
 
 HEADER = Path(__file__).resolve().parent.parent / "include" / "nxhip.h"
 E, NODES, ROWS = 3, 4, 20
@@ -92,6 +105,125 @@ class _StubAssembler:
 KW = dict(rows=np.array([1, 7]), weights=np.array([1.0, 2.0]))
 
 
+# ---- the contraction's model ---------------------------------------------------------------
+MODEL_BAR = 1e-10  # tests/test_cp_gradient_host.py's: two solves at the oracle's bar
+MODEL_CASES = [("Y_N4", 2), ("Y_N4", 3)] + [(n, k) for n in ("hub5", "broom33", "cat70",
+                                                             "hubhub5x5", "rand200_s1")
+                                            for k in (2, 3)]
+
+
+def fe_edge_form_model(lay, maps, x, mu, cell_h):
+    """numpy restatement of ``k_fe_b_edge_form`` (``nx_fe_batch_gradient``'s contraction) from
+    the row maps the device gets (``layout_fe.build_fe_aux_maps``: ``v_fe`` the vertex flux
+    rows, ``i_fe`` the interior flux rows, ``p_fe`` the pressure rows): ``x`` the forward and
+    ``mu`` the adjoint column in device rows; per edge over its cells c
+
+    * ``gR[e] = -sum_c h_c mu_c^T M x_c`` -- the cell's left vertex, k - 1 interior nodes and
+      right vertex, ``M`` the reference mass (``element_tensors(k, 0)``);
+    * ``gf[e] = -sum_c h_c mu[p_c]`` (DG0: the source enters a cell's pressure row as -f h);
+    * ``gbc[e] = mu`` at the edge's first and last vertex row."""
+    E, N, k = lay.E, lay.N, lay.k
+    km = k - 1
+    M = np.asarray(element_tensors(k, 0)[0], dtype=np.float64).reshape(k + 1, k + 1)
+    vfe = np.asarray(maps.v_fe, dtype=np.int64).reshape(E, N + 1)
+    ife = np.asarray(maps.i_fe, dtype=np.int64).reshape(E, N, km)
+    pfe = np.asarray(maps.p_fe, dtype=np.int64).reshape(E, N)
+    h = np.asarray(cell_h, dtype=np.float64).reshape(E, N)
+    gR, gf, gbc = np.zeros(E), np.zeros(E), np.zeros((E, 2))
+    for e in range(E):
+        for c in range(N):
+            rows = np.concatenate([vfe[e, c:c + 1], ife[e, c], vfe[e, c + 1:c + 2]])
+            gR[e] -= h[e, c] * float(mu[rows] @ (M @ x[rows]))
+            gf[e] -= h[e, c] * float(mu[pfe[e, c]])
+        gbc[e] = mu[vfe[e, 0]], mu[vfe[e, N]]
+    return gR, gf, gbc
+
+
+@pytest.mark.parametrize("case,k", MODEL_CASES)
+@pytest.mark.parametrize("kind", ["linear", "lsq"])
+def test_model_matches_cpu_adjoint(case, k, kind):
+    """The (k, 0) counterpart of tests/test_cp_gradient_host.py's model test: the device matrix
+    of the (k, 0) layout is symmetric, so the adjoint is a second solve with it on ``k_b_obs``'s
+    right-hand side (here SuperLU on the host evaluation of the term tables: the condensed
+    sweeps are tests/test_gpu_fe_batch.py's subject); the numpy restatement of the contraction
+    through ``nx_fe_set_direct``'s row maps is held against the general-degree CPU adjoint --
+    value, dR, df and dp_bc to 1e-10 relative. Y_N4 and the forests of tests/tree_shapes.py
+    (N <= 6; the shape's own R, else R = 1) on which tests/test_gpu_fe_shapes.py runs the
+    device: junctions of up to 34 multiplier rows, edges pointing into their parent, the
+    seeded two-decade R -- a failure there on the device is then the kernel's."""
+    if case in SHAPES:
+        make, N, _ = SHAPES[case]
+        N, strategy, pbc = min(N, FE_N_CAP), None, p_xy
+    else:
+        make, N, strategy, pbc = CASES[case]
+    mesh = NetworkMesh(make(), N=N, color_strategy=strategy)
+    src, dst = mesh.edges
+    pos = np.asarray(mesh.node_coordinates, dtype=np.float64)
+    lay = build_fe_layout(pos, src, dst, mesh.degrees, N, k, 0)
+    lp = build_local_problem(pos, src, dst, mesh.degrees, N, 0, 1)
+    maps = build_fe_aux_maps(lay, lp)
+    F = OF.build_problem_fe(pos, src, dst, N, k, 0, mesh.edge_colors)
+    assert F.n_dofs == lay.n_rows
+    E = mesh.num_edges
+    if case in SHAPES:
+        R = np.asarray(coefficients(case, E).get("R", np.ones(E)), dtype=np.float64)
+        rev = reversed_edges(src, dst, mesh.degrees)
+        assert (rev >= 3).sum() >= 20 or case in ("hub5", "broom33"), rev
+        assert (R.max() / R.min() > 30.0) == (case in ("hubhub5x5", "rand200_s1"))
+        if case == "broom33":
+            assert int(np.max(mesh.degrees)) == 34  # 34 multiplier rows at one junction
+    else:
+        R = 0.5 + (np.arange(E) % 3) / 2.0
+    f = 0.1 + 0.02 * (np.arange(E) % 5)
+    pb = np.asarray(pbc(F.base.pos3.T.copy()), dtype=np.float64)
+    _, h = O.cell_geometry(F.base)
+    dev = np.empty(F.n_dofs, dtype=np.int64)  # reference block order -> device rows
+    nf = k * N + 1
+    for e in range(E):
+        dev[F.flux_offset[e]:F.flux_offset[e] + nf] = lay.flux_rows[e]
+    dev[F.p_offset:F.lm_offset] = lay.p_rows
+    dev[F.lm_offset:] = lay.lm_rows
+    assert np.array_equal(np.sort(dev), np.arange(F.n_dofs))
+    edge_ids = np.arange(E)
+    bc, ef, _ = batch_coefficients(mesh, edge_ids, pb[None, :], f[None, :])
+    val, rhs = evaluate_terms(lay, R, ef[0], bc[0], h)
+    A = sp.csr_matrix((val, lay.col, lay.rowptr), shape=(lay.n_rows, lay.n_rows))
+    assert abs(A - A.T).max() == 0.0 and abs(A).max() > 0
+
+    rng = np.random.default_rng(11)
+    rows = rng.choice(F.n_dofs, size=min(12, F.n_dofs), replace=False)
+    assert (rows < F.p_offset).any() and (rows >= F.p_offset).any()
+    w = 0.5 + rng.random(rows.size)
+    data = None if kind == "linear" else rng.standard_normal(rows.size)
+    ref = AdjointRefFe(F, R).gradient(pb, f, rows, w, data)
+
+    lu = spla.splu(A.tocsc())
+    x = lu.solve(rhs)
+    assert np.linalg.norm(x[dev] - ref["x"]) <= MODEL_BAR * np.linalg.norm(ref["x"])
+    xo = x[dev[rows]]
+    c = np.zeros(lay.n_rows)
+    if data is None:
+        value = float(np.sum(w * xo))
+        c[dev[rows]] = w
+    else:
+        value = 0.5 * float(np.sum(w * (xo - data) ** 2))
+        c[dev[rows]] = w * (xo - data)
+    mu = lu.solve(c)
+    gR, gf, gbc = fe_edge_form_model(lay, maps, x, mu, h)
+    index, sign = edge_boundary_rhs_adjoint(mesh, edge_ids)
+    dp = np.take(gbc.reshape(-1), index) * sign
+
+    def rel(a, b):
+        assert np.linalg.norm(b) > 0
+        return float(np.linalg.norm(a - b) / np.linalg.norm(b))
+
+    errs = {"value": abs(value - ref["value"]) / abs(ref["value"]), "dR": rel(gR, ref["dR"]),
+            "df": rel(gf, ref["df"]), "dp_bc": rel(dp, ref["dp_bc"])}
+    print(f"{case} k={k} {kind}: " + ", ".join(f"{q} {v:.2e}" for q, v in errs.items()))
+    assert max(errs.values()) <= MODEL_BAR, errs
+
+
+# ---- the route -------------------------------------------------------------------------------
 def test_symbol_is_declared_and_exported():
     text = HEADER.read_text()
     assert "nx_fe_batch_gradient" in _lib.EXPORTED_SYMBOLS

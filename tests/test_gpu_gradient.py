@@ -36,6 +36,7 @@ from networks_fenicsx_amd import network_generation as ng
 from networks_fenicsx_amd.assembly import evaluate_nodal
 from networks_fenicsx_amd.post_processing import terminal_conductance
 from oracle import nx_oracle as O
+from tree_shapes import FE_N_CAP, SHAPES, coefficients, p_xy
 
 pytestmark = pytest.mark.gpu
 
@@ -70,6 +71,8 @@ def _graph(name):
         return make, N, None, p_y
     if name == "long_N300":
         return (lambda: ng.make_tree(3, 1, 1)), 300, None, p_y
+    if name in SHAPES:  # tests/tree_shapes.py (the degree-k set-ups of test_gpu_fe_shapes.py)
+        return SHAPES[name][0], min(SHAPES[name][1], FE_N_CAP), None, p_xy
     raise KeyError(name)
 
 
@@ -80,8 +83,13 @@ class Setup:
         self.mesh = NetworkMesh(make(), N=N, color_strategy=strategy)
         self.asm = HydraulicNetworkAssembler(self.mesh, **asm_kw)
         E, nn = self.mesh.num_edges, self.mesh.num_nodes
-        self.R = 0.5 + (np.arange(E) % 3) / 2.0
-        self.asm.compute_forms(p_bc_ex=self.pbc, R=self.R)
+        if name in SHAPES:  # the shape's own coefficients (none: R = 1, f = 0)
+            coef = coefficients(name, E)
+            self.R = np.asarray(coef.get("R", np.ones(E)), dtype=np.float64)
+            self.asm.compute_forms(p_bc_ex=self.pbc, R=self.R, **({"f": coef["f"]} if coef else {}))
+        else:
+            self.R = 0.5 + (np.arange(E) % 3) / 2.0
+            self.asm.compute_forms(p_bc_ex=self.pbc, R=self.R)
         src, dst = self.mesh.edges
         self.P = P = O.build_problem(self.mesh.node_coordinates, src, dst, N,
                                      self.mesh.edge_colors)

@@ -6,17 +6,19 @@ The recipe and the bar are tests/test_gradient_ref_fe.py's: differences in every
 ``1e-5 R_e``), every boundary node's ``p_bc`` and every ``f_e`` (step ``1e-3``: x is linear in
 both, so J is at most quadratic and the central difference has no truncation error); 1e-7 of
 ``max |g|`` per gradient (observed over these eight cases: <= 1.2e-9 for dR, <= 1e-11 for df
-and dp_bc)."""
+and dp_bc).
+
+The same on the forests of ``tree_shapes.FD_SHAPES`` (tests/test_gradient_ref_fe.py), on which
+the adjoint is the yardstick of tests/test_gpu_fe_shapes.py."""
 
 import numpy as np
 import pytest
 
 from cases import CASES
-from gradient_ref_fe import AdjointRefFe, forward_fe, objective
 from networks_fenicsx_amd import NetworkMesh
 from oracle import nx_oracle_fe as OF
-
-BAR = 1e-7
+from test_gradient_ref_fe import fd_check, shape_setup
+from tree_shapes import FD_SHAPES
 
 
 def _setup(case, k, m):
@@ -36,32 +38,18 @@ def _setup(case, k, m):
 @pytest.mark.parametrize("kind", ["linear", "lsq"])
 def test_adjoint_matches_finite_differences(case, k, m, kind):
     P, R, f, pb = _setup(case, k, m)
-    rng = np.random.default_rng(3)
-    rows = rng.choice(P.n_dofs, size=12, replace=False)
-    w = 0.5 + rng.random(12)
-    data = None if kind == "linear" else rng.standard_normal(12)
-    g = AdjointRefFe(P, R).gradient(pb, f, rows, w, data)
+    fd_check(P, R, f, pb, kind, f"{case} ({k},{m})")
 
-    def J(pb_, f_, R_):
-        return objective(forward_fe(P, pb_, f_, R_), rows, w, data)
 
-    assert g["value"] == pytest.approx(J(pb, f, R), rel=1e-13, abs=1e-15)
-    E = P.base.src.size
-    fd_R = np.zeros(E)
-    fd_f = np.zeros(E)
-    for e in range(E):
-        d = np.zeros(E)
-        d[e] = 1e-5 * R[e]
-        fd_R[e] = (J(pb, f, R + d) - J(pb, f, R - d)) / (2 * d[e])
-        d[e] = 1e-3
-        fd_f[e] = (J(pb, f + d, R) - J(pb, f - d, R)) / 2e-3
-    fd_p = np.zeros(pb.size)
-    for v in np.concatenate([P.base.leaf_in, P.base.root_out]):
-        d = np.zeros(pb.size)
-        d[v] = 1e-3
-        fd_p[v] = (J(pb + d, f, R) - J(pb - d, f, R)) / 2e-3
-    for name, fd in (("dR", fd_R), ("df", fd_f), ("dp_bc", fd_p)):
-        assert np.abs(fd).max() > 0, name
-        err = np.abs(g[name] - fd).max() / np.abs(fd).max()
-        print(f"{case} ({k},{m}) {kind} {name}: {err:.2e} of max|g|")
-        assert err <= BAR, (name, err)
+@pytest.mark.parametrize("name", list(FD_SHAPES))
+@pytest.mark.parametrize("k,m", [(2, 1), (3, 2)])
+@pytest.mark.parametrize("kind", ["linear", "lsq"])
+def test_adjoint_matches_finite_differences_on_shapes(name, k, m, kind):
+    """tests/test_gradient_ref_fe.py's forests that are not binary at continuous pressure: a
+    hub's and a broom's shared node pressure with 6 edges, side edges pointing into a spine, a
+    hub of hubs with the seeded two-decade R."""
+    P, R, f, pb = shape_setup(name, k, m)
+    g, fd_p, _ = fd_check(P, R, f, pb, kind, f"{name} ({k},{m})")
+    inward = np.setdiff1d(P.base.root_out, [0])
+    if inward.size:  # the derivative at the "in" side of a reversed edge is not trivially 0
+        assert np.abs(fd_p[inward]).min() > 0 and np.abs(g["dp_bc"][inward]).min() > 0

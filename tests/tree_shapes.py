@@ -149,14 +149,71 @@ SHAPES = {
 JOBS = (1, 4, 256)  # target_jobs; 256 is build_tree_preconditioner's default
 
 
+def seeded_coefficients(seed: int, E: int) -> dict:
+    """A seeded per-edge R = 10^U(-1, 1) (two decades) with f = 0.1 + 0.02 (e mod 5)."""
+    R = 10.0 ** np.random.default_rng(seed).uniform(-1.0, 1.0, E)
+    return {"R": R, "f": 0.1 + 0.02 * (np.arange(E) % 5)}
+
+
 def coefficients(name: str, E: int) -> dict:
     """The forms' coefficients of a shape: nothing (R = 1, f = 0), or a seeded per-edge
     R = 10^U(-1, 1) with f = 0.1 + 0.02 (e mod 5)."""
     if not SHAPES[name][2]:
         return {}
-    seed = sorted(SHAPES).index(name) + 11
-    R = 10.0 ** np.random.default_rng(seed).uniform(-1.0, 1.0, E)
-    return {"R": R, "f": 0.1 + 0.02 * (np.arange(E) % 5)}
+    return seeded_coefficients(sorted(SHAPES).index(name) + 11, E)
+
+
+# The degree-k gradients (tests/test_gradient_ref_fe.py, tests/test_gradient_ref_cp.py: the CPU
+# adjoint against finite differences; at most 16 edges): name -> (graph factory, N, seeded R).
+# hub(5)'s hub is past both record caps of the continuous-pressure node forest, broom(5)'s
+# junction too; caterpillar(7) has side edges pointing INTO the spine at i = 3, 6 and
+# hubhub(2, 2) four incoming leaf edges, so both have boundary nodes that are an edge's source.
+FD_SHAPES = {
+    "hub5_N3": (lambda: hub(5), 3, False),
+    "broom5_N2": (lambda: broom(5), 2, False),
+    "cat7_N2": (lambda: caterpillar(7), 2, False),
+    "hubhub2x2_N2": (lambda: hubhub(2, 2), 2, True),
+}
+# the forests the degree-k batched paths are held on (tests/test_gpu_fe_shapes.py, and the host
+# models before them: tests/test_fe_gradient_host.py, tests/test_cp_gradient_host.py)
+FE_GRADIENT_SHAPES = ["hub3", "hub5", "hub70", "broom33", "cat70", "hubhub5x5", "rand200_s1"]
+FE_N_CAP = 6  # cells per edge at general degrees (tests/test_gpu_tree_shapes.py, _fe_open)
+
+
+def fd_shape(name: str):
+    """``(graph, N, R (E,), f (E,))`` of an ``FD_SHAPES`` entry: the gradient tests' R = 0.5 +
+    (e mod 3) / 2, or the seeded two-decade R; f = 0.1 + 0.02 (e mod 5)."""
+    make, N, seeded = FD_SHAPES[name]
+    G = make()
+    E = G.number_of_edges()
+    f = 0.1 + 0.02 * (np.arange(E) % 5)
+    R = seeded_coefficients(29, E)["R"] if seeded else 0.5 + (np.arange(E) % 3) / 2.0
+    return G, N, R, f
+
+
+def reversed_edges(src, dst, degrees) -> np.ndarray:
+    """The degree of the node each REVERSED edge points into, one entry per reversed edge: an
+    edge is reversed where its target is its source's parent in the breadth-first forest from
+    node 0 (the forest of ``layout_fe.build_cp_tables``), so the edge's local direction runs
+    against the forest's. Entries >= 3: reversed edges at junctions."""
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    n = int(max(src.max(), dst.max())) + 1
+    adj = [[] for _ in range(n)]
+    for a, b in zip(src, dst):
+        adj[a].append(int(b))
+        adj[b].append(int(a))
+    depth = np.full(n, -1, dtype=np.int64)
+    depth[0] = 0
+    q = deque([0])
+    while q:
+        u = q.popleft()
+        for w in adj[u]:
+            if depth[w] < 0:
+                depth[w] = depth[u] + 1
+                q.append(w)
+    assert depth.min() >= 0, "connected"
+    rev = depth[dst] < depth[src]
+    return np.asarray(degrees, dtype=np.int64)[dst[rev]]
 
 
 def decomposition_facts(pc) -> dict:
@@ -207,7 +264,10 @@ def cp_record_facts(tab) -> dict:
 # hub fills its record exactly, cat70 stays under both caps, every other hub and broom is past
 # both (hub4 by one each)
 CP_RECORDS = {"hub3": (4, 3), "hub4": (5, 4), "hub5": (6, 5), "hub9": (10, 9),
-              "broom5": (6, 5), "broom33": (34, 33), "cat70": (3, 2)}
+              "broom5": (6, 5), "broom33": (34, 33), "cat70": (3, 2),
+              # (hub70: 71 incident edges at one node; hubhub5x5: the hub of hubs and its five
+              # hubs; rand200_s1: 13 nodes past the caps, the largest with 19 edges)
+              "hub70": (71, 70), "hubhub5x5": (6, 5), "rand200_s1": (19, 19)}
 
 
 def check_cp_records(name: str, tab) -> dict:
