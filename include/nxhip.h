@@ -551,8 +551,8 @@ int nx_fe_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc, cons
  * nx_cp_batch_supported: *ok = 1 when nx_cp_batch_solve takes the batched kernels on this
  * handle, else 0: an nx_create_fe handle with the node-condensed solve attached
  * (nx_fe_set_cp), nx_set_solver(h, 1, 1), one rank (no nx_fe_cp_ranks, not in a group, no
- * ghosts), no chords attached (nx_fe_cp_set_cycles) and at least one edge. (k, 0) and P1/DG0
- * handles give 0.
+ * ghosts), at least one edge, and no chords attached (nx_fe_cp_set_cycles) -- or chords and
+ * nx_set_cp_batch_cycles(h, 1), below. (k, 0) and P1/DG0 handles give 0.
  *
  * nx_cp_batch_solve: the arguments of nx_fe_batch_solve; out = n_cols x n_rows. NX_ERR_STATE
  * where nx_cp_batch_supported says 0, where the matrix has not been assembled for the
@@ -594,9 +594,48 @@ int nx_fe_batch_rhs(nx_network_t* h, int32_t n_cols, const double* edge_bc, cons
  * 5 + U + D with order = 0, whatever its column count. A chunk with a refinement pass adds
  * 4 + U + D.
  *
+ * Graphs with cycles (nx_set_cp_batch_cycles; off by default). With chords attached
+ * (nx_fe_cp_set_cycles) the factor stage above factors the grounded system S_g, and every
+ * column takes the single solve's correction on the batch's own factors,
+ *   x = S_g^-1 (g - U w),   w = (I + C U^T Z)^-1 C U^T x_g,   x_g = S_g^-1 g,
+ * with one refinement of the grounded solve. Once per contents of R (kept across calls; new
+ * boundary values or sources build nothing): U^T Z (k_cp_zcols), I + C U^T Z (k_cp_cap) and its
+ * inverse (k_gj_*) on the call's factors into an ns x ns array the batch owns (ns the border
+ * slots at chord ends, at most 4096; allocated when the switch is set and chords are attached,
+ * freed with the chord tables) -- never the single solve's inverse: the two factor sets differ
+ * in their last bits, and a shared inverse would make a solve's bits depend on the batched calls
+ * before it. The handle's Gauss-Jordan array and column scratch serve the build. Per chunk,
+ * between the node forest's down pass and k_cp_b_back, each with grid = (work, column tiles):
+ *   k_cp_b_cyc_w      y = C U^T x_g per column in LDS, then w = Inv y: a workgroup takes 64 rows
+ *                     of Inv against a tile of 4 columns, each element of Inv read once per
+ *                     tile; a row's sum in 8 strided parts joined in order, no contraction
+ *                     (LDS 32 ns + 16 K bytes: 144 KB at 4096 slots)
+ *   k_cp_b_cyc_rhs    the node right-hand side g - U w (2 per node: 2 n, 2 n + 1)
+ *   k_cp_b_nodes<1> / k_cp_b_level<1>   the forest up and down on that right-hand side
+ *   k_cp_b_cyc_res    the grounded system's node residual of the result
+ *   k_cp_b_nodes<1> / k_cp_b_level<1>   the forest on the residual
+ *   k_cp_b_cyc_add    x_n += the sweep's values
+ * so every solve pass -- a chunk's first and its refinement -- adds 4 + 2 (U + D): S = 10 + 3 (U +
+ * D) with order != 0 and a refinement pass 8 + 3 (U + D). The call that builds the inverse adds
+ * ceil(ns / b) + 2 ns + 2, b the column batch of nx_fe_cp_set_cycles (min(ns, 512) unless the
+ * forest has more than 32768 nodes). Per column the workspace grows by ns + 6 nodes doubles. A
+ * zero pivot in the build marks the batch's correction failed: nx_cp_batch_supported says 0
+ * from then on, and that call's columns miss the residual check and take the single-column
+ * route. A failed allocation of the inverse leaves nx_cp_batch_supported at 0.
+ *
+ * nx_set_cp_batch_cycles: handle state, enable = 0 / 1 (NX_ERR_ARG otherwise, and for a NULL
+ * handle). It may be set before or after the chords are attached. Without it a handle with
+ * chords says 0 to nx_cp_batch_supported, as before.
+ * nx_get_cp_batch_cycles: the flag, whether the last nx_cp_batch_solve / nx_cp_batch_gradient
+ * applied the correction, and the batch's own builds of the inverse so far (NULL outputs are
+ * skipped). nx_get_cp_cycles's figures are the single solve's and do not move with the batch.
+ *
  * nx_cp_batch_rhs (test hook): k_fe_b_rhs alone; out = n_cols x n_rows, device layout.
  */
 int nx_cp_batch_supported(nx_network_t* h, int32_t* ok);
+int nx_set_cp_batch_cycles(nx_network_t* h, int32_t enable);
+int nx_get_cp_batch_cycles(nx_network_t* h, int32_t* enabled, int32_t* applied,
+                           int32_t* builds);
 int nx_cp_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge_bc,
                       const double* edge_f, const double* f_const, double rtol, int32_t maxit,
                       int32_t order, double* out, int32_t* iters, double* relres,
@@ -734,7 +773,11 @@ int nx_fe_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
  * outputs per column); a workspace that an earlier nx_cp_batch_solve allocated without it is
  * allocated again with it, and keeps it. The handle's own factors, coefficients, rhs, x, tmp,
  * published state and snapshots are left as they were. Not served: Hessian-vector products,
- * ensembles (a resistance field per scenario), graphs with cycles and several ranks.
+ * ensembles (a resistance field per scenario), several ranks, and graphs with cycles unless the
+ * handle has opted in (nx_set_cp_batch_cycles): the correction is part of the symmetric
+ * operator, so the forward pass, the adjoint pass and their refinements all go through the
+ * corrected solve, and every edge -- chords included -- contributes to the contraction through
+ * its own rows. The inverse is built at most once per call, before kind 0's adjoint column.
  *
  * Launches (nx_get_batch_info reports the call; refined: forward plus adjoint columns). With
  * U / D the launches of the node forest's up / down pass (nx_cp_batch_solve), the factor stage
@@ -743,7 +786,9 @@ int nx_fe_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
  *   kind 1   per chunk  1 (rhs) + P + 1 (k_b_obs) + P + 1 (k_cp_b_edge_form)
  *   kind 0   per call   F + 1 (k_b_obs) + P;  per chunk  1 + P + 1 + 1
  *   kind 1   per call   F
- * A refinement pass adds P; a flushed assembly adds 1.
+ * A refinement pass adds P; a flushed assembly adds 1. A graph with cycles
+ * (nx_set_cp_batch_cycles): P = 8 + 3 (U + D), and the call that builds the inverse adds
+ * nx_cp_batch_solve's build launches.
  */
 int nx_cp_batch_gradient(nx_network_t* h, int32_t n_cols, const double* edge_bc,
                          const double* edge_f, const double* f_const, double rtol, int32_t maxit,

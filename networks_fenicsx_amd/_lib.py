@@ -63,6 +63,8 @@ _SIGS = {
     "nx_cp_batch_solve": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _pd, _pi32, _pd,
                                     _pi32]),
     "nx_cp_batch_rhs": (C.c_int, [_h, _i32, _pd, _pd, _pd, _pd]),
+    "nx_set_cp_batch_cycles": (C.c_int, [_h, _i32]),
+    "nx_get_cp_batch_cycles": (C.c_int, [_h, _pi32, _pi32, _pi32]),
     "nx_batch_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _pi32, _pd, _pd,
                                     _pd, _pd, _pd, _pd, _pi32, _pd, _pi32]),
     "nx_fe_batch_gradient": (C.c_int, [_h, _i32, _pd, _pd, _pd, _f64, _i32, _i32, _i32, _pi32, _pd,
@@ -510,6 +512,21 @@ class Handle:
         ok = C.c_int32(0)
         check(lib().nx_cp_batch_supported(self.ptr, C.byref(ok)))
         return bool(ok.value)
+
+    def set_cp_batch_cycles(self, enable: bool) -> None:
+        """``nx_set_cp_batch_cycles``: let ``nx_cp_batch_solve`` / ``nx_cp_batch_gradient`` take
+        this continuous-pressure handle's graph with cycles (the chord correction per column,
+        on the batch's own capacitance inverse)."""
+        check(lib().nx_set_cp_batch_cycles(self.ptr, 1 if enable else 0))
+
+    def cp_batch_cycles_info(self) -> dict:
+        """``nx_get_cp_batch_cycles``: ``enabled``, ``applied`` -- the last batched call used
+        the correction -- and ``builds``, the batch's own builds of the capacitance inverse
+        (once per contents of R; the single solve's are :meth:`cp_cycles`)."""
+        v = [C.c_int32(0) for _ in range(3)]
+        check(lib().nx_get_cp_batch_cycles(self.ptr, *[C.byref(x) for x in v]))
+        return {"enabled": bool(v[0].value), "applied": bool(v[1].value),
+                "builds": int(v[2].value)}
 
     def cp_batch_solve(self, edge_bc, edge_f=None, f_const=None, rtol: float = 1e-12,
                        maxit: int = 50000, blocks: bool = True):

@@ -8759,6 +8759,16 @@ struct nx_network {
   void* cp_bws = nullptr;
   int cp_bws_cap = 0;
   size_t cp_bws_bytes = 0;
+  // nx_set_cp_batch_cycles: the batched calls take this handle's graph with cycles. The batch's
+  // own capacitance inverse (cpb_inv, cpc_ns^2, transposed as cpc_inv; built on the workspace's
+  // factors, whose last bits differ from the single solve's, so the two never share one), R's
+  // version it was built for, a singular build (the handle then refuses the batch), the builds
+  // so far and whether the last batched call applied the correction
+  bool cpb_on = false;
+  double* cpb_inv = nullptr;
+  int64_t cpb_version = -1;
+  bool cpb_failed = false, cpb_last = false;
+  int cpb_builds = 0;
 };
 
 struct nx_group {
@@ -11231,6 +11241,24 @@ static void cp_batch_free(nx_network* h) {
   h->cp_bws_cap = 0;
   h->cp_bws_bytes = 0;
 }
+// The batch's capacitance inverse on a graph with cycles (nx_set_cp_batch_cycles). It belongs
+// to the chord tables, not to the column workspace: freed with them (cpc_clear) and in
+// nx_destroy; a workspace that grows keeps it.
+static void cpb_free(nx_network* h) {
+  if (h->cpb_inv) (void)hipFree(h->cpb_inv);
+  h->cpb_inv = nullptr;
+  h->cpb_version = -1;
+}
+// ... allocated where the switch is on and chords are attached; a failed allocation leaves the
+// handle without it (nx_cp_batch_supported then says 0 and the scenario loop serves)
+static void cpb_alloc(nx_network* h) {
+  if (!h->cpb_on || h->cpc_ns <= 0 || h->cpb_inv) return;
+  if (hipMalloc((void**)&h->cpb_inv, sizeof(double) * (size_t)h->cpc_ns * h->cpc_ns) != hipSuccess) {
+    (void)hipGetLastError();
+    h->cpb_inv = nullptr;
+  }
+  h->cpb_version = -1;
+}
 
 NX_API int nx_destroy(nx_network_t* h) {
   if (h) h->pend_lhs = h->pend_rhs = 0;  // nothing to assemble for a dying handle
@@ -11275,6 +11303,7 @@ NX_API int nx_destroy(nx_network_t* h) {
   if (h->bws) (void)hipFree(h->bws);
   if (h->fe_bws) (void)hipFree(h->fe_bws);
   cp_batch_free(h);
+  cpb_free(h);
   if (h->gobs) (void)hipFree(h->gobs);
   if (h->stash) (void)hipFree(h->stash);
   std::free(h->stash_state);
@@ -15143,6 +15172,9 @@ struct CpBatch {
   double* X;
   int64_t ld;
   double *z, *ge, *hv, *ct, *xn;
+  // a graph with cycles, the sweeps after the first (cp_b_node_up<true>): the per-column node
+  // right-hand side, 2 per node (2 n, 2 n + 1), in place of the node's rows of B and its ge
+  const double* nrhs;
 };
 
 // k_cp_edge's sweep without a right-hand side: per vertex Pi | C | W as the sweep uses them
@@ -15368,7 +15400,10 @@ __global__ __launch_bounds__(64) void k_cp_b_fwd(CpBatch p) {
 
 // One node's condensed right-hand side, one tile of columns: h_n = b rows + sum ge - sum of
 // the children's terms, in cp_node_up's order; then its own term B^T (P^-1 h) for its parent
-// (cp_up_term's expressions). i: the node's level-order index.
+// (cp_up_term's expressions). i: the node's level-order index. kNodeRhs: the b rows and the
+// ge sum come ready per column from p.nrhs (a graph with cycles: the sweeps on g - U w and on
+// the grounded residual); the children's terms and the node's own as without it.
+template <bool kNodeRhs>
 __device__ __forceinline__ void cp_b_node_up(const CpBatch& p, const CpTree& t, int i,
                                              const CpCols& cl, int nt) {
 #pragma clang fp contract(off)
@@ -15405,9 +15440,15 @@ __device__ __forceinline__ void cp_b_node_up(const CpBatch& p, const CpTree& t, 
   double g[kCpTile][2];
 #pragma unroll
   for (int k = 0; k < kCpTile; ++k) {
-    const double* b = p.B + cl.col[k] * p.ld;
-    g[k][0] = b[pr];
-    g[k][1] = lr >= 0 ? b[lr] : 0.0;
+    if constexpr (kNodeRhs) {
+      const double* q = p.nrhs + cl.col[k] * nn2 + 2 * (int64_t)n;
+      g[k][0] = q[0];
+      g[k][1] = q[1];
+    } else {
+      const double* b = p.B + cl.col[k] * p.ld;
+      g[k][0] = b[pr];
+      g[k][1] = lr >= 0 ? b[lr] : 0.0;
+    }
   }
   auto edge = [&](int e, int end) {
 #pragma unroll
@@ -15425,7 +15466,11 @@ __device__ __forceinline__ void cp_b_node_up(const CpBatch& p, const CpTree& t, 
       g[k][1] -= q[1];
     }
   };
-  if (ni >= 0) {
+  if constexpr (kNodeRhs) {
+    (void)pr;
+    (void)lr;
+    (void)edge;
+  } else if (ni >= 0) {
 #pragma unroll
     for (int j = 0; j < kCpRecInc; ++j)
       if (j < ni) edge(r[4 + 2 * j], r[5 + 2 * j]);
@@ -15506,7 +15551,8 @@ __device__ __forceinline__ void cp_b_node_down(const CpBatch& p, const CpTree& t
 // Levels [L0, L1) of the node forest, a thread per node and tile of columns (blockIdx.y: the
 // tile), a barrier per level -- paid per tile, not per column. rng: a run of wide levels in
 // subtree chunks, one per workgroup (k_cp_nodes_rec's ranges), or null: the levels whole, in
-// one workgroup.
+// one workgroup. kNodeRhs: cp_b_node_up's variant (the down pass is the same for both).
+template <bool kNodeRhs>
 __global__ __launch_bounds__(1024) void k_cp_b_nodes(CpBatch p, CpTree t,
                                                      const int* __restrict__ rng, int L0, int L1,
                                                      int up) {
@@ -15525,7 +15571,7 @@ __global__ __launch_bounds__(1024) void k_cp_b_nodes(CpBatch p, CpTree t,
       hi = t.lev_off[L0 + L + 1];
     }
     for (int i = lo + (int)threadIdx.x; i < hi; i += (int)blockDim.x) {
-      if (up) cp_b_node_up(p, t, i, cl, nt);
+      if (up) cp_b_node_up<kNodeRhs>(p, t, i, cl, nt);
       else cp_b_node_down(p, t, i, cl, nt);
     }
     __syncthreads();
@@ -15533,13 +15579,14 @@ __global__ __launch_bounds__(1024) void k_cp_b_nodes(CpBatch p, CpTree t,
 }
 
 // One level [i0, i1) of level-order nodes across the grid (a wide level)
+template <bool kNodeRhs>
 __global__ __launch_bounds__(256) void k_cp_b_level(CpBatch p, CpTree t, int i0, int i1, int up) {
   const int i = i0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= i1) return;
   const int c0 = (int)blockIdx.y * kCpTile;
   const int nt = min(kCpTile, p.ncols - c0);
   const CpCols cl = cp_cols(p.list, c0, nt);
-  if (up) cp_b_node_up(p, t, i, cl, nt);
+  if (up) cp_b_node_up<kNodeRhs>(p, t, i, cl, nt);
   else cp_b_node_down(p, t, i, cl, nt);
 }
 
@@ -15666,6 +15713,197 @@ __global__ __launch_bounds__(64) void k_cp_b_back(CpBatch p, const int* __restri
         if (lr >= 0) x[lr] = accum ? x[lr] + xn[2 * n + 1] : xn[2 * n + 1];
       }
   }
+}
+
+// ---- the batch on a graph with cycles (nx_set_cp_batch_cycles): fe_cp_solve's
+// chord correction per column, x = S_g^-1 (g - U w), w = (I + C U^T Z)^-1 C U^T x_g, on the
+// batch's own factors and its own inverse. Every kernel has grid = (work, column tiles); every
+// sum of a column runs in a fixed order that depends on the graph alone, so a column's bits do
+// not depend on its batch, its position or its chunk.
+constexpr int kCpcRows = 64, kCpcParts = 8;  // k_cp_b_cyc_w: rows of w per workgroup, column parts
+inline size_t cp_b_cyc_lds(int ns) {
+  return sizeof(double) * kCpTile * ((size_t)ns + kCpcRows * kCpcParts);
+}
+
+// w = Inv y for a tile of columns, y = C U^T x_g (k_cp_cyc_w's sums over the slot entry
+// tables, p.xn the first sweep's node values): every workgroup forms the tile's y in LDS (ns x
+// kCpTile, slot-major), then takes kCpcRows rows of Inv against it -- a row's sum in kCpcParts
+// column parts (stride kCpcParts) joined in part order, each element of Inv read once per tile
+// (the lanes of a wave hold consecutive rows: capT[j ns + i] = Inv[i][j] is unit stride, and
+// y[j] is one LDS address for the whole wave). LDS: cp_b_cyc_lds(ns), 144 KB at 4096 slots.
+__global__ __launch_bounds__(kCpcRows* kCpcParts) void k_cp_b_cyc_w(
+    CpBatch p, CpCyc c, const double* __restrict__ capT, double* __restrict__ w) {
+#pragma clang fp contract(off)
+  extern __shared__ double cbw_y[];
+  constexpr int T = kCpcRows * kCpcParts;
+  const int ns = c.ns;
+  double* part = cbw_y + (size_t)ns * kCpTile;
+  const int c0 = (int)blockIdx.y * kCpTile;
+  const int nt = min(kCpTile, p.ncols - c0);
+  const CpCols cl = cp_cols(p.list, c0, nt);
+  const int64_t nn2 = 2 * (int64_t)p.nn;
+  for (int r = threadIdx.x; r < ns; r += T) {
+    const int s = c.slot[r] & 1;
+    double v[kCpTile];
+#pragma unroll
+    for (int t = 0; t < kCpTile; ++t) v[t] = 0.0;
+    for (int k = c.ent_off[r]; k < c.ent_off[r + 1]; ++k) {
+      const int* en = c.ent + 4 * k;
+      double cp, cm;
+      cp_cyc_coef(p.a.se, en, s, &cp, &cm);
+      const int64_t on = c.slot[en[2]] >> 1;  // the other end's node
+#pragma unroll
+      for (int t = 0; t < kCpTile; ++t) {
+        const double* xq = p.xn + cl.col[t] * nn2 + 2 * on;
+        v[t] += cp * xq[0];
+        if (en[3] >= 0) v[t] += cm * xq[1];
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < kCpTile; ++t) cbw_y[(size_t)r * kCpTile + t] = v[t];
+  }
+  __syncthreads();
+  const int li = threadIdx.x % kCpcRows, pq = threadIdx.x / kCpcRows;
+  const int i = (int)blockIdx.x * kCpcRows + li;
+  double s[kCpTile];
+#pragma unroll
+  for (int t = 0; t < kCpTile; ++t) s[t] = 0.0;
+  if (i < ns)
+    for (int j = pq; j < ns; j += kCpcParts) {
+      const double a = capT[(int64_t)j * ns + i];
+      const double* y = cbw_y + (size_t)j * kCpTile;
+#pragma unroll
+      for (int t = 0; t < kCpTile; ++t) s[t] += a * y[t];
+    }
+#pragma unroll
+  for (int t = 0; t < kCpTile; ++t) part[(pq * kCpcRows + li) * kCpTile + t] = s[t];
+  __syncthreads();
+  if (pq == 0 && i < ns) {
+#pragma unroll
+    for (int t = 0; t < kCpTile; ++t)
+      if (t < nt) {
+        double o = part[li * kCpTile + t];
+        for (int q = 1; q < kCpcParts; ++q) o += part[(q * kCpcRows + li) * kCpTile + t];
+        w[cl.col[t] * ns + i] = o;
+      }
+  }
+}
+
+// The second sweep's node right-hand side g - U w, one node and one tile of columns per
+// thread, 2 per node (2 n, 2 n + 1): the node's rows of B plus its edges' ge in cp_b_node_up's
+// order (so without chords at the node it is that sweep's sum, bit for bit), minus w at the
+// node's slots.
+__global__ __launch_bounds__(256) void k_cp_b_cyc_rhs(CpBatch p, CpTree t,
+                                                      const int* __restrict__ slot_of, int ns,
+                                                      const double* __restrict__ w,
+                                                      double* __restrict__ nb2) {
+#pragma clang fp contract(off)
+  const int n = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (n >= t.nn) return;
+  const int c0 = (int)blockIdx.y * kCpTile;
+  const int nt = min(kCpTile, p.ncols - c0);
+  const CpCols cl = cp_cols(p.list, c0, nt);
+  const int64_t E = p.a.E, nn2 = 2 * (int64_t)p.nn;
+  const int pr = p.a.nrow[2 * n], lr = p.a.nrow[2 * n + 1];
+  double g[kCpTile][2];
+#pragma unroll
+  for (int k = 0; k < kCpTile; ++k) {
+    const double* b = p.B + cl.col[k] * p.ld;
+    g[k][0] = b[pr];
+    g[k][1] = lr >= 0 ? b[lr] : 0.0;
+  }
+  for (int j = t.inc_off[n]; j < t.inc_off[n + 1]; ++j) {
+    const int e = t.inc[2 * j], end = t.inc[2 * j + 1];
+#pragma unroll
+    for (int k = 0; k < kCpTile; ++k) {
+      const double* q = p.ge + cl.col[k] * 4 * E + 4 * (int64_t)e + 2 * end;
+      g[k][0] += q[0];
+      g[k][1] += q[1];
+    }
+  }
+  const int j0 = slot_of[2 * n], j1 = slot_of[2 * n + 1];
+#pragma unroll
+  for (int k = 0; k < kCpTile; ++k)
+    if (k < nt) {
+      const double* wq = w + cl.col[k] * ns;
+      if (j0 >= 0) g[k][0] -= wq[j0];
+      if (j1 >= 0) g[k][1] -= wq[j1];
+      double* o = nb2 + cl.col[k] * nn2 + 2 * (int64_t)n;
+      o[0] = g[k][0];
+      o[1] = g[k][1];
+    }
+}
+
+// The grounded system's node residual of the second sweep's x per column (k_cp_cyc_res's
+// expressions in its order; nb2 already holds the ge sums): rho_n = nb2_n - D_n x_n - B_n
+// x_parent - sum_children B_c^T x_c, the blocks loaded once per tile.
+__global__ __launch_bounds__(256) void k_cp_b_cyc_res(CpBatch p, CpTree t,
+                                                      const double* __restrict__ nb2,
+                                                      double* __restrict__ rho) {
+#pragma clang fp contract(off)
+  const int n = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (n >= t.nn) return;
+  const int c0 = (int)blockIdx.y * kCpTile;
+  const int nt = min(kCpTile, p.ncols - c0);
+  const CpCols cl = cp_cols(p.list, c0, nt);
+  const int64_t nn2 = 2 * (int64_t)p.nn;
+  const double* se = p.a.se;
+  double D[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int j = t.inc_off[n]; j < t.inc_off[n + 1]; ++j) {
+    const int e = t.inc[2 * j], end = t.inc[2 * j + 1];
+    double B[4];
+    cp_block(se, e, end, end, B);
+    for (int q = 0; q < 4; ++q) D[q] += B[q];
+  }
+  double g[kCpTile][2];
+#pragma unroll
+  for (int k = 0; k < kCpTile; ++k) {
+    const double* gq = nb2 + cl.col[k] * nn2 + 2 * (int64_t)n;
+    const double* xq = p.xn + cl.col[k] * nn2 + 2 * (int64_t)n;
+    g[k][0] = gq[0] - (D[0] * xq[0] + D[1] * xq[1]);
+    g[k][1] = gq[1] - (D[2] * xq[0] + D[3] * xq[1]);
+  }
+  const int pp = t.parent[3 * n];
+  if (pp >= 0) {
+    const int pend = t.parent[3 * n + 2];
+    double B[4];
+    cp_block(se, t.parent[3 * n + 1], pend, 1 - pend, B);
+#pragma unroll
+    for (int k = 0; k < kCpTile; ++k) {
+      const double* xq = p.xn + cl.col[k] * nn2 + 2 * (int64_t)pp;
+      g[k][0] -= B[0] * xq[0] + B[1] * xq[1];
+      g[k][1] -= B[2] * xq[0] + B[3] * xq[1];
+    }
+  }
+  for (int q = t.child_off[n]; q < t.child_off[n + 1]; ++q) {
+    const int c = t.child[q], cend = t.parent[3 * c + 2];
+    double B[4];  // child rows x this node's columns
+    cp_block(se, t.parent[3 * c + 1], cend, 1 - cend, B);
+#pragma unroll
+    for (int k = 0; k < kCpTile; ++k) {
+      const double* xq = p.xn + cl.col[k] * nn2 + 2 * (int64_t)c;
+      g[k][0] -= B[0] * xq[0] + B[2] * xq[1];
+      g[k][1] -= B[1] * xq[0] + B[3] * xq[1];
+    }
+  }
+  const bool lam = p.a.nrow[2 * n + 1] >= 0;  // (no multiplier: the dummy stays 0)
+#pragma unroll
+  for (int k = 0; k < kCpTile; ++k)
+    if (k < nt) {
+      double* o = rho + cl.col[k] * nn2 + 2 * (int64_t)n;
+      o[0] = g[k][0];
+      o[1] = lam ? g[k][1] : 0.0;
+    }
+}
+
+// x_n += d_n per column (the refinement sweep's values), grid = (2 nn / 256, columns)
+__global__ __launch_bounds__(256) void k_cp_b_cyc_add(const int* __restrict__ list, int64_t nn2,
+                                                      double* __restrict__ xn,
+                                                      const double* __restrict__ xd) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nn2) return;
+  const int64_t col = list ? list[blockIdx.y] : (int64_t)blockIdx.y;
+  xn[col * nn2 + i] += xd[col * nn2 + i];
 }
 
 // k_cp_b_edge_form: k_b_edge_form / k_fe_b_edge_form for the continuous-pressure layout
@@ -15808,9 +16046,15 @@ __global__ __launch_bounds__(kBlock) void k_cp_b_edge_form(CpFormArgs a) {
   }
 }
 
+// A graph with cycles in the batch: the handle has opted in (nx_set_cp_batch_cycles), the
+// batch's inverse is allocated and no build of it has been found singular.
+bool cp_batch_cyc_on(const nx_network* h) {
+  return h->cpc_ns > 0 && h->cpb_on && h->cpb_inv != nullptr && !h->cpb_failed;
+}
 bool cp_batch_ok(const nx_network* h) {
   return h && h->fe && h->fe_cp && h->solver == 1 && !proc_rank(h) && h->group == nullptr &&
-         h->nranks == 1 && h->n_ghost == 0 && h->cp_Eg == 0 && h->cpc_ns == 0 && h->E > 0;
+         h->nranks == 1 && h->n_ghost == 0 && h->cp_Eg == 0 && h->E > 0 &&
+         (h->cpc_ns == 0 || cp_batch_cyc_on(h));
 }
 
 // The continuous-pressure part of the workspace. Per call: the vertex factors, Se, the node
@@ -15819,6 +16063,9 @@ bool cp_batch_ok(const nx_network* h) {
 struct CpWs {
   double *fac, *se, *Pinv, *fhv, *fctr, *zero;
   double *z, *ge, *hv, *ct, *xn;
+  // a graph with cycles (the switch on; else empty): per column w (ns), the second sweep's
+  // node rhs, the grounded residual and its sweep's values (2 nn each)
+  double *cw, *nb2, *rho, *xd;
   size_t bytes;
 };
 CpWs cp_layout(const nx_network* h, int cap, void* base) {
@@ -15836,6 +16083,11 @@ CpWs cp_layout(const nx_network* h, int cap, void* base) {
   w.hv = k.take(cap * 2 * nn);
   w.ct = k.take(cap * 2 * nn);
   w.xn = k.take(cap * 2 * nn);
+  const bool cyc = h->cpc_ns > 0 && h->cpb_on;
+  w.cw = k.take(cyc ? cap * (int64_t)h->cpc_ns : 0);
+  w.nb2 = k.take(cyc ? cap * 2 * nn : 0);
+  w.rho = k.take(cyc ? cap * 2 * nn : 0);
+  w.xd = k.take(cyc ? cap * 2 * nn : 0);
   w.bytes = 8 * (size_t)k.off + 64;
   return w;
 }
@@ -15899,34 +16151,105 @@ int cp_batch_factor(nx_network* h, const CpWs& wc) {
 
 // X (+)= A^{-1} Bv on nc columns (list: which, device; null: the first nc): the forward
 // sweep, the node forest up and down over cp_level_walk's runs, the back-substitution.
-// Launches: 2 + the forest's up and down runs, whatever nc.
+// Launches: 2 + the forest's up and down runs, whatever nc. A graph with cycles
+// (cp_batch_cyc_on, the inverse built: cp_batch_cyc_build): after the first sweep k_cp_b_cyc_w
+// and k_cp_b_cyc_rhs, the sweep again on g - U w, then the grounded solve's one refinement
+// (k_cp_b_cyc_res, the sweep on the residual, k_cp_b_cyc_add) -- 6 + three times the forest's
+// up and down runs.
+template <bool kNodeRhs>
+int cp_batch_sweep(nx_network* h, const CpBatch& p, const CpTree& tr, int tiles) {
+  const std::vector<int>& lo = h->cp_lev_host;
+  int launches = 0;
+  for (int up = 1; up >= 0; --up)
+    launches += cp_level_walk(
+        h, tr.rec != nullptr, up,
+        [&](const nx_network::CpRun& run) {
+          hipLaunchKernelGGL(k_cp_b_nodes<kNodeRhs>, dim3(run.nch, tiles), dim3(kCpChunk), 0,
+                             h->stream, p, tr, h->cp_rng + run.off, run.L0, run.L1, up);
+        },
+        [&](int L) {
+          hipLaunchKernelGGL(k_cp_b_level<kNodeRhs>, dim3(grid_of(lo[L + 1] - lo[L], 256), tiles),
+                             dim3(256), 0, h->stream, p, tr, lo[L], lo[L + 1], up);
+        },
+        [&](int La, int Lb, bool) {
+          hipLaunchKernelGGL(k_cp_b_nodes<kNodeRhs>, dim3(1, tiles), dim3(1024), 0, h->stream, p,
+                             tr, (const int*)nullptr, La, Lb, up);
+        });
+  return launches;
+}
 int cp_batch_apply(nx_network* h, const BatchWs& ws, const CpWs& wc, const int* list, int nc,
                    const double* Bv, double* Xv, int accum) {
   const CpBatch p{cp_batch_args(h, wc), wc.Pinv, list, nc, h->cp_nn, Bv, Xv, ws.cols.ld,
-                  wc.z, wc.ge, wc.hv, wc.ct, wc.xn};
+                  wc.z, wc.ge, wc.hv, wc.ct, wc.xn, nullptr};
   CpTree tr = cp_batch_tree(h, wc);
   const int tiles = grid_of(nc, kCpTile), eb = grid_of(h->E, 64);
-  const std::vector<int>& lo = h->cp_lev_host;
   hipLaunchKernelGGL(k_cp_b_fwd, dim3(eb, tiles), dim3(64), 0, h->stream, p);
   h->b_launches += 1;
-  for (int up = 1; up >= 0; --up)
-    h->b_launches += cp_level_walk(
-        h, tr.rec != nullptr, up,
-        [&](const nx_network::CpRun& run) {
-          hipLaunchKernelGGL(k_cp_b_nodes, dim3(run.nch, tiles), dim3(kCpChunk), 0, h->stream, p,
-                             tr, h->cp_rng + run.off, run.L0, run.L1, up);
-        },
-        [&](int L) {
-          hipLaunchKernelGGL(k_cp_b_level, dim3(grid_of(lo[L + 1] - lo[L], 256), tiles), dim3(256),
-                             0, h->stream, p, tr, lo[L], lo[L + 1], up);
-        },
-        [&](int La, int Lb, bool) {
-          hipLaunchKernelGGL(k_cp_b_nodes, dim3(1, tiles), dim3(1024), 0, h->stream, p, tr,
-                             (const int*)nullptr, La, Lb, up);
-        });
+  h->b_launches += cp_batch_sweep<false>(h, p, tr, tiles);
+  if (cp_batch_cyc_on(h) && h->cpb_version == h->r_version) {  // wc.xn holds x_g
+    const int ns = h->cpc_ns, nn = h->cp_nn;
+    const CpCyc c{ns, h->cpc_slot, h->cpc_ent_off, h->cpc_ent};
+    const size_t lds = cp_b_cyc_lds(ns);
+    // (opt_in_lds opts a kernel in once, whatever size later calls name: the size at the slot cap)
+    if (lds > 64 * 1024)
+      opt_in_lds(reinterpret_cast<const void*>(k_cp_b_cyc_w), (int)cp_b_cyc_lds(2 * kMaxCyc));
+    hipLaunchKernelGGL(k_cp_b_cyc_w, dim3(grid_of(ns, kCpcRows), tiles),
+                       dim3(kCpcRows * kCpcParts), lds, h->stream, p, c, h->cpb_inv, wc.cw);
+    hipLaunchKernelGGL(k_cp_b_cyc_rhs, dim3(grid_of(nn, 256), tiles), dim3(256), 0, h->stream, p,
+                       tr, h->cpc_slot_of, ns, wc.cw, wc.nb2);
+    CpBatch p2 = p;
+    p2.nrhs = wc.nb2;
+    h->b_launches += 2 + cp_batch_sweep<true>(h, p2, tr, tiles);
+    // one refinement of the grounded solve: its node residual, swept, added
+    hipLaunchKernelGGL(k_cp_b_cyc_res, dim3(grid_of(nn, 256), tiles), dim3(256), 0, h->stream, p,
+                       tr, wc.nb2, wc.rho);
+    CpBatch p3 = p;
+    p3.nrhs = wc.rho;
+    p3.xn = wc.xd;
+    h->b_launches += 2 + cp_batch_sweep<true>(h, p3, tr, tiles);
+    hipLaunchKernelGGL(k_cp_b_cyc_add, dim3(grid_of(2 * (int64_t)nn, 256), nc), dim3(256), 0,
+                       h->stream, list, 2 * (int64_t)nn, wc.xn, wc.xd);
+    h->cpb_last = true;
+  }
   hipLaunchKernelGGL(k_cp_b_back, dim3(eb, tiles), dim3(64), 0, h->stream, p, h->cp_nown, accum);
   h->b_launches += 1;
   HIPCALL(hipGetLastError());
+  return NX_OK;
+}
+
+// The batch's capacitance inverse for the resident R (r_version), on the call's factors
+// (after cp_batch_factor): cpc_build's steps -- U^T Z in column batches (k_cp_zcols), I + C U^T
+// Z (k_cp_cap), its inverse (gj_invert) -- on the workspace's Se / Pinv into cpb_inv, with the
+// handle's cpc_scr / cpc_gj as scratch; the single solve's cpc_inv and its state are not
+// touched. Kept across calls while R's contents stand. A zero pivot marks the batch's
+// correction failed: nx_cp_batch_supported says 0 from then on, and this call's columns, swept
+// without the correction, miss the residual check and take the per-column route.
+// Launches: ceil(ns / cpc_batch) + 1 + 2 ns + 1.
+int cp_batch_cyc_build(nx_network* h, const CpWs& wc) {
+  h->cpb_last = false;
+  if (!cp_batch_cyc_on(h) || h->cpb_version == h->r_version) return NX_OK;
+  const int ns = h->cpc_ns;
+  const CpCyc c{ns, h->cpc_slot, h->cpc_ent_off, h->cpc_ent};
+  CpTree tr = cp_batch_tree(h, wc);
+  for (int j0 = 0; j0 < ns; j0 += h->cpc_batch) {
+    hipLaunchKernelGGL(k_cp_zcols, dim3(std::min(h->cpc_batch, ns - j0)), dim3(256), 0, h->stream,
+                       wc.se, tr, c, j0, h->cpc_scr, h->cpb_inv);
+    h->b_launches += 1;
+  }
+  int* bad = reinterpret_cast<int*>(h->cpc_gj + 2 * (size_t)ns * ns);
+  HIPCALL(hipMemsetAsync(bad, 0, sizeof(int), h->stream));
+  hipLaunchKernelGGL(k_cp_cap, dim3(std::min(4096, grid_of(2 * (int64_t)ns * ns, 256))), dim3(256),
+                     0, h->stream, wc.se, c, h->cpb_inv, h->cpc_gj);
+  int b = 0;
+  CHECK(gj_invert(h->stream, h->cpc_gj, ns, bad, h->cpb_inv, &b));
+  h->b_launches += 1 + 2 * ns + 1;
+  if (b != 0) {
+    h->cpb_failed = true;
+    h->cpb_version = -1;
+    return NX_OK;
+  }
+  h->cpb_version = h->r_version;
+  h->cpb_builds += 1;
   return NX_OK;
 }
 
@@ -15942,6 +16265,28 @@ int cp_batch_state(nx_network* h, const char* who) {
 NX_API int nx_cp_batch_supported(nx_network_t* h, int32_t* ok) {
   if (!h || !ok) return fail(NX_ERR_ARG, "null argument");
   *ok = cp_batch_ok(h) ? 1 : 0;
+  return NX_OK;
+}
+
+NX_API int nx_set_cp_batch_cycles(nx_network_t* h, int32_t enable) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (enable != 0 && enable != 1) return fail(NX_ERR_ARG, "enable: 0 or 1");
+  h->cpb_on = enable != 0;
+  // (switched off, the inverse stays with the chord tables: a second solver on the same handle
+  // that leaves the switch off does not make the first one build again)
+  if (h->cpb_on && h->cpc_ns > 0 && !h->cpb_inv) {
+    CHECK(set_device(h));
+    cpb_alloc(h);
+  }
+  return NX_OK;
+}
+
+NX_API int nx_get_cp_batch_cycles(nx_network_t* h, int32_t* enabled, int32_t* applied,
+                                  int32_t* builds) {
+  if (!h) return fail(NX_ERR_ARG, "null handle");
+  if (enabled) *enabled = h->cpb_on ? 1 : 0;
+  if (applied) *applied = h->cpb_last ? 1 : 0;
+  if (builds) *builds = h->cpb_builds;
   return NX_OK;
 }
 
@@ -15983,6 +16328,7 @@ NX_API int nx_cp_batch_solve(nx_network_t* h, int32_t n_cols, const double* edge
   const BatchWs ws = batch_carve(h);
   const CpWs wc = cp_layout(h, h->cp_bws_cap, h->cp_bws);
   CHECK(cp_batch_factor(h, wc));
+  CHECK(cp_batch_cyc_build(h, wc));  // (a graph with cycles: once per contents of R)
   // the policy's operator: the right-hand-side sweeps on the call's factors (the refinement
   // accumulates into ws.X); the single-column route is fe_cp_solve on the handle's own arrays,
   // then MINRES capped at maxit, and where that ends unconverged and no better, the refined
@@ -16512,6 +16858,7 @@ NX_API int nx_cp_batch_gradient(nx_network_t* h, int32_t n_cols, const double* e
   // the factor stage depends on the resident R alone: once per call, for the forward pass, the
   // adjoint pass and their refinements
   CHECK(cp_batch_factor(h, wc));
+  CHECK(cp_batch_cyc_build(h, wc));  // (a graph with cycles: once per contents of R)
   auto pass = [&](int nc, const double* Bv, double* Xv, BatchStatus st,
                   std::vector<double>& stats) {
     return batch_solve_cols(
@@ -17963,6 +18310,9 @@ static int cpc_clear(nx_network* h) {
   h->cpc_version = -1;
   h->cpc_failed = false;
   h->cpc_last = false;
+  cpb_free(h);  // (the batch's inverse is laid out for the slots that leave)
+  h->cpb_failed = false;
+  h->cpb_last = false;
   return NX_OK;
 }
 
@@ -18065,6 +18415,7 @@ static int cpc_attach(nx_network* h, int32_t n_chords, const int32_t* chord, int
   HIPCALL(hipStreamSynchronize(h->stream));
   h->cpc_batch = batch;
   h->cpc_ns = ns;
+  cpb_alloc(h);  // (nx_set_cp_batch_cycles before the chords: the batch's inverse now)
   return NX_OK;
 }
 

@@ -1020,19 +1020,22 @@ def cp_apply_model(lay: FeLayout, tab: CpTables, fm: dict, Bm: np.ndarray, R: np
     operation is elementwise over the columns, in the kernels' order, so a column's bits do
     not depend on the columns beside it."""
     Bm = np.ascontiguousarray(Bm, dtype=np.float64)
+    z, ge = _cp_fwd_model(lay, tab, fm, Bm, R, cell_h)
+    xn = _cp_sweep_model(tab, fm, _cp_node_rhs_model(tab, Bm, ge))
+    return _cp_back_model(lay, tab, fm, Bm, R, cell_h, z, xn)
+
+
+def _cp_fwd_model(lay, tab, fm, Bm, R, cell_h):
+    """k_cp_b_fwd: per column z = Pi rho per vertex ``(E, N + 1, 2, nc)`` and ge per edge
+    ``(E, 4, nc)``."""
     nc = Bm.shape[0]
     N, k, m, nI, E = lay.N, lay.k, lay.m, tab.nI, lay.E
     nf = k * N + 1
     per = nf + m * N - 1
     Ch = np.asarray(tab.cst[16:16 + 4 * nI], dtype=np.float64).reshape(4, nI)
-    Eh = np.asarray(tab.cst[16 + 4 * nI:16 + 8 * nI], dtype=np.float64).reshape(nI, 4)
-    Fh = np.asarray(tab.cst[16 + 8 * nI:16 + 8 * nI + nI * nI],
-                    dtype=np.float64).reshape(nI, nI)
     tI = [int(t) for t in tab.tI]
-    eb = tab.eb.reshape(-1, 4)
-    nrow = tab.nrow.reshape(-1, 2)
     h = np.asarray(cell_h, dtype=np.float64).reshape(E, N)
-    fac, Se, Pinv = fm["fac"], fm["Se"], fm["Pinv"]
+    fac = fm["fac"]
     zero = np.zeros(nc)
 
     def lrow(c, i):  # cell c's interior node i (local row)
@@ -1080,20 +1083,42 @@ def cp_apply_model(lay: FeLayout, tab: CpTables, fm: dict, Bm: np.ndarray, R: np
                 rho = rn
         for r in range(4):
             ge[e, r] = gb[r]
+    return z, ge
+
+
+def _cp_node_rhs_model(tab, Bm, ge):
+    """The node right-hand side ``(n, 2, nc)``: a node's rows of B plus its edges' ge in list
+    order (cp_b_node_up's first sums; k_cp_b_cyc_rhs before it subtracts w)."""
+    nc = Bm.shape[0]
     n = tab.n_nodes
     inc = tab.inc.reshape(-1, 2)
+    nrow = tab.nrow.reshape(-1, 2)
+    g = np.zeros((n, 2, nc))
+    for nd in range(n):
+        g0 = Bm[:, nrow[nd, 0]].copy()
+        g1 = Bm[:, nrow[nd, 1]].copy() if nrow[nd, 1] >= 0 else np.zeros(nc)
+        for j in range(tab.inc_off[nd], tab.inc_off[nd + 1]):
+            e, end = inc[j]
+            g0 = g0 + ge[e, 2 * end]
+            g1 = g1 + ge[e, 2 * end + 1]
+        g[nd, 0], g[nd, 1] = g0, g1
+    return g
+
+
+def _cp_sweep_model(tab, fm, g):
+    """k_cp_b_nodes / k_cp_b_level on the node right-hand sides ``g`` ``(n, 2, nc)``: up (minus
+    the children's terms, the node's own term for its parent), then down; returns the node
+    values ``(n, 2, nc)``."""
+    Se, Pinv = fm["Se"], fm["Pinv"]
+    n = tab.n_nodes
+    nc = g.shape[2]
     par = tab.parent.reshape(-1, 3)
     hv, ct, xn = np.zeros((n, 2, nc)), np.zeros((n, 2, nc)), np.zeros((n, 2, nc))
     lev = tab.lev_off
     for L in range(lev.size - 2, -1, -1):
         for i in range(lev[L], lev[L + 1]):
             nd = tab.order[i]
-            g0 = Bm[:, nrow[nd, 0]].copy()
-            g1 = Bm[:, nrow[nd, 1]].copy() if nrow[nd, 1] >= 0 else zero.copy()
-            for j in range(tab.inc_off[nd], tab.inc_off[nd + 1]):
-                e, end = inc[j]
-                g0 = g0 + ge[e, 2 * end]
-                g1 = g1 + ge[e, 2 * end + 1]
+            g0, g1 = g[nd, 0].copy(), g[nd, 1].copy()
             for j in range(tab.child_off[nd], tab.child_off[nd + 1]):
                 c = tab.child[j]
                 g0 = g0 - ct[c, 0]
@@ -1118,6 +1143,29 @@ def cp_apply_model(lay: FeLayout, tab: CpTables, fm: dict, Bm: np.ndarray, R: np
             Pn = [float(v) for v in Pinv[nd]]
             xn[nd, 0] = Pn[0] * r0 + Pn[1] * r1
             xn[nd, 1] = Pn[2] * r0 + Pn[3] * r1
+    return xn
+
+
+def _cp_back_model(lay, tab, fm, Bm, R, cell_h, z, xn):
+    """k_cp_b_back: the columns' solutions ``(nc, n_rows)`` from z and the node values."""
+    nc = Bm.shape[0]
+    N, k, m, nI, E = lay.N, lay.k, lay.m, tab.nI, lay.E
+    nf = k * N + 1
+    per = nf + m * N - 1
+    Eh = np.asarray(tab.cst[16 + 4 * nI:16 + 8 * nI], dtype=np.float64).reshape(nI, 4)
+    Fh = np.asarray(tab.cst[16 + 8 * nI:16 + 8 * nI + nI * nI],
+                    dtype=np.float64).reshape(nI, nI)
+    tI = [int(t) for t in tab.tI]
+    eb = tab.eb.reshape(-1, 4)
+    nrow = tab.nrow.reshape(-1, 2)
+    h = np.asarray(cell_h, dtype=np.float64).reshape(E, N)
+    fac = fm["fac"]
+    n = tab.n_nodes
+    zero = np.zeros(nc)
+
+    def lrow(c, i):  # cell c's interior node i (local row)
+        return c * k + 1 + i if tI[i] > 0 else nf + (c * m + 1 + (i - (k - 1))) - 1
+
     X = np.zeros_like(Bm)
     for nd in range(n):
         X[:, nrow[nd, 0]] = xn[nd, 0]
@@ -1160,6 +1208,167 @@ def cp_apply_model(lay: FeLayout, tab: CpTables, fm: dict, Bm: np.ndarray, R: np
                     X[:, base + lrow(i, j)] = val
             yn = [y0, y1]
     return X
+
+
+CP_CYC_PARTS = 8  # kCpcParts of csrc/nxhip.hip: the strided parts of a row's sum in k_cp_b_cyc_w
+
+
+def _cp_cyc_tables(tab: CpTables):
+    """The slot tables ``nx_fe_cp_set_cycles`` derives (cpc_attach): ``slot`` (ns,) = 2 node +
+    (0 pressure, 1 multiplier), ``slot_of`` (2 n,) and per slot its node's chord ends in
+    ascending chord order -- ``(chord edge, the node's end, the other end's pressure slot, its
+    multiplier slot or -1)``."""
+    cs = np.asarray(tab.cslot).reshape(-1, 2)
+    slot = [2 * int(a) + int(s) for a, s in cs]
+    slot_of = -np.ones(2 * tab.n_nodes, dtype=np.int64)
+    slot_of[slot] = np.arange(len(slot))
+    eb = tab.eb.reshape(-1, 4)
+    at = [[] for _ in range(tab.n_nodes)]
+    for e in np.asarray(tab.chord):
+        e = int(e)
+        at[int(eb[e, 0])].append((e, 0))
+        at[int(eb[e, 1])].append((e, 1))
+    ent = []
+    for sl in slot:
+        row = []
+        for e, end in at[sl >> 1]:
+            o = int(eb[e, 1 - end])
+            row.append((e, end, int(slot_of[2 * o]), int(slot_of[2 * o + 1])))
+        ent.append(row)
+    return slot, slot_of, ent
+
+
+def _cp_cyc_coef(Se, e, end, s):
+    """cp_cyc_coef: the coupling of row ``s`` of chord ``e``'s end ``end`` to the other end's
+    pressure and multiplier."""
+    S = Se[e]
+    q = 4 * (2 * end + s) + 2 * (1 - end)
+    return float(S[q]), float(S[q + 1])
+
+
+def cp_cyc_factor_model(lay: FeLayout, tab: CpTables, R: np.ndarray, cell_h: np.ndarray) -> dict:
+    """:func:`cp_factor_model` on a graph with cycles, with what ``nx_cp_batch_solve`` builds
+    once per contents of ``R`` on top of it (cp_batch_cyc_build). The chords are absent from
+    the forest's parent and child lists and their diagonal blocks are in the incidence lists,
+    so the factor stage factors the grounded system ``S_g`` as it stands. Then, in the kernels'
+    order: ``UtZ`` (ns, ns) by unit right-hand sides through the stored pivots (k_cp_zcols: the
+    sweeps of :func:`cp_apply_model`'s node part), ``cap = I + C U^T Z`` (k_cp_cap: a row
+    slot's chord ends in list order) and ``inv``, its inverse by Gauss-Jordan elimination with
+    partial pivoting (k_gj_*: the first row of the largest magnitude; the device may contract
+    the elimination's multiply-subtract, so ``inv`` agrees to rounding). ``ok`` is False where
+    a pivot is zero. Without chords it returns :func:`cp_factor_model`'s dict with ``ns = 0``."""
+    fm = cp_factor_model(lay, tab, R, cell_h)
+    fm["ns"] = 0
+    if not np.asarray(tab.chord).size:
+        return fm
+    slot, slot_of, ent = _cp_cyc_tables(tab)
+    ns = len(slot)
+    Se = fm["Se"]
+    unit = np.zeros((tab.n_nodes, 2, ns))
+    for j, sl in enumerate(slot):
+        unit[sl >> 1, sl & 1, j] = 1.0
+    Z = _cp_sweep_model(tab, fm, unit)
+    UtZ = np.stack([Z[sl >> 1, sl & 1] for sl in slot])  # (slot i, column j)
+    cap = np.eye(ns)
+    for r, sl in enumerate(slot):
+        v = cap[r].copy()
+        for e, end, op, om in ent[r]:
+            cp, cm = _cp_cyc_coef(Se, e, end, sl & 1)
+            v = v + cp * UtZ[op]
+            if om >= 0:
+                v = v + cm * UtZ[om]
+        cap[r] = v
+    aug = np.hstack([cap, np.eye(ns)])
+    ok = True
+    for col in range(ns):
+        p = col + int(np.argmax(np.abs(aug[col:, col])))
+        if not abs(aug[p, col]) > 0.0:
+            ok = False
+            break
+        if p != col:
+            aug[[col, p]] = aug[[p, col]]
+        aug[col] = aug[col] * (1.0 / aug[col, col])
+        f = aug[:, col].copy()
+        f[col] = 0.0
+        aug -= f[:, None] * aug[col][None, :]
+    fm.update(ns=ns, slot=slot, slot_of=slot_of, ent=ent, UtZ=UtZ, cap=cap,
+              inv=aug[:, ns:].copy(), ok=ok)
+    return fm
+
+
+def cp_cyc_apply_model(lay: FeLayout, tab: CpTables, fm: dict, Bm: np.ndarray, R: np.ndarray,
+                       cell_h: np.ndarray) -> np.ndarray:
+    """:func:`cp_apply_model` on the factors of :func:`cp_cyc_factor_model`: per column
+    ``fe_cp_solve``'s corrected solve ``x = S_g^-1 (g - U w)``, ``w = inv (C U^T x_g)``, and
+    one refinement of the grounded solve, in the kernels' order --
+
+    * the forward sweep and the node sweep as on a forest: ``x_g``;
+    * k_cp_b_cyc_w: ``y = C U^T x_g`` over the slot entry tables, ``w = inv y`` with a row's
+      sum in ``CP_CYC_PARTS`` strided parts joined in part order;
+    * k_cp_b_cyc_rhs: the node right-hand side (b rows plus ge in list order) minus ``U w``;
+    * the node sweep on it; k_cp_b_cyc_res: its node residual against ``S_g``; the node sweep
+      on the residual; k_cp_b_cyc_add; k_cp_b_back.
+
+    Elementwise over the columns. Without chords (``fm["ns"] == 0``) it is
+    :func:`cp_apply_model`, bit for bit."""
+    if not fm.get("ns"):
+        return cp_apply_model(lay, tab, fm, Bm, R, cell_h)
+    Bm = np.ascontiguousarray(Bm, dtype=np.float64)
+    nc = Bm.shape[0]
+    Se, inv, slot, ent = fm["Se"], fm["inv"], fm["slot"], fm["ent"]
+    ns = fm["ns"]
+    n = tab.n_nodes
+    inc = tab.inc.reshape(-1, 2)
+    par = tab.parent.reshape(-1, 3)
+    nrow = tab.nrow.reshape(-1, 2)
+    z, ge = _cp_fwd_model(lay, tab, fm, Bm, R, cell_h)
+    g = _cp_node_rhs_model(tab, Bm, ge)
+    xg = _cp_sweep_model(tab, fm, g)
+    y = np.zeros((ns, nc))
+    for r, sl in enumerate(slot):
+        v = np.zeros(nc)
+        for e, end, op, om in ent[r]:
+            cp, cm = _cp_cyc_coef(Se, e, end, sl & 1)
+            on = slot[op] >> 1
+            v = v + cp * xg[on, 0]
+            if om >= 0:
+                v = v + cm * xg[on, 1]
+        y[r] = v
+    w = None
+    for q in range(CP_CYC_PARTS):
+        s = np.zeros((ns, nc))
+        for j in range(q, ns, CP_CYC_PARTS):
+            s = s + inv[:, j][:, None] * y[j][None, :]
+        w = s if w is None else w + s
+    g2 = g.copy()
+    for j, sl in enumerate(slot):
+        g2[sl >> 1, sl & 1] = g2[sl >> 1, sl & 1] - w[j]
+    xn = _cp_sweep_model(tab, fm, g2)
+    rho = np.zeros_like(g2)
+    for nd in range(n):
+        D = [0.0] * 4
+        for j in range(tab.inc_off[nd], tab.inc_off[nd + 1]):
+            e, end = inc[j]
+            Bk = _cp_blk(Se, e, end, end)
+            for q in range(4):
+                D[q] += Bk[q]
+        x0, x1 = xn[nd, 0], xn[nd, 1]
+        g0 = g2[nd, 0] - (D[0] * x0 + D[1] * x1)
+        g1 = g2[nd, 1] - (D[2] * x0 + D[3] * x1)
+        if par[nd, 0] >= 0:
+            Bk = _cp_blk(Se, par[nd, 1], par[nd, 2], 1 - par[nd, 2])
+            xp = xn[par[nd, 0]]
+            g0 = g0 - (Bk[0] * xp[0] + Bk[1] * xp[1])
+            g1 = g1 - (Bk[2] * xp[0] + Bk[3] * xp[1])
+        for j in range(tab.child_off[nd], tab.child_off[nd + 1]):
+            c = tab.child[j]
+            Bk = _cp_blk(Se, par[c, 1], par[c, 2], 1 - par[c, 2])
+            g0 = g0 - (Bk[0] * xn[c, 0] + Bk[2] * xn[c, 1])
+            g1 = g1 - (Bk[1] * xn[c, 0] + Bk[3] * xn[c, 1])
+        rho[nd, 0] = g0
+        rho[nd, 1] = g1 if nrow[nd, 1] >= 0 else 0.0
+    xn = xn + _cp_sweep_model(tab, fm, rho)
+    return _cp_back_model(lay, tab, fm, Bm, R, cell_h, z, xn)
 
 
 def cp_edge_form_model(lay: FeLayout, tab: CpTables, x: np.ndarray, mu: np.ndarray,

@@ -227,6 +227,19 @@ class Solver:
             measurements). The option also lets :meth:`gradient` serve these degrees on a
             forest (``nx_cp_batch_gradient``); off, it raises
             ``NotImplementedError`` there.
+        batch_continuous_cycles: with ``batch_continuous`` and an assembler built with
+            ``cycle_direct=True``, let :meth:`solve_many`, ``terminal_conductance`` and
+            :meth:`gradient` take the batched path on a graph with cycles
+            (``nx_set_cp_batch_cycles``: the single solve's chord correction per column, on
+            the batch's own factors and its own capacitance inverse, built once per contents
+            of ``R``; up to 4096 border slots at chord ends). ``None`` reads
+            ``NXHIP_CP_BATCH_CYCLES`` (``"1"`` on; off when unset); an explicit ``False``
+            overrides the environment. Alone -- without ``batch_continuous``, or on an
+            assembler without ``cycle_direct`` -- it changes nothing; off, such a graph takes
+            the per-scenario loop and :meth:`gradient` raises ``NotImplementedError``, as
+            before. :meth:`hessian_vector`, ``R=`` ensembles, several ranks and
+            ``ksp_type="minres"`` are not served on these degrees either way (DESIGN.md
+            section 3m, with the measurements).
     """
 
     def __init__(
@@ -239,6 +252,7 @@ class Solver:
         ensemble_cycles: bool | None = None,
         batch_degrees: bool | None = None,
         batch_continuous: bool | None = None,
+        batch_continuous_cycles: bool | None = None,
     ):
         self._assembler = assembler
         if batch_degrees is None:
@@ -247,6 +261,9 @@ class Solver:
         if batch_continuous is None:
             batch_continuous = os.environ.get("NXHIP_CP_BATCH", "") == "1"
         self._cp_batch = bool(batch_continuous)
+        if batch_continuous_cycles is None:
+            batch_continuous_cycles = os.environ.get("NXHIP_CP_BATCH_CYCLES", "") == "1"
+        self._cp_batch_cycles = bool(batch_continuous_cycles)
         if ensemble_cycles is None:
             ensemble_cycles = os.environ.get("NXHIP_ENS_CYCLES", "") == "1"
         self._ens_cycles = bool(ensemble_cycles)
@@ -333,6 +350,15 @@ class Solver:
                                                     or self.assembler.fe_direct_available))
         # (handle state, set on every call: two solvers on one assembler each get their own)
         h.set_ensemble_cycles(self._ens_cycles)
+        # (the same for the batched continuous-pressure calls' cycle switch, which has no effect
+        # without batch_continuous: set where this solver wants it, and taken back where the
+        # handle itself says another solver left it on. The getattr: handle objects without
+        # the query -- the stubs that the host tests drive this method with -- have never had
+        # the switch on; a real handle pays one C call here)
+        if self._cp_batch and self._cp_batch_cycles:
+            h.set_cp_batch_cycles(True)
+        elif getattr(h, "cp_batch_cycles_info", None) and h.cp_batch_cycles_info()["enabled"]:
+            h.set_cp_batch_cycles(False)
 
     @timed("nxfx:Solver:solve_many")
     def solve_many(self, p_bc, f=None) -> "BatchResult":
@@ -348,7 +374,9 @@ class Solver:
         pressure where ``nx_fe_batch_supported`` holds (``nx_fe_batch_solve``: the condensed
         direct solve with a column dimension), and with ``batch_continuous`` continuous
         pressure on a forest where ``nx_cp_batch_supported`` holds (``nx_cp_batch_solve``: the
-        node-condensed solve factored once per call). Otherwise -- general degrees,
+        node-condensed solve factored once per call) -- and, with ``batch_continuous_cycles``
+        on top, on a graph with cycles whose assembler has ``cycle_direct`` (the chord
+        correction per column). Otherwise -- general degrees,
         ``ksp_type="minres"``,
         ``pc_type="none"``, the lumped mass, the global-memory sweeps, or ``NXHIP_BATCH=0`` --
         the per-scenario loop runs (``"sequential"``): the rhs coefficients alone are set (R
@@ -542,7 +570,9 @@ class Solver:
         node-condensed solve per call, both solves on its factors, the contraction over the
         (k, m) rows); ``rows`` then index the (k, m) system's block order. ``batch_degrees``
         alone does not switch it on. Not served on these degrees: ``R=``,
-        :meth:`hessian_vector`, graphs with cycles and several ranks.
+        :meth:`hessian_vector`, several ranks, and graphs with cycles unless
+        ``batch_continuous_cycles`` is on as well (with ``cycle_direct`` on the assembler: both
+        solves then go through the corrected batched solve, chords included in ``dR`` / ``df``).
 
         ``R`` (``(B, num_edges)`` or ``(B,)`` constants, as :meth:`solve_ensemble`): scenario j
         is evaluated at ``R[j]`` instead of the last ``compute_forms``' R
